@@ -17,6 +17,13 @@ keeps B candidates per GPU per step (N*B per step in total); `--scaling strong` 
 `--config images` is the throughput mode: --images independent 256x256 images per GPU, each
 stepped with the reference's 64 candidates per call, no collective; a step is one optimizer call on every image.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps and prints the headline.  `--full` adds everything else the line can carry:
+the remap on its own, the channel sweeps, the reference's 64-candidate loop, the other scaling mode (N > 1), the CPU
+baseline with its parity check against the measured path, and short child runs of the other configurations.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most
+64 MB; rank 0's arrays), so that two builds can be compared output for output: the inputs are seeded and the same for the
+same arguments.
 """
 import argparse
 import json
@@ -40,6 +47,30 @@ VALU_PEAK_GINSTR = 256 * 4 * 2.4 / 2.0  # G wave64 instructions/s: 1,024 SIMD-32
 # and SIMD with two or more waves resident, v_fma_f32 1.35 ns, v_add_f32 1.16 ns, v_fma_f64 2.3-2.4 ns, v_add/mul_f64 1.85-2.0 ns,
 # v_cvt_f64_f32 1.8 ns): ~165 binary32 (1.3 ns) and ~80 binary64 (2.0 ns) instructions per group iteration
 VALU_SUSTAINED_GINSTR = 1024 * 245.0 / (165 * 1.3 + 80 * 2.0)
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: every array of one run together
+DUMP_SAMPLE_SEED = 0x5EED          # --dump-outputs: the fixed sample of outputs too large to write whole
+DUMP_MAX_MAPS = 64                 # --config images: palette_maps (256 KiB each as float32) of at most this many images
+
+
+def dump_sample(n, k):
+    """Sorted positions of a fixed, seeded sample of k out of n (all n when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(path, arrays):
+    """Write every array as path/<name>.npy: float64 stays float64, everything else becomes float32."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def lib_version():
@@ -71,7 +102,7 @@ def config_extras(args):
                         ("images", ["--config", "images", "--steps", "30"])):
         try:
             env = {k: v for k, v in os.environ.items() if not (_SET_HW_QUEUES and k == "GPU_MAX_HW_QUEUES")}
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--warmup", "5", *extra],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--warmup", "5", *extra],
                                capture_output=True, text=True, timeout=240, env=env)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             d = json.loads(line[-1])
@@ -150,6 +181,20 @@ def bench_images(args, torch, dist, S, world, rank, local_rank, device, force_di
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     errs = batch.errors()
+    if rank == 0 and args.dump_outputs:
+        # this rank's images after their last timed call: the call's result and the state it committed
+        last = [img.last_step() for img in batch.images]
+        maps = dump_sample(len(batch), DUMP_MAX_MAPS)
+        dump_outputs(args.dump_outputs, {
+            "image_ids": np.array(batch.ids, np.float64),
+            "best_error": np.array([e for e, _, _ in last], np.float64),
+            "best_rgb5": np.stack([b for _, b, _ in last]),
+            "best_k": np.array([k for _, _, k in last]),
+            "palette": np.stack([img.palette for img in batch.images]),
+            "sampled_images": maps,
+            "tile_palettes": np.stack([batch.images[i].tile_palettes for i in maps]),
+            "palette_map": np.stack([batch.images[i].palette_map for i in maps]),
+        })
     if rank == 0:
         total = len(batch) * world * args.batch * args.steps  # (ranks hold equal blocks; an image dropped at initialisation is not counted)
         value = total / dt
@@ -213,13 +258,19 @@ def main():
                     help="--config images: one stream and one set of launches per image instead of one launch per stage for all images")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="N > 1: strong (default; --batch candidates per call in total, sharded over the GPUs — north_star's metric) or weak "
-                         "(--batch per GPU); the other mode is measured as an extra")
-    ap.add_argument("--no-extras", action="store_true", help="skip the reference-loop, other-configuration and other-scaling-mode legs")
+                         "(--batch per GPU); --full measures the other mode as an extra")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: remap on its own, channel sweeps, the reference's loop, the other scaling mode, the CPU "
+                         "baseline with its parity check and the other configurations (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the channel, reference-loop, other-configuration and "
+                                                             "other-scaling-mode legs")
     ap.add_argument("--converge", type=int, default=30, help="sweeps of 4,096-candidate calls before the converged leg of reference_batch")
-    ap.add_argument("--no-config-extras", action="store_true", help="skip the short runs of the other configurations (perceptual, dither, images)")
+    ap.add_argument("--no-config-extras", action="store_true", help="--full: skip the short runs of the other configurations (perceptual, dither, images)")
     ap.add_argument("--config", choices=["rgb", "perceptual", "dither", "images"], default="rgb")
     ap.add_argument("--chunk", type=int, default=0, help="candidates per launch group (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
     ap.add_argument("--job-timeout", type=float, default=1500.0,
                     help="typed plainly with --gpus N > 1: seconds after which the launcher ends every rank and exits 124 (0 = none); "
                          "a rank that dies ends the job at once either way (snesimage_amd/launch.py)")
@@ -326,20 +377,23 @@ def main():
     seed = 1
 
     def run(lo, hi, n):
+        """The steps lo..hi-1; the last step's error vector (every candidate's, after the exchange between ranks)."""
+        errors = None
         for i in range(lo, hi):
             method, p, idx, ch, _ = slots[i % len(slots)]
             # the benchmark scores n random candidates on every slot (method 0); the channel sweeps of
             # lib.rs:286-328 are exercised by the tests
-            sharded_step(scorer, S.METHOD_RANDOM, p, idx, ch, seed, i, n)
+            errors = sharded_step(scorer, S.METHOD_RANDOM, p, idx, ch, seed, i, n)
+        return errors
 
     def timed(lo, hi, n):
-        """Barrier + synchronize on both sides, max over ranks (the contract's timed region); seconds."""
+        """Barrier + synchronize on both sides, max over ranks (the contract's timed region); seconds and the last step's errors."""
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(lo, hi, n)
+        errors = run(lo, hi, n)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -348,11 +402,11 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt
+        return dt, errors
 
     # The remap on its own (SURVEY §8d config 2 reports it beside remap + SSIMULACRA2): every candidate's palette_map, no error()
     remap = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_r = min(args.batch, 4096)
         d_cand = torch.from_numpy(S.random_candidates(7, 7, n_r)).to(device)
         d_maps = torch.empty((n_r, 256, 256), dtype=torch.uint8, device=device)
@@ -378,14 +432,23 @@ def main():
     run(0, args.warmup, n_total)
     torch.cuda.synchronize()
     image.timing_enable(2)  # the dominant kernel's bracket only: each event record is a ~4 us bubble in the stream, and these sit inside the timed region
-    dt = timed(args.warmup, args.warmup + args.steps, n_total)
+    dt, last_errors = timed(args.warmup, args.warmup + args.steps, n_total)
     tim = image.timing_read()
     image.timing_enable(False)
-    err, best, _ = image.last_step()
+    err, best, best_k = image.last_step()
+    if rank == 0 and args.dump_outputs:
+        # the last timed step as its caller receives it (every candidate's error, the winner) and the state it committed
+        errors = last_errors.cpu().numpy()
+        rows = dump_sample(errors.size, DUMP_MAX_BYTES // 2 // errors.itemsize)  # half the budget at most: a sample beyond 4M candidates
+        arrays = {"errors": errors[rows], "best_error": np.array([err], np.float64), "best_rgb5": best, "best_k": np.array([best_k]),
+                  "palette": image.palette, "tile_palettes": image.tile_palettes, "palette_map": image.palette_map}
+        if rows.size < errors.size:
+            arrays["errors_rows"] = rows
+        dump_outputs(args.dump_outputs, arrays)
     # Beside the headline, never part of `value`: the channel sweeps of lib.rs:286-328 as the headline issues its random calls —
     # call by call on the scheduler's slots, 32 candidates (the values of one channel) each, three calls per entry
     channel_calls = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         kc = 360  # the channel sweep of one scheduler step at 8 x 15
         base = n_slots + 5000
 
@@ -411,7 +474,7 @@ def main():
     # Beside the headline (never part of `value`): the reference's own batch — 64 candidates per optimizer call (lib.rs:205),
     # sharded over the ranks like the headline — and, on several GPUs, the other scaling mode.
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # The reference's own loop — one optimizer call per scheduler slot, 64 candidates (32 in the channel sweeps), lib.rs:888-933,
         # 191-328 — run through the slot windows (snesimage_run_slots: several calls per launch set, committed in order,
         # bit-identical to call-by-call stepping).  `useful` counts the candidates of calls that took effect; candidates of
@@ -457,7 +520,7 @@ def main():
             n_other = args.batch * world if other == "weak" else args.batch
             ko = max(10, args.steps // 2)
             run(n_slots + 1000, n_slots + 1003, n_other)
-            dto = timed(n_slots + 1003, n_slots + 1003 + ko, n_other)
+            dto, _ = timed(n_slots + 1003, n_slots + 1003 + ko, n_other)
             extras[other] = {"scaling": other, "candidates_per_step": n_other, "value": n_other * ko / dto, "unit": "candidates/s",
                              "ms_per_step": dto / ko * 1e3, "steps": ko}
 
@@ -539,8 +602,9 @@ def main():
         out.update(extras)
         if channel_calls:
             out["channel_calls"] = channel_calls
-        out["remap_only"] = remap
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["remap_only"] = remap
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(img, sub_count, sub_size, flags, tile_palettes, palette)
             # the four candidates the CPU leg scored first, at the head of a 64-candidate list on the measured (group-sparse) path:
             # ties the figures above to results (north_star's bar: 1e-5 relative on the SSIMULACRA2 error)
@@ -556,7 +620,7 @@ def main():
                 raise SystemExit("bench.py: the measured path disagrees with the CPU oracle (max relative error %.3g): the measurement is void" % rel)
     image.close()
     if rank == 0:
-        if world == 1 and args.config == "rgb" and not args.no_extras and not args.no_config_extras:
+        if world == 1 and args.config == "rgb" and args.full and not args.no_extras and not args.no_config_extras:
             out["other_configs"] = config_extras(args)  # (the context above is closed: the children have the GPU to themselves)
         print(json.dumps(out), flush=True)
     if world > 1 or force_dist:
