@@ -41,7 +41,8 @@ enum {
 };
 
 /* OptimizedImage::new — lib.rs:46-65.  rgba: w*h*4 bytes, row-major RGBA8.  w must be 256 (tile
- * stride hard-coded to 32, lib.rs:58,565); h a power of two in [8,256].  sub_count*sub_size <= 253.
+ * stride hard-coded to 32, lib.rs:58,565); h a multiple of 8 in [8,256] (256 x 224, the SNES frame, included; a
+ * 239-row picture is padded to 240 by the caller).  sub_count*sub_size <= 253.
  * device: HIP device ordinal (>= 0). */
 int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t sub_count,
                          uint32_t sub_size, uint32_t flags, int32_t device, snesimage_ctx **out);
@@ -217,6 +218,10 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
  * device were out of memory (n < 0 switches the hook off).  A failed grow returns SNES_ERR_HIP and leaves the context
  * usable: the next call allocates afresh. */
 void snesimage_debug_fail_alloc(int32_t n);
+/* Test hook: while on (non-zero), the group-sparse path's per-candidate storage is filled with 0xff bytes (a NaN in every
+ * float) when it is allocated, so that a read of anything no kernel wrote shows in the results instead of reading the
+ * zeros a fresh allocation often holds.  Applies to storage allocated after the call. */
+void snesimage_debug_poison_alloc(int32_t on);
 /* Launch timing by the library's own HIP events on the stream each launch group runs on (bench.py's roofline leg).
  * While enabled, every scoring launch group records events; timing_read() returns summed milliseconds:
  *   ms3[0] = the whole launch group (all kernels that score one chunk of candidates);

@@ -91,7 +91,7 @@ int32_t enqueue_batched_scoring(hipStream_t st, const snes::BatchArgs *A, uint32
         else hipLaunchKernelGGL(kb_dither_base<0>, dim3(1, 1, K), dim3(512), 0, ps, A, bdead);
     }
     hipLaunchKernelGGL(kb_build_plist, dim3(npx_blocks, 1, K), dim3(256), 0, ps, A, bdead);
-    hipLaunchKernelGGL(kb_base_down, dim3((unsigned)((G.W / 32) * ((G.H + 31) / 32)), 1, K), dim3(256), 0, ps, A, bdead);
+    hipLaunchKernelGGL(kb_base_down, dim3(down_grid(G), 1, K), dim3(256), 0, ps, A, bdead);
     if (split) { HIPCHK(hipEventRecord(side->in, ps)); HIPCHK(hipStreamWaitEvent(whole ? st : bs, side->in, 0)); } // the other stream goes on from here
     // (B's work items are in place since every member's sparse_alloc)
     const bool quad = (size_t)n * K <= c0->sp.h2q_max; // few candidates in all: the H passes with a quad of lanes per row (as score_list does for short lists)

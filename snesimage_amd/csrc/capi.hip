@@ -99,6 +99,7 @@ template <typename T> hipError_t dmalloc(T **p, size_t bytes) {
     }
     return hipMalloc(p, bytes);
 }
+std::atomic<bool> g_poison_alloc{false}; // snesimage_debug_poison_alloc: sparse storage starts as NaN bytes, not as whatever hipMalloc returned
 
 } // namespace
 
@@ -309,7 +310,7 @@ int32_t ensure_source(snesimage_ctx *c) {
                        c->d_img1, c->d_img1T);
     if (G.nscales > 1) {
         DownParams D{}; D.G = G; D.lin0 = c->d_lin0; D.work = c->d_img1; D.workT = c->d_img1T;
-        hipLaunchKernelGGL(k_downscale_chain<false>, dim3((G.W / 32) * ((G.H + 31) / 32), 1), dim3(256), 0, c->stream, D);
+        hipLaunchKernelGGL(k_downscale_chain<false>, dim3(down_grid(G), 1), dim3(256), 0, c->stream, D);
     }
     for (int s = 0; s < G.nscales; s++) {
         HParams Hp{}; Hp.G = G; Hp.K = c->K; Hp.s = s; Hp.npairs = 3; Hp.ncol = c->ncol;
@@ -321,6 +322,10 @@ int32_t ensure_source(snesimage_ctx *c) {
         int ppv = 256 / G.sw[s];
         hipLaunchKernelGGL((k_vpass<false, true, false>), dim3((3 + ppv - 1) / ppv), dim3(256), 0, c->stream, Vp);
     }
+    bool padded = false;
+    for (int s = 0; s < G.nscales; s++) padded = padded || G.th[s] != G.sh[s];
+    if (padded)
+        hipLaunchKernelGGL(k_src_pad_rows, dim3(16, G.nscales), dim3(256), 0, c->stream, G, c->d_sd1, c->d_r1);
     for (int s = 0; s < G.nscales; s++)
         if ((c->fast_mask & (1 << s)) || c->sp.enabled) { // the row-sparse path reads the blocked layouts at every scale
             const int N = G.sw[s] * G.sh[s];
@@ -401,7 +406,7 @@ int32_t score_chunk(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t nc, double
     if (G.nscales > 1) {
         DownParams D{}; D.G = G; D.pack = c->d_pack; D.pal_lin = c->d_pal_lin; D.cand_tab = c->d_cand_tab; D.cand_lab = c->d_cand_lab; D.labpx = c->d_labpx;
         D.work = c->d_work; D.ncol = c->ncol; D.perceptual = c->perceptual ? 1 : 0; D.use_maps = use_maps ? 1 : 0; D.fast_mask = c->fast_mask & ~1; D.maps = c->d_maps; D.tile_pal = c->d_tile_pal; D.sub_size = (int)c->sub_size;
-        hipLaunchKernelGGL(k_downscale_chain<true>, dim3((G.W / 32) * ((G.H + 31) / 32), nc), dim3(256), 0, c->stream, D);
+        hipLaunchKernelGGL(k_downscale_chain<true>, dim3(down_grid(G), nc), dim3(256), 0, c->stream, D);
     }
     const bool fast0 = (c->fast_mask & 1) && (use_maps || !c->perceptual); // scale 0 takes its pixels from the pack (RGB keys) or from the per-candidate maps (dither)
     auto is_fast = [&](int s) { return s == 0 ? fast0 : ((c->fast_mask >> s) & 1) != 0; };
@@ -495,6 +500,7 @@ int32_t sparse_alloc(snesimage_ctx *c, uint32_t need, uint32_t lanes = 1) {
     const size_t ncap = (size_t)lanes * need + 1; // + the base image B
     sp.item_stride = (long long)need * (G.sh[0] / 4) * 3;
     HIPCHK(dmalloc(&sp.store, sizeof(float) * (size_t)S.cand_stride * ncap));
+    if (g_poison_alloc.load()) HIPCHK(hipMemsetAsync(sp.store, 0xff, sizeof(float) * (size_t)S.cand_stride * ncap, c->stream)); // (ordered before B's scan below; sparse_alloc ends with a synchronisation)
     HIPCHK(dmalloc(&sp.cand_tab, sizeof(float) * 8 * ncap));
     if (c->perceptual) {
         dfree(sp.cand_lab); dfree(sp.bitmap);
@@ -636,9 +642,9 @@ int32_t sparse_base_pass(snesimage_ctx *c, int sp_idx, int si, uint32_t n_cand) 
         // in front of the hand-over, which would only delay it (0.267 -> 0.279 ms per 64-candidate call the other way).
         const bool down_with_sweeps = sp.side && n_cand >= sp.h0_min && sp.h0_min > 0;
         sp.base_down_side = down_with_sweeps;
-        if (!down_with_sweeps) hipLaunchKernelGGL(k_base_down, dim3((unsigned)((G.W / 32) * ((G.H + 31) / 32))), dim3(256), 0, c->stream, P); // B: every row of every scale
+        if (!down_with_sweeps) hipLaunchKernelGGL(k_base_down, dim3(down_grid(G)), dim3(256), 0, c->stream, P); // B: every row of every scale
         if (sp.side) { HIPCHK(hipEventRecord(sp.ev_base_in, c->stream)); HIPCHK(hipStreamWaitEvent(bs, sp.ev_base_in, 0)); }
-        if (down_with_sweeps) hipLaunchKernelGGL(k_base_down, dim3((unsigned)((G.W / 32) * ((G.H + 31) / 32))), dim3(256), 0, bs, P);
+        if (down_with_sweeps) hipLaunchKernelGGL(k_base_down, dim3(down_grid(G)), dim3(256), 0, bs, P);
         // (B's work items — every group, from column 0 — are in place since sparse_alloc)
         // wide scales: B rows start at column 0 (list s*kColBuckets) and leave the per-block H checkpoints and the scale-0 XYB plane
         if (sp.h2q_max > 0) hipLaunchKernelGGL(k_sparse_h2q_base, dim3((unsigned)((G.sh[0] / 4 * 3 + 3) / 4), (unsigned)(P.s_first * kColBuckets)), dim3(64), h2_lds(c), bs, P);
@@ -1012,7 +1018,7 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (!rgba || !out) return fail(SNES_ERR_ARG, "null pointer");
     *out = nullptr;
     if (w != 256) return fail(SNES_ERR_ARG, "image width must be 256 (tile stride is fixed at 32, lib.rs:58)");
-    if (h < 8 || h > 256 || (h & (h - 1)) != 0) return fail(SNES_ERR_ARG, "image height must be a power of two in [8,256]");
+    if (h < 8 || h > 256 || (h % 8) != 0) return fail(SNES_ERR_ARG, "image height must be a multiple of 8 in [8,256]");
     if (sub_count < 1 || sub_size < 1 || sub_count > 253 || sub_size > 253 || sub_count * sub_size > 253) return fail(SNES_ERR_ARG, "sub_count*sub_size must be in [1,253]");
     if (device < 0) return fail(SNES_ERR_ARG, "device must be a HIP device ordinal >= 0 (this library has no CPU path)");
     int ndev = 0;
@@ -1052,10 +1058,15 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     Geom &G = c->G;
     G.W = (int)w; G.H = (int)h; G.nscales = 0;
     // ssimulacra2's scale loop tests the size BEFORE downscaling (`if width < 8 || height < 8 { break }` then
-    // `downscale_by_2`), so the last scale computed may be as small as 4 rows: 256x8 -> scales 256x8 and 128x4.
+    // `downscale_by_2`, which rounds up), so the last scale computed may be as small as 4 rows: 256x8 -> scales 256x8 and
+    // 128x4; 256x224 -> 224, 112, 56, 28, 14, 7 rows.  Scale 0 is laid out with its H rows; scales 1.. with the rows of the
+    // power of two P >= H (224: 128, 64, 32, 16, 8), so that every scale from 1 on halves the one before, in whole 4-row
+    // groups, as at a power-of-two height; the rows past th[s] are padding (kernels.hpp).
+    int P2 = 8;
+    while (P2 < (int)h) P2 *= 2;
     for (int s = 0; s < kMaxScales; s++) {
-        if (s > 0 && (G.sw[s - 1] < 8 || G.sh[s - 1] < 8)) break;
-        G.sw[s] = (int)w >> s; G.sh[s] = (int)h >> s; G.nscales = s + 1;
+        if (s > 0 && (G.sw[s - 1] < 8 || G.th[s - 1] < 8)) break;
+        G.sw[s] = (int)w >> s; G.th[s] = s == 0 ? (int)h : (G.th[s - 1] + 1) / 2; G.sh[s] = s == 0 ? (int)h : P2 >> s; G.nscales = s + 1;
     }
     long long off = 0, soff = 0;
     for (int s = 0; s < G.nscales; s++) {
@@ -1065,7 +1076,7 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
         G.off_hout[s] = off; off += 9 * N;
     }
     G.cand_stride = off;
-    for (int s = 0; s < G.nscales; s++) if ((G.sw[s] % 64) == 0 && (G.sh[s] % 64) == 0) c->fast_mask |= 1 << s;
+    for (int s = 0; s < G.nscales; s++) if ((G.sw[s] % 64) == 0 && (G.th[s] % 64) == 0 && G.th[s] == G.sh[s]) c->fast_mask |= 1 << s; // (no padding rows)
     if (const char *e = getenv("SNES_NO_FAST")) { if (atoi(e)) c->fast_mask = 0; }
     c->src_floats = (size_t)soff;
 
@@ -1524,6 +1535,8 @@ int32_t snesimage_timing_read(snesimage_ctx *c, double *ms3, uint64_t *launches,
 
 // test hook: the (n+1)-th workspace allocation from now on fails with hipErrorOutOfMemory (n < 0: off)
 void snesimage_debug_fail_alloc(int32_t n) { g_fail_alloc_in.store(n); }
+// test hook: the group-sparse storage allocated from now on is filled with NaN bytes (0 = off)
+void snesimage_debug_poison_alloc(int32_t on) { g_poison_alloc.store(on != 0); }
 
 int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const float *y, uint32_t n, float *out) {
     if (!x || !out || n == 0) return fail(SNES_ERR_ARG, "bad arguments");

@@ -51,7 +51,7 @@ std::string fmt_f64(double v) { // Rust's `{}` for f64: shortest representation 
 void usage() {
     fprintf(stderr,
             "Usage: snesimage_cli [OPTIONS] <SOURCE_FILENAME> <TARGET_FILENAME>\n\n"
-            "Arguments:\n  <SOURCE_FILENAME>  PNG image, raw RGBA8 file (256 x H x 4 bytes) or synth:SEED\n  <TARGET_FILENAME>  JSON output\n\n"
+            "Arguments:\n  <SOURCE_FILENAME>  PNG image, raw RGBA8 file (256 x H x 4 bytes, H a multiple of 8 up to 256) or synth:SEED\n  <TARGET_FILENAME>  JSON output\n\n"
             "Options:\n  -c, --subpalette-count <N>  [default: 1]\n  -s, --subpalette-size <N>   [default: 7]\n"
             "  -d, --dither\n      --perceptual-palettes\n      --nes\n"
             "      --calls <N>          optimizer calls to run [default: 0]\n      --candidates <N>     random candidates per call [default: 64]\n"
@@ -177,9 +177,12 @@ int main(int argc, char **argv) {
     if (!resume_file.empty()) { // palette + tile_palettes of an earlier output (src/lib.rs:579-625); the tiles follow from optimize()
         std::vector<long> pal, tp;
         if (!json_int_array(resume_file, "palette", pal) || !json_int_array(resume_file, "tile_palettes", tp)) die("cannot read palette and tile_palettes from " + resume_file);
-        if (pal.size() != 16 * (size_t)count || tp.size() != 1024) die("resume file does not match --subpalette-count (palette must hold 16 entries per subpalette, tile_palettes 1024)");
-        std::vector<uint8_t> tp8(1024), rgb5(3 * (size_t)count * size);
-        for (size_t i = 0; i < 1024; i++) { if (tp[i] < 0 || tp[i] >= (long)count) die("resume file: tile palette out of range"); tp8[i] = (uint8_t)tp[i]; }
+        // as_json writes one tile palette per tile of the image (src/lib.rs:598-616): 32 per 8 rows, 1,024 at 256 rows, 896 at 224
+        const size_t ntiles = 32 * (size_t)(h / 8);
+        if (pal.size() != 16 * (size_t)count || tp.size() != ntiles)
+            die("resume file does not match the image and --subpalette-count (palette must hold 16 entries per subpalette, tile_palettes one per 8 x 8 tile: " + std::to_string(ntiles) + ")");
+        std::vector<uint8_t> tp8(1024, 0), rgb5(3 * (size_t)count * size); // (the rows of tiles below the image keep subpalette 0, as after snesimage_create)
+        for (size_t i = 0; i < ntiles; i++) { if (tp[i] < 0 || tp[i] >= (long)count) die("resume file: tile palette out of range"); tp8[i] = (uint8_t)tp[i]; }
         for (uint32_t p = 0; p < count; p++)
             for (uint32_t i = 0; i < size; i++) { // slot 0 of every 16 is the transparent colour (src/lib.rs:583-585)
                 const long v = pal[16 * (size_t)p + 1 + i];

@@ -15,7 +15,10 @@
 //   src scale s       : img1[3][H][W], img1T[3][W][H], mu1[3][H][W], s11[3][H][W] (f32)
 //   per candidate     : xyb_s[3][H][W], xybT_s[3][W][H] (s >= 1), hout_s[9][H][W] (H-pass output),
 //                        part[S][3][6] f64 partial sums
-// Scale s has W_s = W >> s, H_s = H >> s (W = 256, H a power of two).
+// Scale s has W_s = W >> s columns and th_s rows (ssimulacra2: th_0 = H, th_s = (th_{s-1} + 1) / 2; H a multiple of 8).
+// Its planes are laid out with sh_s >= th_s rows: sh_0 = H, sh_s = P >> s for s >= 1, P the power of two >= H, so that
+// every scale >= 1 keeps the power-of-two shape the kernels tile by.  Rows th_s .. sh_s - 1 are padding: their
+// XYB values are 0 (the blur's zero beyond the edge), and the source side makes them add +0.0 to every pooling sum.
 #pragma once
 #include "color.hpp"
 
@@ -36,13 +39,20 @@ struct BlurK { // recursive-Gaussian constants (host-computed in binary64, round
 
 struct Geom {
     int W, H, nscales;
-    int sw[kMaxScales], sh[kMaxScales];
+    int sw[kMaxScales], sh[kMaxScales]; // sh: rows of the layout (a power of two from scale 1 on)
+    int th[kMaxScales];                 // the scale's true rows (th <= sh): what ssimulacra2 computes and pools
     // float offsets inside one candidate's workspace
     long long off_xyb[kMaxScales], off_xybT[kMaxScales], off_hout[kMaxScales];
     long long cand_stride; // floats per candidate
     // float offsets inside the source arrays
     long long src_off[kMaxScales]; // same offset used in img1, img1T, mu1, s11 (each 3*N_s at scale s)
 };
+
+// Blocks of k_downscale_chain / k_base_down: one per 32 x 32 pixels of scale 0, over every row of scale 1's layout
+inline unsigned down_grid(const Geom &G) { return (unsigned)((G.W / 32) * ((2 * G.sh[1] + 31) / 32)); }
+// Row of scale s - 1 that stands for row 2y + 1 in the 2x2 box of row y of scale s (ssimulacra2's downscale_by_2 clamps at
+// the edge: a scale of odd height repeats its last row)
+SNES_HD int down_odd_row(const Geom &G, int s, int y) { return 2 * y + 1 < G.th[s - 1] ? 2 * y + 1 : 2 * y; }
 
 __device__ __constant__ double kSsim2Weight[108] = SSIM2_WEIGHTS; // include/ssimulacra2_constants.h
 
@@ -278,7 +288,7 @@ __global__ __launch_bounds__(256) void k_downscale_chain(DownParams P) {
             for (int iy = 0; iy < 2; iy++)
 #pragma unroll
                 for (int ix = 0; ix < 2; ix++) {
-                    int x0 = X1 * 2 + ix, y0 = Y1 * 2 + iy; // never clamps: W, H are even
+                    int x0 = X1 * 2 + ix, y0 = min(Y1 * 2 + iy, G.H - 1); // (clamped only in padding rows of scale 1, whose XYB is 0)
                     int px = y0 * G.W + x0;
                     if (CAND) {
                         uint32_t ci;
@@ -301,6 +311,7 @@ __global__ __launch_bounds__(256) void k_downscale_chain(DownParams P) {
         float X, Y, B;
         float r = sum[0] * 0.25f, g = sum[1] * 0.25f, b = sum[2] * 0.25f;
         linear_to_positive_xyb(r, g, b, X, Y, B);
+        if (Y1 >= G.th[1]) X = Y = B = 0.0f; // padding row
         l1[0][ly][lx] = r; l1[1][ly][lx] = g; l1[2][ly][lx] = b;
         tr[0][ly][lx] = X; tr[1][ly][lx] = Y; tr[2][ly][lx] = B;
         if (in) {
@@ -330,15 +341,17 @@ __global__ __launch_bounds__(256) void k_downscale_chain(DownParams P) {
             const int XS = bx * DIM + lx, YS = by * DIM + ly;                                                                 \
             const int WS = G.sw[S], HS = G.sh[S];                                                                             \
             float v[3];                                                                                                       \
+            const int ly1 = 2 * ly + (down_odd_row(G, S, YS) - 2 * YS); /* the last row again at an odd height */             \
             for (int c = 0; c < 3; c++) {                                                                                     \
                 float sum = 0.0f;                                                                                             \
                 sum += SRC[c][2 * ly][2 * lx]; sum += SRC[c][2 * ly][2 * lx + 1];                                             \
-                sum += SRC[c][2 * ly + 1][2 * lx]; sum += SRC[c][2 * ly + 1][2 * lx + 1];                                     \
+                sum += SRC[c][ly1][2 * lx]; sum += SRC[c][ly1][2 * lx + 1];                                                   \
                 v[c] = sum * 0.25f; DST[c][ly][lx] = v[c];                                                                    \
             }                                                                                                                 \
             if (YS < HS) {                                                                                                    \
                 float X, Y, B;                                                                                                \
                 linear_to_positive_xyb(v[0], v[1], v[2], X, Y, B);                                                            \
+                if (YS >= G.th[S]) X = Y = B = 0.0f;                                                                          \
                 size_t ns = (size_t)WS * HS;                                                                                  \
                 float *o = wbase + (CAND ? G.off_xyb[S] : G.src_off[S]);                                                      \
                 float *oT = CAND ? (wbase + G.off_xybT[S]) : (P.workT + G.src_off[S]);                                        \
@@ -359,9 +372,11 @@ __global__ __launch_bounds__(256) void k_downscale_chain(DownParams P) {
         const int WS = G.sw[5], HS = G.sh[5];
         if (by < HS) {
             float v[3];
-            for (int c = 0; c < 3; c++) { float sum = 0.0f; sum += l4[c][0][0]; sum += l4[c][0][1]; sum += l4[c][1][0]; sum += l4[c][1][1]; v[c] = sum * 0.25f; }
+            const int o4 = down_odd_row(G, 5, by) - 2 * by;
+            for (int c = 0; c < 3; c++) { float sum = 0.0f; sum += l4[c][0][0]; sum += l4[c][0][1]; sum += l4[c][o4][0]; sum += l4[c][o4][1]; v[c] = sum * 0.25f; }
             float X, Y, B;
             linear_to_positive_xyb(v[0], v[1], v[2], X, Y, B);
+            if (by >= G.th[5]) X = Y = B = 0.0f;
             size_t ns = (size_t)WS * HS;
             float *o = wbase + (CAND ? G.off_xyb[5] : G.src_off[5]);
             float *oT = CAND ? (wbase + G.off_xybT[5]) : (P.workT + G.src_off[5]);
@@ -426,6 +441,22 @@ __device__ __forceinline__ void maps_accumulate(double (&acc)[6], float m1, floa
 __device__ __forceinline__ float source_sd1(float mu1, float sigma11) { const float mu11 = mu1 * mu1; return sigma11 - mu11; }
 __device__ __forceinline__ float source_a1(float img1, float mu1) { return fabsf(img1 - mu1); }
 __device__ __forceinline__ double source_r1(float a1) { return 1.0 / (1.0 + (double)a1); }
+// Padding rows of the source side (th_s <= y < sh_s, scales >= 1): sd1 = NaN and r1 = 0 there, so that maps_accumulate adds
+// +0.0 to all six sums whatever the candidate holds — the SSIM quotient is NaN (d = 0: `d > 0 ? d : 0`), the edge term a
+// finite value times 0 (artifact = detail_lost = 0).  Every V pass (dense, fast, sparse, B's) then pools exactly th_s rows
+// without a test of its own.  Runs between the source V passes and the copies into the blocked layouts.
+__global__ __launch_bounds__(256) void k_src_pad_rows(Geom G, float *__restrict__ sd1, double *__restrict__ r1) {
+    const int s = (int)blockIdx.y;
+    if (s >= G.nscales) return;
+    const int W = G.sw[s], pad = G.sh[s] - G.th[s];
+    const int n = 3 * W * pad;
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int)(gridDim.x * blockDim.x)) {
+        const int c = i / (W * pad), rem = i - c * (W * pad);
+        const size_t idx = (size_t)G.src_off[s] + (size_t)c * W * G.sh[s] + (size_t)G.th[s] * W + rem;
+        sd1[idx] = __builtin_nanf("");
+        r1[idx] = 0.0;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // Horizontal pass of the recursive Gaussian (ssimulacra2 blur/gaussian.rs horizontal_row) for the
@@ -456,7 +487,7 @@ __global__ __launch_bounds__(256) void k_hpass(HParams P) {
     const int ppw = 256 / H;
     const int ql = t / H, y = t - ql * H;
     const int pair_raw = blockIdx.x * ppw + ql;
-    const bool active = pair_raw < P.npairs;
+    const bool active = ql < ppw && pair_raw < P.npairs;
     const int pair = active ? pair_raw : 0;
     const int cand = pair / 3, ch = pair - cand * 3;
     const size_t ns = (size_t)W * H;
@@ -543,7 +574,7 @@ __global__ __launch_bounds__(256) void k_hpass(HParams P) {
                     const int plane = it / (q4 * 256);
                     const int rq = row / H, ry = row - rq * H;
                     const int rpair = blockIdx.x * ppw + rq;
-                    if (rpair < P.npairs) {
+                    if (rq < ppw && rpair < P.npairs) { // (256 / H pairs per block: at a height that does not divide 256 the last threads have none)
                         const int rc = rpair / 3, rch = rpair - rc * 3;
                         float *dst = P.work + (size_t)rc * G.cand_stride + G.off_hout[s] + (size_t)(rch * 3 + plane) * ns + (size_t)ry * W + x0 + c4 * 4;
                         *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(&buf[plane][row][c4 * 4]);
@@ -698,7 +729,7 @@ __device__ __forceinline__ void final_score_body(const double *__restrict__ part
     for (int ch = 0; ch < 3; ch++)
         for (int s = 0; s < G.nscales; s++) {
             const double *p = part + (((size_t)c * G.nscales + s) * 3 + ch) * 6;
-            const double opp = 1.0 / (double)((size_t)G.sw[s] * G.sh[s]);
+            const double opp = 1.0 / (double)((size_t)G.sw[s] * G.th[s]); // (true rows: padding rows add +0.0)
             double avg_ssim[2] = {opp * p[0], sqrt(sqrt(opp * p[1]))};
             double avg_edge[4] = {opp * p[2], sqrt(sqrt(opp * p[3])), opp * p[4], sqrt(sqrt(opp * p[5]))};
             for (int n = 0; n < 2; n++) {
@@ -733,7 +764,7 @@ __device__ __forceinline__ void final_score_wave_body(const double *__restrict__
     if (lane < npair) {
         const int ch = lane / ns, s = lane - ch * ns;
         const double *p = part + (((size_t)c * ns + s) * 3 + ch) * 6;
-        const double opp = 1.0 / (double)((size_t)G.sw[s] * G.sh[s]);
+        const double opp = 1.0 / (double)((size_t)G.sw[s] * G.th[s]); // (true rows: padding rows add +0.0)
         term[0] = opp * p[0]; term[1] = opp * p[2]; term[2] = opp * p[4];                                  // avg_ssim[0], avg_edge[0], avg_edge[2]
         term[3] = sqrt(sqrt(opp * p[1])); term[4] = sqrt(sqrt(opp * p[3])); term[5] = sqrt(sqrt(opp * p[5])); // avg_ssim[1], avg_edge[1], avg_edge[3]
     }

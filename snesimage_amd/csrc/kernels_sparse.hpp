@@ -127,6 +127,10 @@ __device__ __forceinline__ void scan_publish(const SparseParams &P, const int k,
         for (int s = 0; s < kMaxScales; s++) {
             ms[s] = 0ull; cbs[s] = 0;
             if (s < G.nscales) {
+                // B: every group of the scale's layout.  Folding its H/4 groups of scale 0 would miss the groups that are padding
+                // only (a height that is not a power of two: 224 rows leave scale-1 groups 28-31 out); their H output is read by
+                // every V sweep above them (the filter looks 4 rows ahead) and must be computed, not found in the allocation.
+                if (P.is_base && live) { const int ng = G.sh[s] >> 2; m = ng >= 64 ? ~0ull : ((1ull << ng) - 1ull); }
                 const bool flag = ((m >> lane) & 1ull) != 0ull;
                 const int nb = G.sw[s] >= 64 ? (G.sw[s] >> 6) : 1;
                 // a changed input at column x moves the H outputs from column x - 4 on (the filter's right taps reach n + 4)
@@ -513,9 +517,10 @@ __device__ __forceinline__ void sparse_down_body(const SparseParams &P, int only
                 for (int iy = 0; iy < 2; iy++)
 #pragma unroll
                     for (int ix = 0; ix < 2; ix++) {
-                        const unsigned long long w = P.pack[(size_t)(2 * y + iy) * G.W + 2 * x + ix];
-                        const int px0 = (2 * y + iy) * G.W + 2 * x + ix;
-                        const uint32_t ci = P.use_maps ? maps_ci(P, is_base ? P.bmap : P.maps + (size_t)(k - P.k0) * G.W * G.H, is_base, 2 * x + ix, 2 * y + iy, (uint32_t)w)
+                        const int y0 = min(2 * y + iy, G.H - 1); // (clamped in the padding rows of scale 1 only: their XYB is 0)
+                        const unsigned long long w = P.pack[(size_t)y0 * G.W + 2 * x + ix];
+                        const int px0 = y0 * G.W + 2 * x + ix;
+                        const uint32_t ci = P.use_maps ? maps_ci(P, is_base ? P.bmap : P.maps + (size_t)(k - P.k0) * G.W * G.H, is_base, 2 * x + ix, y0, (uint32_t)w)
                                           : is_base ? ((uint32_t)w >> 24)
                                           : (P.perceptual ? (won_bit(P.bitmap + (size_t)k * (G.W * G.H / 32), px0) ? (uint32_t)P.ncol : ((uint32_t)w >> 24))
                                                           : sparse_ci((uint32_t)w, (uint32_t)(w >> 32), crgb, (uint32_t)P.ncol));
@@ -530,7 +535,7 @@ __device__ __forceinline__ void sparse_down_body(const SparseParams &P, int only
 #pragma unroll
                 for (int c = 0; c < 3; c++) { // linear planes in the C4 order: [column quad][row][column & 3]
                     const float *q0 = grp + (size_t)c * 4 * Wp + (size_t)((2 * x) >> 2) * 16 + rp * 4 + ((2 * x) & 3);
-                    const float2 a = *reinterpret_cast<const float2 *>(q0), b = *reinterpret_cast<const float2 *>(q0 + 4);
+                    const float2 a = *reinterpret_cast<const float2 *>(q0), b = *reinterpret_cast<const float2 *>(q0 + (down_odd_row(G, s, y) - 2 * y) * 4);
                     float sum = 0.0f;
                     sum += a.x; sum += a.y; sum += b.x; sum += b.y;
                     v[c] = sum * 0.25f;
@@ -538,6 +543,7 @@ __device__ __forceinline__ void sparse_down_body(const SparseParams &P, int only
             }
             float X, Y, B;
             linear_to_positive_xyb(v[0], v[1], v[2], X, Y, B);
+            if (y >= G.th[s]) X = Y = B = 0.0f; // padding row
             float *ol = mine + P.S.off_lin[s] + (size_t)j * 12 * Ws;
             float *oc = mine + P.S.off_xybC[s] + (size_t)j * 12 * Ws, *orr = mine + P.S.off_xybR[s] + (size_t)j * 12 * Ws;
             const float xyb[3] = {X, Y, B};
@@ -695,15 +701,18 @@ __device__ __forceinline__ void sparse_down_tiles_body(const SparseParams &P, co
             if (live && sl2[u] >= 0) { // (uniform over each half of the wave: rows 0-3 and 4-7 of the tile are the two groups of scale 2)
                 float X, Y, B;
                 linear_to_positive_xyb(v2[0], v2[1], v2[2], X, Y, B);
+                if (y2 >= G.th[2]) X = Y = B = 0.0f; // padding row
                 float *oc = mine + P.S.off_xybC[2] + (size_t)sl2[u] * 12 * W2 + (size_t)(x2 >> 2) * 16 + (y2 & 3) * 4 + (x2 & 3);
                 oc[0] = X; oc[(size_t)4 * W2] = Y; oc[(size_t)8 * W2] = B;
             }
-            // scale 3 inside the tile: the lanes of even row and column hold pixel (4 ty + ly / 2, 4 tx + lx / 2)
+            // scale 3 inside the tile: the lanes of even row and column hold pixel (4 ty + ly / 2, 4 tx + lx / 2); at an odd
+            // height of scale 2 its last row stands in for the row below it
+            const bool odd2 = y2 + 1 < G.th[2];
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 const float b1 = __shfl(v2[c], (lane + 1) & 63), c1 = __shfl(v2[c], (lane + 8) & 63), d1 = __shfl(v2[c], (lane + 9) & 63);
                 float sum = 0.0f;
-                sum += v2[c]; sum += b1; sum += c1; sum += d1;
+                sum += v2[c]; sum += b1; sum += odd2 ? c1 : v2[c]; sum += odd2 ? d1 : b1;
                 if (((ly | lx) & 1) == 0) s_v3[u][c][ly >> 1][4 * tx + (lx >> 1)] = sum * 0.25f;
             }
             }
@@ -720,6 +729,7 @@ __device__ __forceinline__ void sparse_down_tiles_body(const SparseParams &P, co
                 const int r = t >> 5, x = t & 31, Ws = G.sw[3];
                 float X, Y, B;
                 linear_to_positive_xyb(v3[0][r][x], v3[1][r][x], v3[2][r][x], X, Y, B);
+                if (4 * ty + r >= G.th[3]) X = Y = B = 0.0f;
                 float *oc = mine + P.S.off_xybC[3] + (size_t)j3 * 12 * Ws + (size_t)(x >> 2) * 16 + r * 4 + (x & 3);
                 float *orr = mine + P.S.off_xybR[3] + (size_t)j3 * 12 * Ws + (size_t)x * 4 + r;
                 oc[0] = X; oc[(size_t)4 * Ws] = Y; oc[(size_t)8 * Ws] = B;
@@ -731,14 +741,16 @@ __device__ __forceinline__ void sparse_down_tiles_body(const SparseParams &P, co
                     const int y4 = 2 * ty + a4, r = y4 & 3;
                     const int j4 = M->gslot[P.S.goff[4] + (y4 >> 2)];
                     float v[3];
+                    const int o3 = 2 * a4 + (down_odd_row(G, 4, y4) - 2 * y4);
 #pragma unroll
                     for (int c = 0; c < 3; c++) {
                         float sum = 0.0f;
-                        sum += v3[c][2 * a4][2 * x]; sum += v3[c][2 * a4][2 * x + 1]; sum += v3[c][2 * a4 + 1][2 * x]; sum += v3[c][2 * a4 + 1][2 * x + 1];
+                        sum += v3[c][2 * a4][2 * x]; sum += v3[c][2 * a4][2 * x + 1]; sum += v3[c][o3][2 * x]; sum += v3[c][o3][2 * x + 1];
                         v[c] = sum * 0.25f;
                     }
                     float X, Y, B;
                     linear_to_positive_xyb(v[0], v[1], v[2], X, Y, B);
+                    if (y4 >= G.th[4]) X = Y = B = 0.0f;
                     float *oc = mine + P.S.off_xybC[4] + (size_t)j4 * 12 * Ws + (size_t)(x >> 2) * 16 + r * 4 + (x & 3);
                     float *orr = mine + P.S.off_xybR[4] + (size_t)j4 * 12 * Ws + (size_t)x * 4 + r;
                     oc[0] = X; oc[(size_t)4 * Ws] = Y; oc[(size_t)8 * Ws] = B;
@@ -757,17 +769,19 @@ __device__ __forceinline__ void sparse_down_tiles_body(const SparseParams &P, co
                         for (int a4 = 0; a4 < 2; a4++)
 #pragma unroll
                             for (int e = 0; e < 2; e++) {
-                                const int x4 = 2 * x + e;
+                                const int x4 = 2 * x + e, y4 = 2 * ty + a4, o3 = 2 * a4 + (down_odd_row(G, 4, y4) - 2 * y4);
                                 float sum = 0.0f;
-                                sum += v3[c][2 * a4][2 * x4]; sum += v3[c][2 * a4][2 * x4 + 1]; sum += v3[c][2 * a4 + 1][2 * x4]; sum += v3[c][2 * a4 + 1][2 * x4 + 1];
+                                sum += v3[c][2 * a4][2 * x4]; sum += v3[c][2 * a4][2 * x4 + 1]; sum += v3[c][o3][2 * x4]; sum += v3[c][o3][2 * x4 + 1];
                                 v4[a4][e] = sum * 0.25f;
                             }
+                        const int o4 = down_odd_row(G, 5, ty) - 2 * ty;
                         float sum = 0.0f;
-                        sum += v4[0][0]; sum += v4[0][1]; sum += v4[1][0]; sum += v4[1][1];
+                        sum += v4[0][0]; sum += v4[0][1]; sum += v4[o4][0]; sum += v4[o4][1];
                         v[c] = sum * 0.25f;
                     }
                     float X, Y, B;
                     linear_to_positive_xyb(v[0], v[1], v[2], X, Y, B);
+                    if (ty >= G.th[5]) X = Y = B = 0.0f;
                     float *oc = mine + P.S.off_xybC[5] + (size_t)j5 * 12 * Ws + (size_t)(x >> 2) * 16 + r * 4 + (x & 3);
                     float *orr = mine + P.S.off_xybR[5] + (size_t)j5 * 12 * Ws + (size_t)x * 4 + r;
                     oc[0] = X; oc[(size_t)4 * Ws] = Y; oc[(size_t)8 * Ws] = B;
@@ -820,6 +834,7 @@ __device__ __forceinline__ void base_store(const SparseParams &P, float *mine, i
     const int g = Y >> 2, r = Y & 3;
     float Xc, Yc, Bc;
     linear_to_positive_xyb(lin[0], lin[1], lin[2], Xc, Yc, Bc);
+    if (Y >= P.G.th[s]) Xc = Yc = Bc = 0.0f; // padding row
     const float xyb[3] = {Xc, Yc, Bc};
     float *ol = mine + P.S.off_lin[s] + (size_t)g * 12 * Ws;
     float *oc = mine + P.S.off_xybC[s] + (size_t)g * 12 * Ws, *orr = mine + P.S.off_xybR[s] + (size_t)g * 12 * Ws;
@@ -849,8 +864,9 @@ __device__ __forceinline__ void base_down_body(const SparseParams &P) {
             for (int iy = 0; iy < 2; iy++)
 #pragma unroll
                 for (int ix = 0; ix < 2; ix++) {
-                    const uint32_t lo = (uint32_t)P.pack[(size_t)(Y1 * 2 + iy) * G.W + X1 * 2 + ix];
-                    const uint32_t ci = P.use_maps ? maps_ci(P, P.bmap, true, X1 * 2 + ix, Y1 * 2 + iy, lo) : lo >> 24;
+                    const int y0 = min(Y1 * 2 + iy, G.H - 1); // (clamped in padding rows only)
+                    const uint32_t lo = (uint32_t)P.pack[(size_t)y0 * G.W + X1 * 2 + ix];
+                    const uint32_t ci = P.use_maps ? maps_ci(P, P.bmap, true, X1 * 2 + ix, y0, lo) : lo >> 24;
                     sum[0] += s_lin[3 * ci]; sum[1] += s_lin[3 * ci + 1]; sum[2] += s_lin[3 * ci + 2];
                 }
         }
@@ -864,10 +880,11 @@ __device__ __forceinline__ void base_down_body(const SparseParams &P) {
         if (t < DIM * DIM) {                                                                           \
             const int lx = t % DIM, ly = t / DIM;                                                      \
             float v[3];                                                                                \
+            const int YS = by * DIM + ly, ly1 = 2 * ly + (down_odd_row(G, S, YS) - 2 * YS);            \
             for (int c = 0; c < 3; c++) {                                                              \
                 float sum = 0.0f;                                                                      \
                 sum += SRC[c][2 * ly][2 * lx]; sum += SRC[c][2 * ly][2 * lx + 1];                      \
-                sum += SRC[c][2 * ly + 1][2 * lx]; sum += SRC[c][2 * ly + 1][2 * lx + 1];              \
+                sum += SRC[c][ly1][2 * lx]; sum += SRC[c][ly1][2 * lx + 1];                            \
                 v[c] = sum * 0.25f; DST[c][ly][lx] = v[c];                                             \
             }                                                                                          \
             if (by * DIM + ly < G.sh[S]) base_store(P, mine, S, bx * DIM + lx, by * DIM + ly, v, G.nscales > S + 1); \
@@ -879,7 +896,8 @@ __device__ __forceinline__ void base_down_body(const SparseParams &P) {
     SNES_BASE_LEVEL(4, l3, l4, 2)
     if (G.nscales > 5 && t == 0) {
         float v[3];
-        for (int c = 0; c < 3; c++) { float sum = 0.0f; sum += l4[c][0][0]; sum += l4[c][0][1]; sum += l4[c][1][0]; sum += l4[c][1][1]; v[c] = sum * 0.25f; }
+        const int o = down_odd_row(G, 5, by) - 2 * by;
+        for (int c = 0; c < 3; c++) { float sum = 0.0f; sum += l4[c][0][0]; sum += l4[c][0][1]; sum += l4[c][o][0]; sum += l4[c][o][1]; v[c] = sum * 0.25f; }
         if (by < G.sh[5]) base_store(P, mine, 5, bx, by, v, false);
     }
 #undef SNES_BASE_LEVEL
