@@ -179,6 +179,47 @@ int32_t snesimage_batch_step_async(snesimage_batch *batch, uint32_t method, uint
                                    uint32_t n_random);
 int32_t snesimage_batch_sync(snesimage_batch *batch);
 
+/* One palette shared by several images — the frames of an animated background, the poses of a sprite: on the SNES everything
+ * drawn on one background reads the same CGRAM (the reference optimizes one image per process, lib.rs:833-853).  A set borrows
+ * F >= 1 contexts (members) as a batch does — same device, image size, palette geometry, chunk and flags; a member belongs to
+ * no batch, group or other set — and keeps one palette in all of them; each member keeps its own tile_palettes and
+ * palette_map.  The set's error is E = sum of the members' error() in member order (binary64, left to right).
+ * An optimizer call gives every member the same candidate list (random: keyed (seed, step_id) as in snesimage_step; channel,
+ * NES: from the shared palette), E_k = sum of the members' e_{i,k}, and the reference's acceptance rule on E (strict < against
+ * the members' summed incumbents, lib.rs:216-219; the NES method takes its argmin, lib.rs:250): the winner goes to every
+ * member, whose incumbent becomes its own e_{i,k*}.  A set of one member steps exactly as snesimage_step.
+ * The initialisers are the reference's own on the member stack (the members top to bottom in member order, W x F*H): tile
+ * means in its order over that picture (tile_x outer), k-means, the stack's tile palettes split back by rows; the pixels
+ * of every tile using subpalette p, member after member.  Then optimize() on every member.
+ * snesimage_shared_create refuses members whose palettes differ (SNES_ERR_STATE) and what a batch refuses (SNES_ERR_ARG,
+ * SNES_ERR_STATE, SNES_ERR_UNSUPPORTED).  Every set call needs the members as the set left them: a member changed through
+ * its own calls (palette, tile palettes, map, a step) makes the next set call fail with SNES_ERR_STATE.  Lifetime as a
+ * batch's: destroy the set before its members; destroying a member first retires the set (SNES_ERR_STATE;
+ * snesimage_shared_destroy is still required).  Each member's storage is sized for `chunk` candidates (about 4.45 MB per
+ * candidate): set the chunk to the call's candidate count before creating the set. */
+typedef struct snesimage_shared snesimage_shared;
+int32_t snesimage_shared_create(snesimage_ctx **ctxs, uint32_t n, snesimage_shared **out);
+void snesimage_shared_destroy(snesimage_shared *set);
+int32_t snesimage_shared_initialize_tiles(snesimage_shared *set);     /* lib.rs:79-189 on the member stack */
+int32_t snesimage_shared_recalculate_palettes(snesimage_shared *set); /* lib.rs:407-415 on the member stack */
+/* the palette of every member := in (count*size*3 raw 5-bit colours), then optimize() on every member */
+int32_t snesimage_shared_set_palette_rgb5(snesimage_shared *set, const uint8_t *in);
+int32_t snesimage_shared_error(snesimage_shared *set, double *out); /* E */
+/* E_k for k < n: snesimage_score_candidates on every member, summed in member order.  Host pointers; synchronous; the
+ * members are left unchanged. */
+int32_t snesimage_shared_score_candidates(snesimage_shared *set, uint32_t palette, uint32_t index, const uint8_t *rgb5,
+                                          uint32_t n, double *errors);
+/* One optimizer call on the set (at most `chunk` candidates).  error: E after the call; best_rgb5: the slot's colour. */
+int32_t snesimage_shared_step(snesimage_shared *set, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel,
+                              uint64_t seed, uint64_t step_id, uint32_t n_random, double *error, uint8_t *best_rgb5);
+/* The same without any host synchronisation; results via snesimage_shared_last_step (error = E). */
+int32_t snesimage_shared_step_async(snesimage_shared *set, uint32_t method, uint32_t palette, uint32_t index,
+                                    uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random);
+int32_t snesimage_shared_last_step(snesimage_shared *set, snesimage_call_result *out);
+/* snesimage_reassign_tiles on every member (a tile's cost depends on its own pixels and the shared palette only);
+ * *moved = tiles moved in all members. */
+int32_t snesimage_shared_reassign_tiles(snesimage_shared *set, uint32_t *moved);
+
 /* Dynamic tile -> subpalette reassignment — NOT a reference method: /root/reference/TODO.md:36-37 lists it as missing ("no
  * attempt is made to reassign tiles dynamically if it could improve the overall result").  Every tile with an opaque pixel
  * moves to the subpalette with the strictly smallest cost, cost(p) = sum over the tile's opaque pixels (raster order) of the

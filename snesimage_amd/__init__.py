@@ -6,3 +6,4 @@ loads the library and fails loudly when it has not been built — there is no CP
 """
 from .api import (DITHER, METHOD_CHANNEL, METHOD_NES, METHOD_RANDOM, NES, PERCEPTUAL, OptimizedImage,  # noqa: F401
                   SnesImageError, debug_math, random_candidates, schedule)
+from .shared import SharedPalette  # noqa: F401,E402

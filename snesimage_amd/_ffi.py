@@ -72,6 +72,19 @@ SIGNATURES = [
     ("snesimage_batch_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
                                                C.c_uint64, C.c_uint32]),
     ("snesimage_batch_sync", C.c_int32, [C.c_void_p]),
+    ("snesimage_shared_create", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("snesimage_shared_destroy", None, [C.c_void_p]),
+    ("snesimage_shared_initialize_tiles", C.c_int32, [C.c_void_p]),
+    ("snesimage_shared_recalculate_palettes", C.c_int32, [C.c_void_p]),
+    ("snesimage_shared_set_palette_rgb5", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_shared_error", C.c_int32, [C.c_void_p, _f64p]),
+    ("snesimage_shared_score_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _f64p]),
+    ("snesimage_shared_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                          C.c_uint32, _f64p, _u8p]),
+    ("snesimage_shared_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                C.c_uint64, C.c_uint32]),
+    ("snesimage_shared_last_step", C.c_int32, [C.c_void_p, C.POINTER(CallResult)]),
+    ("snesimage_shared_reassign_tiles", C.c_int32, [C.c_void_p, _u32p]),
     ("snesimage_get_tile_palettes", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_tile_palettes", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_get_palette_rgb5", C.c_int32, [C.c_void_p, _u8p]),

@@ -249,10 +249,14 @@ int32_t snesimage_batch_sync(snesimage_batch *b) {
     return batch_quiesce(b);
 }
 
-// snesimage_step_async for every image of the batch, slot and method shared, candidate streams keyed (seeds[i], step_id).
-int32_t snesimage_batch_step_async(snesimage_batch *b, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, const uint64_t *seeds, uint64_t step_id, uint32_t n_random) {
-    if (!b || !seeds) return fail(SNES_ERR_ARG, "null pointer");
-    if (b->dead) return fail(SNES_ERR_STATE, "a member context of this batch was destroyed");
+} // extern "C"
+
+namespace {
+
+// The launches of one optimizer call for every member of b, on the batch's stream: member i's candidate stream keyed
+// (seeds[i], step_id).  joint == nullptr: every member commits its own call (kb_commit); otherwise the members share one
+// palette (a set, shared_host.inc) and ks_commit decides once for all of them, its record going to *joint.
+int32_t batch_call(snesimage_batch *b, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, const uint64_t *seeds, uint64_t step_id, uint32_t n_random, snes::StepResult *joint) {
     snesimage_ctx *c0 = b->ctx[0];
     CHECK(check_slot(c0, palette, index));
     if (method > 2 || channel > 2) return fail(SNES_ERR_ARG, "bad method or channel");
@@ -283,7 +287,8 @@ int32_t snesimage_batch_step_async(snesimage_batch *b, uint32_t method, uint32_t
     HIPCHK(hipEventRecord(b->used[r], st));
     hipLaunchKernelGGL(kb_gen_candidates, dim3((n + 63) / 64, 1, K), dim3(64), 0, st, A, (const int *)nullptr);
     CHECK(enqueue_batched_scoring(st, A, K, n, c0, nullptr, nullptr, c0->dither)); // (one stream: with 128 images' working sets the second stream of the slot windows costs 12 %)
-    hipLaunchKernelGGL(kb_commit, dim3(1, 1, K), dim3(256), 0, st, A, (const int *)nullptr);
+    if (joint) hipLaunchKernelGGL(ks_commit, dim3(1), dim3(256), 0, st, A, (int)K, joint);
+    else hipLaunchKernelGGL(kb_commit, dim3(1, 1, K), dim3(256), 0, st, A, (const int *)nullptr);
     if (c0->dither) hipLaunchKernelGGL(kb_take_map, dim3(1, 1, K), dim3(1024), 0, st, A, (const int *)nullptr);
     HIPCHK(hipGetLastError());
     for (auto *c : b->ctx) { // what snesimage_step_async leaves behind in a context
@@ -293,6 +298,17 @@ int32_t snesimage_batch_step_async(snesimage_batch *b, uint32_t method, uint32_t
     b->calls++;
     b->busy = true;
     return SNES_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// snesimage_step_async for every image of the batch, slot and method shared, candidate streams keyed (seeds[i], step_id).
+int32_t snesimage_batch_step_async(snesimage_batch *b, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, const uint64_t *seeds, uint64_t step_id, uint32_t n_random) {
+    if (!b || !seeds) return fail(SNES_ERR_ARG, "null pointer");
+    if (b->dead) return fail(SNES_ERR_STATE, "a member context of this batch was destroyed");
+    return batch_call(b, method, palette, index, channel, seeds, step_id, n_random, nullptr);
 }
 
 } // extern "C"

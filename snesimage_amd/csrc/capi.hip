@@ -7,6 +7,7 @@
 #include "kernels_sparse.hpp"
 #include "kernels_sparse2.hpp"
 #include "kernels_batch.hpp"
+#include "kernels_shared.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1562,5 +1563,6 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 } // extern "C"
 
 #include "batch_host.inc"
+#include "shared_host.inc"
 #include "window_host.inc"
 #include "group_host.inc"

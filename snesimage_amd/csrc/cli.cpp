@@ -10,6 +10,8 @@
 // reference's TODO.md:38-39), --preview FILE.png (source | result side by side, the picture the SDL window of
 // src/lib.rs:937-960 shows).  The source image is a PNG (png_io.hpp restates `image::open(..).into_rgba8()`,
 // src/lib.rs:836, for that format), a raw RGBA8 file of 256*H*4 bytes, or `synth:SEED`.
+// --share SOURCE=TARGET (repeatable) optimizes one palette for the main image and every such image together (a set,
+// include/snesimage_hip.h): the frames of an animation share one CGRAM on the console.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -62,6 +64,8 @@ void usage() {
             "      --preview <F>        write source | result as a PNG\n"
             "      --reassign-tiles <K> every K sweeps of the palette, move each tile to the subpalette that reproduces it best\n"
             "                           (off by default; not in the reference: its TODO.md lists it as missing)\n"
+            "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
+            "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>\n"
             "      --decode-only        write the decoded source as raw RGBA8 to <TARGET_FILENAME> and stop (no GPU)\n  -h, --help\n  -V, --version\n");
 }
 // the flat integer array stored under `"key":[...]` in one of this driver's (or the reference's) JSON outputs
@@ -101,48 +105,9 @@ void synth(uint64_t seed, uint32_t w, uint32_t h, std::vector<uint8_t> &out) { /
         }
 }
 
-} // namespace
-
-int main(int argc, char **argv) {
-    std::vector<std::string> pos;
-    uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, window = 0; // src/config.rs:13-18 defaults
-    uint64_t seed = 1;
-    int device = 0;
-    std::string tile_file, preview_file, resume_file;
-    std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
-    bool decode_only = false;
-    for (int i = 1; i < argc; i++) {
-        std::string a = argv[i];
-        auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
-        if (a == "-c" || a == "--subpalette-count") count = (uint32_t)strtoul(need("--subpalette-count"), nullptr, 10);
-        else if (a == "-s" || a == "--subpalette-size") size = (uint32_t)strtoul(need("--subpalette-size"), nullptr, 10);
-        else if (a == "-d" || a == "--dither") flags |= SNES_DITHER;
-        else if (a == "--perceptual-palettes") flags |= SNES_PERCEPTUAL;
-        else if (a == "--nes") flags |= SNES_NES;
-        else if (a == "--calls") calls = (uint32_t)strtoul(need("--calls"), nullptr, 10);
-        else if (a == "--candidates") ncand = (uint32_t)strtoul(need("--candidates"), nullptr, 10);
-        else if (a == "--seed") seed = strtoull(need("--seed"), nullptr, 0);
-        else if (a == "--window") window = (uint32_t)strtoul(need("--window"), nullptr, 10);
-        else if (a == "--device") device = atoi(need("--device"));
-        else if (a == "--devices") { for (const char *q = need("--devices"); *q;) { char *end = nullptr; devices.push_back((int)strtol(q, &end, 10)); if (end == q) { fprintf(stderr, "error: invalid value for '--devices'\n"); return 2; } q = *end == ',' ? end + 1 : end; } }
-        else if (a == "--tile-palettes") tile_file = need("--tile-palettes");
-        else if (a == "--preview") preview_file = need("--preview");
-        else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
-        else if (a == "--resume") resume_file = need("--resume");
-        else if (a == "--decode-only") decode_only = true;
-        else if (a == "-h" || a == "--help") { usage(); return 0; }
-        else if (a == "-V" || a == "--version") { printf("snesimage 0.1.1 (%s)\n", snesimage_version()); return 0; }
-        else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str()); usage(); return 2; }
-        else pos.push_back(a);
-    }
-    if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
-    const std::string source = pos[0], target = pos[1];
-    // the JSON keeps 15 colours per subpalette (src/lib.rs:583-593): a larger subpalette cannot be read back from it
-    if (!resume_file.empty() && size > 15) die("--resume needs --subpalette-size <= 15: the output keeps 15 colours per subpalette");
-
-    log_info("Using source image: " + source); // src/lib.rs:834
-    std::vector<uint8_t> rgba;
-    uint32_t w = 256, h = 256;
+// the source image: PNG, raw RGBA8 (256 x H x 4 bytes) or synth:SEED
+void load_source(const std::string &source, uint32_t &w, uint32_t &h, std::vector<uint8_t> &rgba) {
+    w = 256; h = 256;
     if (source.rfind("synth:", 0) == 0) synth(strtoull(source.c_str() + 6, nullptr, 0), w, h, rgba);
     else {
         FILE *f = fopen(source.c_str(), "rb");
@@ -163,6 +128,73 @@ int main(int argc, char **argv) {
             rgba.swap(file);
         }
     }
+}
+
+void write_json(snesimage_ctx *ctx, const std::string &target) { // src/lib.rs:1000-1002
+    int64_t need = snesimage_as_json(ctx, nullptr, 0);
+    if (need < 0) die(snesimage_last_error());
+    std::vector<char> json((size_t)need);
+    snesimage_as_json(ctx, json.data(), need);
+    FILE *f = fopen(target.c_str(), "wb");
+    if (!f) die("cannot create " + target);
+    fwrite(json.data(), 1, (size_t)need - 1, f);
+    fclose(f);
+}
+
+} // namespace
+
+int main(int argc, char **argv) {
+    std::vector<std::string> pos;
+    uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, window = 0; // src/config.rs:13-18 defaults
+    uint64_t seed = 1;
+    int device = 0;
+    std::string tile_file, preview_file, resume_file;
+    std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
+    std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
+    bool decode_only = false;
+    for (int i = 1; i < argc; i++) {
+        std::string a = argv[i];
+        auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
+        if (a == "-c" || a == "--subpalette-count") count = (uint32_t)strtoul(need("--subpalette-count"), nullptr, 10);
+        else if (a == "-s" || a == "--subpalette-size") size = (uint32_t)strtoul(need("--subpalette-size"), nullptr, 10);
+        else if (a == "-d" || a == "--dither") flags |= SNES_DITHER;
+        else if (a == "--perceptual-palettes") flags |= SNES_PERCEPTUAL;
+        else if (a == "--nes") flags |= SNES_NES;
+        else if (a == "--calls") calls = (uint32_t)strtoul(need("--calls"), nullptr, 10);
+        else if (a == "--candidates") ncand = (uint32_t)strtoul(need("--candidates"), nullptr, 10);
+        else if (a == "--seed") seed = strtoull(need("--seed"), nullptr, 0);
+        else if (a == "--window") window = (uint32_t)strtoul(need("--window"), nullptr, 10);
+        else if (a == "--device") device = atoi(need("--device"));
+        else if (a == "--devices") { for (const char *q = need("--devices"); *q;) { char *end = nullptr; devices.push_back((int)strtol(q, &end, 10)); if (end == q) { fprintf(stderr, "error: invalid value for '--devices'\n"); return 2; } q = *end == ',' ? end + 1 : end; } }
+        else if (a == "--tile-palettes") tile_file = need("--tile-palettes");
+        else if (a == "--preview") preview_file = need("--preview");
+        else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
+        else if (a == "--resume") resume_file = need("--resume");
+        else if (a == "--share") {
+            const std::string v = need("--share");
+            const size_t eq = v.find('=');
+            if (eq == std::string::npos || eq == 0 || eq + 1 == v.size()) { fprintf(stderr, "error: invalid value '%s' for '--share <SOURCE=TARGET>': expected SOURCE=TARGET\n", v.c_str()); return 2; }
+            shares.emplace_back(v.substr(0, eq), v.substr(eq + 1));
+        }
+        else if (a == "--decode-only") decode_only = true;
+        else if (a == "-h" || a == "--help") { usage(); return 0; }
+        else if (a == "-V" || a == "--version") { printf("snesimage 0.1.1 (%s)\n", snesimage_version()); return 0; }
+        else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str()); usage(); return 2; }
+        else pos.push_back(a);
+    }
+    if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
+    const std::string source = pos[0], target = pos[1];
+    if (!shares.empty()) { // a set is stepped call by call on one device, from the k-means initialisers
+        const char *bad = !resume_file.empty() ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
+        if (bad) { fprintf(stderr, "error: the argument '--share <SOURCE=TARGET>' cannot be used with %s\n", bad); return 2; }
+    }
+    // the JSON keeps 15 colours per subpalette (src/lib.rs:583-593): a larger subpalette cannot be read back from it
+    if (!resume_file.empty() && size > 15) die("--resume needs --subpalette-size <= 15: the output keeps 15 colours per subpalette");
+
+    log_info("Using source image: " + source); // src/lib.rs:834
+    std::vector<uint8_t> rgba;
+    uint32_t w = 256, h = 256;
+    load_source(source, w, h, rgba);
     if (decode_only) {
         FILE *f = fopen(target.c_str(), "wb");
         if (!f) die("cannot create " + target);
@@ -171,9 +203,31 @@ int main(int argc, char **argv) {
         printf("%u %u\n", w, h);
         return 0;
     }
+    std::vector<std::vector<uint8_t>> shared_rgba(shares.size()); // every --share source, decoded like the main one
+    for (size_t i = 0; i < shares.size(); i++) {
+        uint32_t ow = 0, oh = 0;
+        log_info("Using shared image: " + shares[i].first);
+        load_source(shares[i].first, ow, oh, shared_rgba[i]);
+        if (ow != w || oh != h) die("shared image " + shares[i].first + " is " + std::to_string(ow) + "x" + std::to_string(oh) + ", the source " + std::to_string(w) + "x" + std::to_string(h));
+    }
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
     if (snesimage_create(rgba.data(), w, h, count, size, flags, device, &ctx) != 0) die(snesimage_last_error());
+    // --share: one context per image, every member's storage sized for one call's candidates (about 4.45 MB each), one set
+    std::vector<snesimage_ctx *> frames{ctx};
+    snesimage_shared *set = nullptr;
+    if (!shares.empty()) {
+        for (const auto &other : shared_rgba) {
+            snesimage_ctx *m = nullptr;
+            if (snesimage_create(other.data(), w, h, count, size, flags, device, &m) != 0) die(snesimage_last_error());
+            frames.push_back(m);
+        }
+        uint32_t chunk = ncand > 32 ? ncand : 32; // the largest call of the schedule: random (ncand), channel (32) or NES (56)
+        if ((flags & SNES_NES) && chunk < 56) chunk = 56;
+        for (snesimage_ctx *m : frames) if (snesimage_set_chunk(m, chunk) != 0) die(snesimage_last_error());
+        if (snesimage_shared_create(frames.data(), (uint32_t)frames.size(), &set) != 0) die(snesimage_last_error());
+        log_info("Sharing one palette between " + std::to_string(frames.size()) + " images");
+    }
     if (!resume_file.empty()) { // palette + tile_palettes of an earlier output (src/lib.rs:579-625); the tiles follow from optimize()
         std::vector<long> pal, tp;
         if (!json_int_array(resume_file, "palette", pal) || !json_int_array(resume_file, "tile_palettes", tp)) die("cannot read palette and tile_palettes from " + resume_file);
@@ -192,6 +246,11 @@ int main(int argc, char **argv) {
             }
         if (snesimage_set_tile_palettes(ctx, tp8.data()) != 0 || snesimage_set_palette_rgb5(ctx, rgb5.data()) != 0 || snesimage_optimize(ctx) != 0) die(snesimage_last_error());
         log_info("Resumed from " + resume_file);
+    } else if (set) { // the reference's initialisers on the images stacked top to bottom
+        if (snesimage_shared_initialize_tiles(set) != 0) die(std::string("Unable to initialize tiles: ") + snesimage_last_error());
+        log_info("Finished assigning initial tiles");
+        log_info("Generating initial palettes");
+        if (snesimage_shared_recalculate_palettes(set) != 0) die(std::string("Unable to recalculate palettes: ") + snesimage_last_error());
     } else {
         if (snesimage_initialize_tiles(ctx) != 0) die(std::string("Unable to initialize tiles: ") + snesimage_last_error()); // src/lib.rs:851-853
         log_info("Finished assigning initial tiles");
@@ -237,12 +296,13 @@ int main(int argc, char **argv) {
     auto end_of_sweep = [&]() {
         if (reassign_every && step != sweep && step % reassign_every == 0) { // a sweep over every slot has just ended (src/lib.rs:925-931)
             uint32_t moved = 0;
-            for (snesimage_ctx *m : members) if (snesimage_reassign_tiles(m, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error());
+            if (set) { if (snesimage_shared_reassign_tiles(set, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error()); }
+            else for (snesimage_ctx *m : members) if (snesimage_reassign_tiles(m, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error());
             log_info("Reassigned " + std::to_string(moved) + " tiles");
         }
         sweep = step;
     };
-    if (ncand <= 64 && window != 1) {
+    if (!set && ncand <= 64 && window != 1) {
         // The reference's loop (src/lib.rs:888-933), several calls per launch: snesimage_run_slots scores the coming calls of the
         // schedule against the current palette and applies them in order up to the first one that changes it — the same
         // trajectory, call for call, as stepping one call at a time (--window 1).  A run ends with its sweep when tiles are
@@ -286,21 +346,19 @@ int main(int argc, char **argv) {
         snesimage_schedule_next(count, size, nes, &palette, &index, &channel, &step, &method);
         snesimage_get_palette_rgb5(ctx, before.data());
         double error = 0.0; uint8_t best[3];
-        const int32_t rc = group ? snesimage_group_step(group, method, p, ix, ch, seed, call, method == SNES_METHOD_RANDOM ? ncand : 0, &error, best)
+        const int32_t rc = set ? snesimage_shared_step(set, method, p, ix, ch, seed, call, method == SNES_METHOD_RANDOM ? ncand : 0, &error, best)
+                         : group ? snesimage_group_step(group, method, p, ix, ch, seed, call, method == SNES_METHOD_RANDOM ? ncand : 0, &error, best)
                                  : snesimage_step(ctx, method, p, ix, ch, seed, call, method == SNES_METHOD_RANDOM ? ncand : 0, &error, best);
         if (rc != 0) die(std::string("Unable to optimize palette: ") + snesimage_last_error());
         report(p, ix, &before[3 * ((size_t)p * size + ix)], best, error);
         end_of_sweep();
     }
     log_info("Writing output to " + target); // src/lib.rs:1000-1002
-    int64_t need = snesimage_as_json(ctx, nullptr, 0);
-    if (need < 0) die(snesimage_last_error());
-    std::vector<char> json((size_t)need);
-    snesimage_as_json(ctx, json.data(), need);
-    FILE *f = fopen(target.c_str(), "wb");
-    if (!f) die("cannot create " + target);
-    fwrite(json.data(), 1, (size_t)need - 1, f);
-    fclose(f);
+    write_json(ctx, target);
+    for (size_t i = 0; i < shares.size(); i++) {
+        log_info("Writing output to " + shares[i].second);
+        write_json(frames[i + 1], shares[i].second);
+    }
     if (!preview_file.empty()) { // left: source, right: as_rgba() of the result (src/lib.rs:940-957)
         std::vector<uint8_t> result((size_t)w * h * 4), both((size_t)2 * w * h * 4), png;
         if (snesimage_as_rgba(ctx, result.data()) != 0) die(snesimage_last_error());
@@ -316,6 +374,8 @@ int main(int argc, char **argv) {
         log_info("Wrote preview to " + preview_file);
     }
     if (group) snesimage_group_destroy(group);
+    if (set) snesimage_shared_destroy(set);
     for (snesimage_ctx *m : members) snesimage_destroy(m);
+    for (size_t i = 1; i < frames.size(); i++) snesimage_destroy(frames[i]);
     return 0;
 }

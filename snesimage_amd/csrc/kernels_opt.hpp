@@ -782,17 +782,12 @@ __global__ void k_shard_select(const uint8_t *__restrict__ cand, int n, int rank
 // Acceptance rule: ascending k, strict `<` against the running best starting from the incumbent
 // (lib.rs:216-219, 302-305) or from f64::MAX for the NES method (lib.rs:250, 258-261).
 struct PaletteTables { const float *eotf, *lab_eotf; uint32_t *rgb8; float *lin, *xyb, *lab; }; // lab == nullptr without --perceptual-palettes
-// The decision of one optimizer call given the first-lowest error (min_e at index min_k; min_k = 0x7fffffff: no finite
-// error) of its candidate list: accept it iff it is strictly below the incumbent (always, for the NES method), write
-// the slot's colour and its rows of the palette tables, leave the committed state's error in *inc_err.  One thread.
-__device__ __forceinline__ void commit_decide(const double min_e, const int min_k, const uint8_t *__restrict__ cand, uint8_t *__restrict__ colors, int slot, int nes, double *__restrict__ inc_err,
-                                              StepResult *__restrict__ last, const PaletteTables &T) {
-    const double start = nes ? 1.7976931348623157e308 : *inc_err;
-    double best = start; int best_k = -1;
-    if (min_k != 0x7fffffff && min_e < start) { best = min_e; best_k = min_k; }
+// What a decision does to one context: candidate best_k (-1: none) becomes the slot's colour, with its rows of the palette
+// tables; best (< f64::MAX) becomes the committed state's error in *inc_err; *last records the call.  One thread.
+__device__ __forceinline__ void commit_apply(const double best, const int best_k, const uint8_t *__restrict__ cand, uint8_t *__restrict__ colors, int slot, double *__restrict__ inc_err,
+                                             StepResult *__restrict__ last, const PaletteTables &T) {
     uint8_t c[3] = {colors[3 * slot], colors[3 * slot + 1], colors[3 * slot + 2]};
     uint8_t changed = 0;
-    if (nes && best_k < 0) best_k = 0; // best_index = 0 (lib.rs:249)
     if (best_k >= 0) {
         uint8_t nc[3] = {cand[3 * best_k], cand[3 * best_k + 1], cand[3 * best_k + 2]};
         changed = (nc[0] != c[0] || nc[1] != c[1] || nc[2] != c[2]) ? 1 : 0;
@@ -814,6 +809,18 @@ __device__ __forceinline__ void commit_decide(const double min_e, const int min_
         if (best < 1.7976931348623157e308) *inc_err = best; // error() of the committed state (lib.rs:910)
     }
     last->error = *inc_err; last->best_k = best_k; last->rgb5[0] = c[0]; last->rgb5[1] = c[1]; last->rgb5[2] = c[2]; last->changed = changed;
+}
+
+// The decision of one optimizer call given the first-lowest error (min_e at index min_k; min_k = 0x7fffffff: no finite
+// error) of its candidate list: accept it iff it is strictly below the incumbent (always, for the NES method), write
+// the slot's colour and its rows of the palette tables, leave the committed state's error in *inc_err.  One thread.
+__device__ __forceinline__ void commit_decide(const double min_e, const int min_k, const uint8_t *__restrict__ cand, uint8_t *__restrict__ colors, int slot, int nes, double *__restrict__ inc_err,
+                                              StepResult *__restrict__ last, const PaletteTables &T) {
+    const double start = nes ? 1.7976931348623157e308 : *inc_err;
+    double best = start; int best_k = -1;
+    if (min_k != 0x7fffffff && min_e < start) { best = min_e; best_k = min_k; }
+    if (nes && best_k < 0) best_k = 0; // best_index = 0 (lib.rs:249)
+    commit_apply(best, best_k, cand, colors, slot, inc_err, last, T);
 }
 
 __device__ __forceinline__ void commit_body(const double *__restrict__ errors, int n, const uint8_t *__restrict__ cand, uint8_t *__restrict__ colors, int slot, int nes, double *__restrict__ inc_err,

@@ -1,0 +1,331 @@
+// snesimage_amd/csrc/shared_host.inc — one palette shared by several images (DESIGN §5b).  Included by capi.hip after
+// batch_host.inc.  A set is an image batch (it borrows its members the same way: `owner`, the batch's stream, its ring of
+// argument blocks) whose optimizer calls give every member the same candidate list and commit once on the joint error
+// (ks_commit, kernels_shared.hpp).  The k-means initialisers run on the member stack — the members top to bottom in
+// member order, W x F*H — with the point order of the reference's own initialisers over that picture.
+
+struct snesimage_shared {
+    snesimage_batch *b = nullptr;
+    snes::StepResult *d_joint = nullptr;      // the set's record of the last call (error = E)
+    double *d_sum = nullptr; uint32_t sum_cap = 0; // snesimage_shared_score_candidates: E_k
+    const double **d_tab = nullptr;           // the members' error vectors, for ks_sum
+    std::vector<unsigned long long> epoch;    // each member's palette / tile-map generation when the set last touched it
+};
+
+namespace {
+
+std::vector<snesimage_ctx *> &members(snesimage_shared *s) { return s->b->ctx; }
+
+// Every set call starts here: the set is intact, and no member was changed behind its back since the set last touched it.
+// wait: the call works on the members outside the batched launches, so the set's stream must be idle first.
+int32_t shared_enter(snesimage_shared *s, bool wait = true) {
+    if (!s) return fail(SNES_ERR_ARG, "null set");
+    if (s->b->dead) return fail(SNES_ERR_STATE, "a member context of this set was destroyed");
+    auto &M = members(s);
+    for (size_t i = 0; i < M.size(); i++)
+        if (M[i]->epoch != s->epoch[i] || M[i]->pend || M[i]->win_pend)
+            return fail(SNES_ERR_STATE, "member " + std::to_string(i) + " of the set was changed outside it (its palette, tile palettes or map): the members no longer share one state");
+    HIPCHK(hipSetDevice(s->b->device));
+    return wait ? batch_quiesce(s->b) : SNES_OK;
+}
+
+// After a set call that changed the members outside the batched launches: everything a batched call takes for granted
+// (as snesimage_batch_create leaves it), then the members' generations are recorded.
+int32_t shared_settle(snesimage_shared *s) {
+    auto &M = members(s);
+    for (auto *c : M) {
+        CHECK(ensure_tables(c));
+        CHECK(ensure_source(c));
+        if (!c->map_synced) CHECK(do_optimize(c));
+        CHECK(ensure_incumbent(c));
+    }
+    for (size_t i = 0; i < M.size(); i++) { HIPCHK(hipStreamSynchronize(M[i]->stream)); s->epoch[i] = M[i]->epoch; }
+    return SNES_OK;
+}
+
+// The palette of every member := rgb5 (as snesimage_set_palette_rgb5 does); optimize() follows in shared_settle.
+int32_t shared_put_palette(snesimage_shared *s, const uint8_t *rgb5) {
+    for (auto *c : members(s)) {
+        CHECK(ensure_map(c));
+        HIPCHK(hipMemcpyAsync(c->d_colors, rgb5, 3 * (size_t)c->ncol, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->tables_valid = false; c->pack_valid = false; c->inc_valid = false; c->map_synced = false; c->epoch++; c->epoch_by_commit = false;
+    }
+    return SNES_OK;
+}
+
+// recalculate_palette(p) (lib.rs:330-405) over the member stack for every p in `which`: the points of subpalette p are the
+// opaque pixels of every tile that uses it, member after member, tiles row-major, x outer and y inner within a tile
+// (pixel coordinates of the stack: member i's row y is row i*H + y).  One k-means problem per subpalette on member 0's
+// workspace, the points gathered there from every member's planes; the colours go to every member.
+int32_t shared_kmeans_recalculate(snesimage_shared *s, const std::vector<uint32_t> &which) {
+    auto &M = members(s);
+    snesimage_ctx *c0 = M[0];
+    const size_t F = M.size();
+    std::vector<std::vector<uint8_t>> tp(F, std::vector<uint8_t>(1024));
+    for (size_t i = 0; i < F; i++) {
+        snesimage_ctx *c = M[i];
+        if (c->perceptual) CHECK(ensure_source(c)); // per-pixel Lab
+        HIPCHK(hipMemcpyAsync(tp[i].data(), c->d_tile_pal, 1024, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    const uint32_t wt = c0->W / 8, ht = c0->H / 8;
+    struct Run { size_t member; long long off, n; };
+    std::vector<uint32_t> index; std::vector<Run> runs;
+    std::vector<int> n; std::vector<long long> off;
+    for (uint32_t palette : which) {
+        off.push_back((long long)index.size());
+        for (size_t i = 0; i < F; i++) {
+            const long long r0 = (long long)index.size();
+            for (uint32_t tile = 0; tile < 1024; tile++) {
+                if (tp[i][tile] != palette) continue;
+                const uint32_t tx = tile % wt, ty = tile / wt;
+                if (ty >= ht) continue;
+                for (uint32_t x = 0; x < 8; x++)
+                    for (uint32_t y = 0; y < 8; y++) {
+                        const uint32_t px = (ty * 8 + y) * c0->W + tx * 8 + x;
+                        if (M[i]->h_orig[4 * (size_t)px + 3] > 0) index.push_back(px);
+                    }
+            }
+            if ((long long)index.size() > r0) runs.push_back(Run{i, r0, (long long)index.size() - r0});
+        }
+        n.push_back((int)((long long)index.size() - off.back()));
+    }
+    const int k = (int)c0->sub_size;
+    for (size_t p = 0; p < n.size(); p++)
+        if (!(2 <= k && k < n[p])) return fail(SNES_ERR_KMEANS, "k-means precondition 2 <= k < n violated (the reference panics here)");
+    CHECK(kmeans_reserve(c0, index.size(), (int)which.size(), k));
+    HIPCHK(hipMemcpyAsync(c0->km.d_index, index.data(), sizeof(uint32_t) * index.size(), hipMemcpyHostToDevice, c0->stream));
+    for (const Run &r : runs) { // member r.member's pixels, indices local to that member, into their place in the point list
+        const snesimage_ctx *c = M[r.member];
+        hipLaunchKernelGGL(k_gather_points, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, c0->stream, c->d_orig, c->d_labpx, c0->km.d_index + r.off, r.n, c->perceptual ? 1 : 0,
+                           c0->km.pts + 3 * r.off);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<double> centres;
+    CHECK(kmeans_run(c0, n, off, k, centres, nullptr));
+    std::vector<uint8_t> col(3 * (size_t)c0->ncol);
+    HIPCHK(hipMemcpyAsync(col.data(), c0->d_colors, col.size(), hipMemcpyDeviceToHost, c0->stream));
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    for (size_t p = 0; p < which.size(); p++)
+        for (int i = 0; i < k; i++) host_centre_to_color(c0, &centres[3 * (p * k + i)], &col[3 * ((size_t)which[p] * c0->sub_size + i)]);
+    return shared_put_palette(s, col.data());
+}
+
+// initialize_tiles (lib.rs:79-189) over the member stack: the tile means in the reference's order over that picture —
+// tile_x outer, the stack's tile rows inner, i.e. for every column of tiles member 0's tiles top to bottom, then member
+// 1's, ... (the members interleave column by column) — with its drop rule; k-means with sub_count clusters; the stack's
+// tile palettes split back to the members by rows; every entry of subpalette p seeded with centre p.
+int32_t shared_kmeans_initialize_tiles(snesimage_shared *s) {
+    auto &M = members(s);
+    snesimage_ctx *c0 = M[0];
+    const size_t F = M.size();
+    if (c0->sub_count == 1) return shared_kmeans_recalculate(s, std::vector<uint32_t>{0}); // lib.rs:80-84
+    const uint32_t wt = c0->W / 8, ht = c0->H / 8, ntile = wt * ht;
+    std::vector<std::vector<float>> sums(F, std::vector<float>(3 * (size_t)ntile));
+    std::vector<std::vector<int>> counts(F, std::vector<int>(ntile));
+    for (size_t i = 0; i < F; i++) { // every member's tile sums on its own stream and workspace (a tile's sums are its own pixels')
+        snesimage_ctx *c = M[i];
+        if (c->perceptual) CHECK(ensure_source(c));
+        CHECK(kmeans_reserve(c, 1, 1, (int)c->sub_count));
+        hipLaunchKernelGGL(k_tile_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, c->d_orig, c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0, c->km.d_sums, c->km.d_counts);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(sums[i].data(), c->km.d_sums, sizeof(float) * sums[i].size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(counts[i].data(), c->km.d_counts, sizeof(int) * counts[i].size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    for (auto *c : M) HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<double> means; std::vector<std::pair<size_t, uint32_t>> map; // (member, tile) of every point
+    for (uint32_t tx = 0; tx < wt; tx++)
+        for (size_t i = 0; i < F; i++)
+            for (uint32_t ty = 0; ty < ht; ty++) {
+                const uint32_t index = ty * wt + tx;
+                const float *sm = &sums[i][3 * (size_t)index];
+                if (sm[0] + sm[1] + sm[2] > 0.0f) { // lib.rs:118
+                    for (int q = 0; q < 3; q++) means.push_back((double)sm[q] / (double)counts[i][index]);
+                    map.emplace_back(i, index);
+                }
+            }
+    const int k = (int)c0->sub_count;
+    std::vector<int> n{(int)map.size()}; std::vector<long long> off{0};
+    if (!(2 <= k && k < n[0])) return fail(SNES_ERR_KMEANS, "k-means precondition 2 <= k < n violated (the reference panics here)");
+    CHECK(kmeans_reserve(c0, map.size(), 1, k));
+    HIPCHK(hipMemcpyAsync(c0->km.pts, means.data(), sizeof(double) * means.size(), hipMemcpyHostToDevice, c0->stream));
+    std::vector<double> centres; std::vector<uint32_t> assign;
+    CHECK(kmeans_run(c0, n, off, k, centres, &assign));
+    std::vector<std::vector<uint8_t>> tp(F, std::vector<uint8_t>(1024));
+    for (size_t i = 0; i < F; i++) {
+        HIPCHK(hipMemcpyAsync(tp[i].data(), M[i]->d_tile_pal, 1024, hipMemcpyDeviceToHost, M[i]->stream));
+        HIPCHK(hipStreamSynchronize(M[i]->stream));
+    }
+    for (size_t t = 0; t < map.size(); t++) tp[map[t].first][map[t].second] = (uint8_t)assign[t]; // lib.rs:133-138
+    std::vector<uint8_t> col(3 * (size_t)c0->ncol);
+    for (int i = 0; i < k; i++) {
+        uint8_t color[3];
+        host_centre_to_color(c0, &centres[3 * (size_t)i], color);
+        for (uint32_t j = 0; j < c0->sub_size; j++) memcpy(&col[3 * ((size_t)i * c0->sub_size + j)], color, 3); // lib.rs:181-183
+    }
+    for (size_t i = 0; i < F; i++) {
+        HIPCHK(hipMemcpyAsync(M[i]->d_tile_pal, tp[i].data(), 1024, hipMemcpyHostToDevice, M[i]->stream));
+        HIPCHK(hipStreamSynchronize(M[i]->stream));
+    }
+    return shared_put_palette(s, col.data());
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t snesimage_shared_create(snesimage_ctx **ctxs, uint32_t n, snesimage_shared **out) {
+    if (!ctxs || !out || n == 0) return fail(SNES_ERR_ARG, "null pointer or empty set");
+    *out = nullptr;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!ctxs[i]) return fail(SNES_ERR_ARG, "null context in set");
+        if (ctxs[i]->group) return fail(SNES_ERR_STATE, "context belongs to a group");
+        for (uint32_t j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(SNES_ERR_ARG, "a context appears twice in the set");
+    }
+    // the batch checks the rest (device, size, geometry, chunk, flags, the group-sparse path) and readies every member
+    snesimage_batch *b = nullptr;
+    CHECK(snesimage_batch_create(ctxs, n, &b));
+    std::unique_ptr<snesimage_shared> s(new snesimage_shared());
+    s->b = b;
+    auto undo = [&](int32_t rc) { snesimage_shared_destroy(s.release()); return rc; };
+    std::vector<uint8_t> p0, pi;
+    for (uint32_t i = 0; i < n; i++) {
+        snesimage_ctx *c = ctxs[i];
+        (i ? pi : p0).resize(3 * (size_t)c->ncol);
+        if (hipMemcpyAsync((i ? pi : p0).data(), c->d_colors, 3 * (size_t)c->ncol, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)
+            return undo(fail(SNES_ERR_HIP, "hipMemcpy failed"));
+        if (i && pi != p0) return undo(fail(SNES_ERR_STATE, "the members of a set must hold the same palette (member " + std::to_string(i) + " differs from member 0)"));
+    }
+    if (hipMalloc(&s->d_joint, sizeof(snes::StepResult)) != hipSuccess || hipMalloc(&s->d_tab, sizeof(double *) * n) != hipSuccess)
+        return undo(fail(SNES_ERR_HIP, "hipMalloc failed"));
+    s->epoch.resize(n);
+    for (uint32_t i = 0; i < n; i++) s->epoch[i] = ctxs[i]->epoch;
+    *out = s.release();
+    return SNES_OK;
+}
+
+void snesimage_shared_destroy(snesimage_shared *s) {
+    if (!s) return;
+    (void)hipSetDevice(s->b->device);
+    snesimage_batch_destroy(s->b); // (waits for its stream)
+    if (s->d_joint) (void)hipFree(s->d_joint);
+    if (s->d_sum) (void)hipFree(s->d_sum);
+    if (s->d_tab) (void)hipFree(s->d_tab);
+    delete s;
+}
+
+int32_t snesimage_shared_initialize_tiles(snesimage_shared *s) {
+    CHECK(shared_enter(s));
+    CHECK(shared_kmeans_initialize_tiles(s));
+    return shared_settle(s);
+}
+
+int32_t snesimage_shared_recalculate_palettes(snesimage_shared *s) { // lib.rs:407-415 over the member stack
+    CHECK(shared_enter(s));
+    std::vector<uint32_t> which;
+    for (uint32_t p = 0; p < members(s)[0]->sub_count; p++) which.push_back(p);
+    CHECK(shared_kmeans_recalculate(s, which));
+    return shared_settle(s);
+}
+
+int32_t snesimage_shared_set_palette_rgb5(snesimage_shared *s, const uint8_t *in) {
+    if (!in) return fail(SNES_ERR_ARG, "null pointer");
+    CHECK(shared_enter(s));
+    CHECK(shared_put_palette(s, in));
+    return shared_settle(s);
+}
+
+int32_t snesimage_shared_error(snesimage_shared *s, double *out) {
+    if (!out) return fail(SNES_ERR_ARG, "null pointer");
+    CHECK(shared_enter(s));
+    double E = 0.0;
+    auto &M = members(s);
+    for (size_t i = 0; i < M.size(); i++) {
+        double e = 0.0;
+        CHECK(do_error(M[i], M[i]->d_scratch_err));
+        HIPCHK(hipMemcpyAsync(&e, M[i]->d_scratch_err, sizeof(double), hipMemcpyDeviceToHost, M[i]->stream));
+        HIPCHK(hipStreamSynchronize(M[i]->stream));
+        E = i == 0 ? e : E + e; // member order, as ks_commit sums
+    }
+    *out = E;
+    return SNES_OK;
+}
+
+// E_k for an explicit candidate list: every member scores it on its own stream (snesimage_score_candidates_device), ks_sum
+// adds the error vectors in member order on the set's stream.  The members are left unchanged.
+int32_t snesimage_shared_score_candidates(snesimage_shared *s, uint32_t palette, uint32_t index, const uint8_t *rgb5, uint32_t n, double *errors) {
+    if (!rgb5 || !errors) return fail(SNES_ERR_ARG, "null pointer");
+    CHECK(shared_enter(s));
+    auto &M = members(s);
+    CHECK(check_slot(M[0], palette, index));
+    if (n == 0) return SNES_OK;
+    if (s->sum_cap < n) {
+        if (s->d_sum) { HIPCHK(hipFree(s->d_sum)); s->d_sum = nullptr; s->sum_cap = 0; }
+        HIPCHK(hipMalloc(&s->d_sum, sizeof(double) * n));
+        s->sum_cap = n;
+    }
+    std::vector<const double *> tab(M.size());
+    for (size_t i = 0; i < M.size(); i++) {
+        snesimage_ctx *c = M[i];
+        CHECK(ensure_cand_capacity(c, n));
+        HIPCHK(hipMemcpyAsync(c->d_cand_sel, rgb5, 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        CHECK(prep_for_slot(c, (int)palette, (int)index));
+        CHECK(score_list(c, c->d_cand_sel, n, c->d_errs_sel, 1, 0, (int)palette, (int)index, nullptr));
+        tab[i] = c->d_errs_sel;
+    }
+    for (auto *c : M) HIPCHK(hipStreamSynchronize(c->stream));
+    hipStream_t st = s->b->stream;
+    HIPCHK(hipMemcpyAsync(s->d_tab, tab.data(), sizeof(double *) * tab.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ks_sum, dim3((n + 255) / 256), dim3(256), 0, st, s->d_tab, (int)M.size(), (int)n, s->d_sum);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(errors, s->d_sum, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SNES_OK;
+}
+
+int32_t snesimage_shared_step_async(snesimage_shared *s, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random) {
+    CHECK(shared_enter(s, false));
+    auto &M = members(s);
+    const std::vector<uint64_t> seeds(M.size(), seed); // one candidate list for every member: snesimage_step's for (seed, step_id)
+    CHECK(batch_call(s->b, method, palette, index, channel, seeds.data(), step_id, n_random, s->d_joint));
+    for (size_t i = 0; i < M.size(); i++) s->epoch[i] = M[i]->epoch;
+    return SNES_OK;
+}
+
+int32_t snesimage_shared_last_step(snesimage_shared *s, snesimage_call_result *out) {
+    if (!s || !out) return fail(SNES_ERR_ARG, "null pointer");
+    if (s->b->dead) return fail(SNES_ERR_STATE, "a member context of this set was destroyed");
+    HIPCHK(hipSetDevice(s->b->device));
+    snes::StepResult r;
+    HIPCHK(hipMemcpyAsync(&r, s->d_joint, sizeof(r), hipMemcpyDeviceToHost, s->b->stream));
+    HIPCHK(hipStreamSynchronize(s->b->stream));
+    s->b->busy = false;
+    out->error = r.error; out->best_k = r.best_k; out->rgb5[0] = r.rgb5[0]; out->rgb5[1] = r.rgb5[1]; out->rgb5[2] = r.rgb5[2]; out->changed = r.changed;
+    return SNES_OK;
+}
+
+int32_t snesimage_shared_step(snesimage_shared *s, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random,
+                              double *error, uint8_t *best_rgb5) {
+    CHECK(snesimage_shared_step_async(s, method, palette, index, channel, seed, step_id, n_random));
+    snesimage_call_result r;
+    CHECK(snesimage_shared_last_step(s, &r));
+    if (error) *error = r.error;
+    if (best_rgb5) { best_rgb5[0] = r.rgb5[0]; best_rgb5[1] = r.rgb5[1]; best_rgb5[2] = r.rgb5[2]; }
+    return SNES_OK;
+}
+
+// Tile reassignment stays per member: a tile's cost depends on its own pixels and the (shared) palette only.
+int32_t snesimage_shared_reassign_tiles(snesimage_shared *s, uint32_t *moved) {
+    CHECK(shared_enter(s));
+    uint32_t total = 0;
+    for (auto *c : members(s)) {
+        uint32_t m = 0;
+        CHECK(snesimage_reassign_tiles(c, &m));
+        total += m;
+    }
+    if (moved) *moved = total;
+    return shared_settle(s);
+}
+
+} // extern "C"

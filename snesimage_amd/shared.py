@@ -1,0 +1,118 @@
+"""One palette shared by several images: the frames of an animated background, the poses of a sprite, the
+screens of one level — on the SNES everything drawn on one background reads the same CGRAM.
+
+`SharedPalette(images)` borrows `OptimizedImage` contexts of the same size, palette geometry, chunk and flags, all holding
+the same palette, and optimizes that palette for all of them: the error of the set is the sum of the members' errors, in
+member order, and every optimizer call commits once on that sum.  Each member keeps its own tile palettes and palette map.
+The initialisers are the reference's own on the member stack (the members top to bottom, W x F*H).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from .api import METHOD_RANDOM, SnesImageError, _p
+
+
+class SharedPalette:
+    """A set over `images` (OptimizedImage, in member order).  Destroy the set (close) before its members."""
+
+    def __init__(self, images):
+        self.images = list(images)
+        self._L = _ffi.load()
+        arr = (C.c_void_p * len(self.images))(*[img._c for img in self.images])
+        h = C.c_void_p()
+        self._chk(self._L.snesimage_shared_create(arr if self.images else None, len(self.images), C.byref(h)))
+        self._s = h
+        first = self.images[0]
+        self.sub_count, self.sub_size, self.flags = first.sub_count, first.sub_size, first.flags
+
+    # -- lifetime -------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_s", None):
+            self._L.snesimage_shared_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SnesImageError(rc, self._L.snesimage_last_error().decode())
+
+    # -- the reference's methods over the set ----------------------------------------------------------
+    def initialize_tiles(self):  # lib.rs:79 on the member stack
+        self._chk(self._L.snesimage_shared_initialize_tiles(self._s))
+
+    def recalculate_palettes(self):  # lib.rs:407 on the member stack
+        self._chk(self._L.snesimage_shared_recalculate_palettes(self._s))
+
+    def error(self):
+        """E: the members' error() summed in member order."""
+        out = C.c_double()
+        self._chk(self._L.snesimage_shared_error(self._s, C.byref(out)))
+        return out.value
+
+    def score_candidates(self, palette, index, rgb5):
+        """E_k for every candidate (n x 3 raw 5-bit colours) in entry (palette, index); the members are left unchanged."""
+        cand = np.ascontiguousarray(rgb5, np.uint8).reshape(-1, 3)
+        out = np.zeros(cand.shape[0], np.float64)
+        self._chk(self._L.snesimage_shared_score_candidates(self._s, palette, index, _p(cand, _ffi._u8p), cand.shape[0],
+                                                            _p(out, _ffi._f64p)))
+        return out
+
+    def step(self, method, palette, index, channel=0, seed=1, step_id=0, n_random=0):
+        """One optimizer call on the set -> (E after the call, the slot's colour)."""
+        err = C.c_double()
+        best = np.zeros(3, np.uint8)
+        self._chk(self._L.snesimage_shared_step(self._s, method, palette, index, channel, seed, step_id, n_random,
+                                                C.byref(err), _p(best, _ffi._u8p)))
+        return err.value, best
+
+    def last_step(self):
+        """(E, best_k, rgb5, changed) of the last call."""
+        r = _ffi.CallResult()
+        self._chk(self._L.snesimage_shared_last_step(self._s, C.byref(r)))
+        return r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)
+
+    def run(self, n_calls, seed=1, first_step_id=0, state=(0, 0, 0, 0), n_random=0):
+        """The reference's loop (lib.rs:888-933) on the set, call by call: n_calls calls from scheduler state
+        (palette, index, channel, step), call j drawing its random candidates from (seed, first_step_id + j).
+        Returns (log, state): log[j] = (E, best_k, rgb5, changed) after call j."""
+        st = [C.c_uint32(int(v)) for v in state]
+        m = C.c_uint32(0)
+        nes = 1 if self.flags & 4 else 0
+        log = []
+        for j in range(n_calls):
+            p, idx, ch = st[0].value, st[1].value, st[2].value
+            self._L.snesimage_schedule_next(self.sub_count, self.sub_size, nes, C.byref(st[0]), C.byref(st[1]), C.byref(st[2]),
+                                            C.byref(st[3]), C.byref(m))
+            self._chk(self._L.snesimage_shared_step_async(self._s, m.value, p, idx, ch, seed, first_step_id + j,
+                                                          n_random if m.value == METHOD_RANDOM else 0))
+            log.append(self.last_step())
+        return log, tuple(v.value for v in st)
+
+    def reassign_tiles(self):
+        """snesimage_reassign_tiles on every member -> tiles moved in all."""
+        moved = C.c_uint32()
+        self._chk(self._L.snesimage_shared_reassign_tiles(self._s, C.byref(moved)))
+        return moved.value
+
+    # -- state ------------------------------------------------------------------------------------
+    @property
+    def palette(self):
+        return self.images[0].palette
+
+    @palette.setter
+    def palette(self, v):
+        v = np.ascontiguousarray(v, np.uint8).reshape(self.sub_count * self.sub_size, 3)
+        self._chk(self._L.snesimage_shared_set_palette_rgb5(self._s, _p(v, _ffi._u8p)))
