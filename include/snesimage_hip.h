@@ -219,6 +219,23 @@ int32_t snesimage_shared_last_step(snesimage_shared *set, snesimage_call_result 
 /* snesimage_reassign_tiles on every member (a tile's cost depends on its own pixels and the shared palette only);
  * *moved = tiles moved in all members. */
 int32_t snesimage_shared_reassign_tiles(snesimage_shared *set, uint32_t *moved);
+/* snesimage_run_slots for a set: the reference's loop for n_calls calls, several calls per launch set.  A window scores the
+ * coming K calls for every member against the current palette (a slot context per member and call, about 0.3 GB each),
+ * sums the members' errors in member order and commits the calls in schedule order up to the first one that accepts; the
+ * rest of the window is scored again.  For every `window` (0 = chosen by the library, 1 = call by call, K = at most K calls
+ * per launch set) everything observable afterwards equals snesimage_schedule_next + snesimage_shared_step per call, bit for
+ * bit: the shared palette, every member's palette_map, incumbent error and snesimage_last_step, the set's
+ * snesimage_shared_last_step, the scheduler state and every log record (log[j].error = E after call j).  Arguments as
+ * snesimage_run_slots.  stats count candidates per member: `scored` and `useful` are calls times candidates per call.
+ * F members times K calls stay within SNES_WINDOW_MAX (default 64) slot contexts, so K <= SNES_WINDOW_MAX / F; a set of
+ * more than SNES_WINDOW_MAX / 2 members, `window` = 1 and n_random > 64 are stepped call by call inside the function.
+ * Refusals as every set call: a retired set or a member changed outside the set give SNES_ERR_STATE. */
+int32_t snesimage_shared_run_slots(snesimage_shared *set, uint32_t n_calls, uint64_t seed, uint64_t first_step_id,
+                                   uint32_t *palette, uint32_t *index, uint32_t *channel, uint32_t *step, uint32_t n_random,
+                                   uint32_t window, snesimage_call_result *log, snesimage_run_stats *stats);
+/* Slot contexts for windows of up to n_slots calls (clamped to SNES_WINDOW_MAX / F) now rather than on first use.
+ * Allocation is grow-only; a failed allocation returns SNES_ERR_HIP and leaves the set usable. */
+int32_t snesimage_shared_slots_reserve(snesimage_shared *set, uint32_t n_slots);
 
 /* Dynamic tile -> subpalette reassignment — NOT a reference method: /root/reference/TODO.md:36-37 lists it as missing ("no
  * attempt is made to reassign tiles dynamically if it could improve the overall result").  Every tile with an opaque pixel

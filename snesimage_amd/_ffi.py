@@ -85,6 +85,9 @@ SIGNATURES = [
                                                 C.c_uint64, C.c_uint32]),
     ("snesimage_shared_last_step", C.c_int32, [C.c_void_p, C.POINTER(CallResult)]),
     ("snesimage_shared_reassign_tiles", C.c_int32, [C.c_void_p, _u32p]),
+    ("snesimage_shared_run_slots", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, _u32p, _u32p, _u32p, _u32p, C.c_uint32,
+                                               C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
+    ("snesimage_shared_slots_reserve", C.c_int32, [C.c_void_p, C.c_uint32]),
     ("snesimage_get_tile_palettes", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_tile_palettes", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_get_palette_rgb5", C.c_int32, [C.c_void_p, _u8p]),

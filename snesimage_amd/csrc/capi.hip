@@ -1565,4 +1565,5 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "batch_host.inc"
 #include "shared_host.inc"
 #include "window_host.inc"
+#include "shared_window_host.inc"
 #include "group_host.inc"

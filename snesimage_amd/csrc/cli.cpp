@@ -65,7 +65,8 @@ void usage() {
             "      --reassign-tiles <K> every K sweeps of the palette, move each tile to the subpalette that reproduces it best\n"
             "                           (off by default; not in the reference: its TODO.md lists it as missing)\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
-            "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>\n"
+            "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
+            "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only\n"
             "      --decode-only        write the decoded source as raw RGBA8 to <TARGET_FILENAME> and stop (no GPU)\n  -h, --help\n  -V, --version\n");
 }
 // the flat integer array stored under `"key":[...]` in one of this driver's (or the reference's) JSON outputs
@@ -184,7 +185,7 @@ int main(int argc, char **argv) {
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
-    if (!shares.empty()) { // a set is stepped call by call on one device, from the k-means initialisers
+    if (!shares.empty()) { // a set runs on one device, from the k-means initialisers; its windows are sized by the library (--window 0) or off (--window 1)
         const char *bad = !resume_file.empty() ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--share <SOURCE=TARGET>' cannot be used with %s\n", bad); return 2; }
     }
@@ -302,11 +303,11 @@ int main(int argc, char **argv) {
         }
         sweep = step;
     };
-    if (!set && ncand <= 64 && window != 1) {
+    if (ncand <= 64 && window != 1) {
         // The reference's loop (src/lib.rs:888-933), several calls per launch: snesimage_run_slots scores the coming calls of the
         // schedule against the current palette and applies them in order up to the first one that changes it — the same
         // trajectory, call for call, as stepping one call at a time (--window 1).  A run ends with its sweep when tiles are
-        // to be reassigned between sweeps.
+        // to be reassigned between sweeps.  --share: snesimage_shared_run_slots, the same for a set (the records carry E).
         std::vector<snesimage_call_result> log;
         if (snesimage_get_palette_rgb5(ctx, before.data()) != 0) die(snesimage_last_error());
         snesimage_run_stats total{};
@@ -321,8 +322,9 @@ int main(int argc, char **argv) {
             log.resize(n);
             uint32_t p = palette, ix = index, ch = channel, st = step, method = 0;
             snesimage_run_stats rs{};
-            if ((group ? snesimage_group_run_slots(group, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)
-                       : snesimage_run_slots(ctx, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)) != 0) die(std::string("Unable to optimize palette: ") + snesimage_last_error());
+            if ((set   ? snesimage_shared_run_slots(set, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)
+                 : group ? snesimage_group_run_slots(group, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)
+                         : snesimage_run_slots(ctx, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)) != 0) die(std::string("Unable to optimize palette: ") + snesimage_last_error());
             total.calls += rs.calls; total.accepted += rs.accepted; total.windows += rs.windows; total.scored += rs.scored; total.useful += rs.useful;
             for (uint32_t j = 0; j < n; j++) {
                 const uint32_t cp = p, ci = ix;

@@ -4,8 +4,12 @@
 // (ks_commit, kernels_shared.hpp).  The k-means initialisers run on the member stack — the members top to bottom in
 // member order, W x F*H — with the point order of the reference's own initialisers over that picture.
 
+struct snesimage_shared_window; // slot windows of the set (shared_window_host.inc)
+namespace { void shared_window_free(snesimage_shared_window *w); }
+
 struct snesimage_shared {
     snesimage_batch *b = nullptr;
+    snesimage_shared_window *win = nullptr;   // slot contexts and records of snesimage_shared_run_slots, made on first use
     snes::StepResult *d_joint = nullptr;      // the set's record of the last call (error = E)
     double *d_sum = nullptr; uint32_t sum_cap = 0; // snesimage_shared_score_candidates: E_k
     const double **d_tab = nullptr;           // the members' error vectors, for ks_sum
@@ -208,6 +212,8 @@ int32_t snesimage_shared_create(snesimage_ctx **ctxs, uint32_t n, snesimage_shar
 void snesimage_shared_destroy(snesimage_shared *s) {
     if (!s) return;
     (void)hipSetDevice(s->b->device);
+    if (s->b->stream) (void)hipStreamSynchronize(s->b->stream);
+    if (s->win) { shared_window_free(s->win); s->win = nullptr; } // (its slot contexts borrow the members' planes: before the members go)
     snesimage_batch_destroy(s->b); // (waits for its stream)
     if (s->d_joint) (void)hipFree(s->d_joint);
     if (s->d_sum) (void)hipFree(s->d_sum);

@@ -21,12 +21,14 @@
 // size that gets most calls through per unit of time is taken.  Results do not depend on it, only speed does.
 struct WindowPolicy {
     double calls = 0.0, accepts = 0.0;
-    uint32_t next(uint32_t used, uint32_t acc, uint32_t lo, uint32_t hi, uint32_t ranks, uint32_t taken) {
+    // weight: what one call of the window costs in units of a single image's call (a set of F members scores every call F times);
+    // sizes below 4 (a set whose storage holds few calls) double instead of stepping by 4
+    uint32_t next(uint32_t used, uint32_t acc, uint32_t lo, uint32_t hi, uint32_t ranks, uint32_t taken, double weight = 1.0) {
         calls = 0.85 * calls + used; accepts = 0.85 * accepts + acc;
         const double p = (accepts + 0.5) / (calls + 8.0);
         double best = -1.0; uint32_t best_k = lo;
-        for (uint32_t k = lo; k <= hi; k += (k < 32 * ranks ? 4 : 8) * ranks) {
-            const double through = (1.0 - std::pow(1.0 - p, (double)k)) / p, rate = through / (15.0 + (double)k / ranks);
+        for (uint32_t k = lo; k <= hi; k = k < 4 ? 2 * k : k + (k < 32 * ranks ? 4 : 8) * ranks) {
+            const double through = (1.0 - std::pow(1.0 - p, (double)k)) / p, rate = through / (15.0 + weight * (double)k / ranks);
             if (rate > best) { best = rate; best_k = k; }
         }
         if (!acc && used == taken) { const uint32_t twice = 2 * taken > hi ? hi : 2 * taken; if (twice > best_k) best_k = twice; } // a clean window: at least twice as many next (the estimate takes a few windows to forget a phase of frequent acceptances)

@@ -101,6 +101,22 @@ class SharedPalette:
             log.append(self.last_step())
         return log, tuple(v.value for v in st)
 
+    def run_slots(self, n_calls, seed=1, first_step_id=0, state=(0, 0, 0, 0), window=0, want_log=True, n_random=0):
+        """The same loop, several calls per launch set (snesimage_shared_run_slots): bit-identical to `run`, for every
+        `window` (0 = chosen by the library, 1 = call by call, K = at most K calls per launch set).  Returns
+        (log, state, stats), shaped like OptimizedImage.run_slots; log[j] = (E, best_k, rgb5, changed) after call j."""
+        st = [C.c_uint32(int(v)) for v in state]
+        log = (_ffi.CallResult * n_calls)() if want_log else None
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_shared_run_slots(self._s, n_calls, seed, first_step_id, C.byref(st[0]), C.byref(st[1]),
+                                                     C.byref(st[2]), C.byref(st[3]), int(n_random), int(window), log, C.byref(stats)))
+        out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log] if want_log else None
+        return out, tuple(v.value for v in st), {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    def reserve_slots(self, n):
+        """Allocate the slot contexts of windows of up to n calls now instead of on first use (about 0.3 GB per member and call)."""
+        self._chk(self._L.snesimage_shared_slots_reserve(self._s, int(n)))
+
     def reassign_tiles(self):
         """snesimage_reassign_tiles on every member -> tiles moved in all."""
         moved = C.c_uint32()
