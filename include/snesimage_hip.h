@@ -246,6 +246,41 @@ int32_t snesimage_shared_slots_reserve(snesimage_shared *set, uint32_t n_slots);
  * member (the result is deterministic: the replicas stay identical), never on one alone. */
 int32_t snesimage_reassign_tiles(snesimage_ctx *ctx, uint32_t *moved);
 
+/* Tile moves decided by the objective — NOT a reference method either.  Tiles are numbered as tile_palettes is indexed
+ * (t = ty * 32 + tx).  A TILE CALL on tile t, whose subpalette is cur: for k = 0 .. sub_count - 1 ascending, k != cur:
+ * tile_palettes[t] := k, optimize(), e_k := error(); acceptance is lib.rs:216-219 (best := incumbent error; e_k < best, strict,
+ * takes best := e_k).  If some k was taken the state becomes that candidate's (tile_palettes[t], its palette_map, the incumbent
+ * error); otherwise it is untouched bit for bit.  The palette never changes.  With --dither optimize() is the whole
+ * Floyd-Steinberg run, so a move may change pixels to the right of and below the tile.  A tile without an opaque pixel and a
+ * move between subpalettes that render the tile identically give e_k == incumbent exactly and are never taken.
+ * A TILE SWEEP over first_tile, n_tiles is the tile calls on those tiles in that order, each seeing the state the one before
+ * left.  snesimage_reassign_tiles moves tiles by a proxy (colour distance, no dithering) that disagrees with the objective:
+ * applied after a sweep it moves the tiles back.  Use one or the other in a run.
+ * All candidates are scored in batches by the map-reading scorer (every distance, --dither, every height and geometry).
+ * Refusals: null context, first_tile + n_tiles beyond (w/8)*(h/8), subs[j] >= sub_count: SNES_ERR_ARG; between the two phases
+ * of a split-phase step: SNES_ERR_STATE; a failed workspace allocation: SNES_ERR_HIP, the context usable and unchanged.  On
+ * the members of a group the rule of snesimage_reassign_tiles holds. */
+typedef struct { double error; int32_t sub; uint8_t changed; } snesimage_tile_result; /* incumbent error and the tile's subpalette after the call */
+/* e_j for n explicit (tile, subpalette) pairs against the current state, which is left unchanged.  A pair naming the tile's
+ * current subpalette returns the incumbent error bit for bit.  maps_out (optional, n*w*h bytes): each candidate's palette_map.
+ * Host pointers; synchronous.  n may exceed the chunk (launch groups as in snesimage_score_candidates, at most 512 pairs each). */
+int32_t snesimage_score_tile_moves(snesimage_ctx *ctx, const uint16_t *tiles, const uint8_t *subs, uint32_t n,
+                                   double *errors, uint8_t *maps_out);
+/* One tile call. */
+int32_t snesimage_tile_step(snesimage_ctx *ctx, uint32_t tile, snesimage_tile_result *out);
+/* A tile sweep, several tile calls per launch set: a window scores the candidates of the coming K calls against the image as
+ * it stands in one batch, commits the calls in order on the device up to the first that accepts, and the calls behind it
+ * are scored again by the next window (one synchronisation per window).  window: 0 = chosen by the library, 1 = call by
+ * call, K = at most K calls per launch set.  For every window everything observable afterwards equals tile call after tile
+ * call, bit for bit.  log (optional): n_tiles records.  stats (optional): as snesimage_run_slots (voided = 0). */
+int32_t snesimage_tile_sweep(snesimage_ctx *ctx, uint32_t first_tile, uint32_t n_tiles, uint32_t window,
+                             snesimage_tile_result *log, snesimage_run_stats *stats);
+/* The same on every member of a set, member after member: a tile move in member i changes e_i alone, so each call is decided
+ * on the member's own error (strict < on e_i, not on the rounded sum E) — exactly snesimage_tile_sweep on each member.
+ * log: F * n_tiles records, member-major; stats summed over the members. */
+int32_t snesimage_shared_tile_sweep(snesimage_shared *set, uint32_t first_tile, uint32_t n_tiles, uint32_t window,
+                                    snesimage_tile_result *log, snesimage_run_stats *stats);
+
 /* State access (the reference mutates these fields directly: lib.rs:1015 and the GUI). */
 int32_t snesimage_get_tile_palettes(snesimage_ctx *ctx, uint8_t *out /*1024*/);
 int32_t snesimage_set_tile_palettes(snesimage_ctx *ctx, const uint8_t *in /*1024*/);

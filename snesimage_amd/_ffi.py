@@ -30,6 +30,11 @@ class RunStats(C.Structure):
                 ("scored", C.c_uint64), ("useful", C.c_uint64)]
 
 
+class TileResult(C.Structure):
+    """snesimage_tile_result: incumbent error and the tile's subpalette after a tile call."""
+    _fields_ = [("error", C.c_double), ("sub", C.c_int32), ("changed", C.c_uint8)]
+
+
 # every symbol include/snesimage_hip.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("snesimage_create", C.c_int32, [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
@@ -43,6 +48,10 @@ SIGNATURES = [
     ("snesimage_optimize", C.c_int32, [C.c_void_p]),
     ("snesimage_error", C.c_int32, [C.c_void_p, _f64p]),
     ("snesimage_reassign_tiles", C.c_int32, [C.c_void_p, _u32p]),
+    ("snesimage_score_tile_moves", C.c_int32, [C.c_void_p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_tile_step", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(TileResult)]),
+    ("snesimage_tile_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
+    ("snesimage_shared_tile_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
     ("snesimage_score_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _f64p]),
     ("snesimage_score_candidates_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]),

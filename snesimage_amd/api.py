@@ -12,6 +12,7 @@ from . import _ffi
 
 DITHER, PERCEPTUAL, NES = 1, 2, 4
 METHOD_RANDOM, METHOD_CHANNEL, METHOD_NES = 0, 1, 2
+TILE_LOG_DTYPE = np.dtype([("error", np.float64), ("sub", np.int32), ("changed", np.uint8)])  # one record of a tile sweep's log
 
 
 class SnesImageError(RuntimeError):
@@ -124,6 +125,38 @@ class OptimizedImage:
         moved = C.c_uint32(0)
         self._chk(self._L.snesimage_reassign_tiles(self._c, C.byref(moved)))
         return moved.value
+
+    def score_tile_moves(self, tiles, subs, want_maps=False):
+        """error() of the image with tile tiles[j] drawn from subpalette subs[j], for every j; the state is left unchanged.
+        Returns errors (float64), or (errors, maps[n, h, w]) with want_maps."""
+        tiles = np.ascontiguousarray(tiles, np.uint16).reshape(-1)
+        subs = np.ascontiguousarray(subs, np.uint8).reshape(-1)
+        if tiles.size != subs.size:
+            raise ValueError("tiles and subs differ in length")
+        errs = np.zeros(tiles.size, np.float64)
+        maps = np.zeros((tiles.size, self.h, self.w), np.uint8) if want_maps else None
+        self._chk(self._L.snesimage_score_tile_moves(self._c, _p(tiles, _ffi._u16p), _p(subs, _ffi._u8p), tiles.size, _p(errs, _ffi._f64p),
+                                                     _p(maps, _ffi._u8p) if want_maps else None))
+        return (errs, maps) if want_maps else errs
+
+    def tile_step(self, tile):
+        """One tile call: the tile moves to the subpalette with the strictly lowest error(), if one beats the incumbent.
+        Returns (error, sub, changed)."""
+        r = _ffi.TileResult()
+        self._chk(self._L.snesimage_tile_step(self._c, int(tile), C.byref(r)))
+        return r.error, r.sub, int(r.changed)
+
+    def tile_sweep(self, first_tile=0, n_tiles=None, window=0):
+        """Tile calls on first_tile .. first_tile + n_tiles - 1 in order, several per launch set (bit-identical to
+        `tile_step` per tile for every `window`: 0 = chosen by the library, 1 = call by call, K = at most K calls).
+        Returns (log, stats): log is a structured array (error, sub, changed), one record per tile."""
+        if n_tiles is None:
+            n_tiles = (self.w // 8) * (self.h // 8) - int(first_tile)
+        log = (_ffi.TileResult * max(1, n_tiles))()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_tile_sweep(self._c, int(first_tile), int(n_tiles), int(window), log, C.byref(stats)))
+        out = np.array([(r.error, r.sub, r.changed) for r in log[:n_tiles]], dtype=TILE_LOG_DTYPE)
+        return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
     def score_candidates(self, palette, index, rgb5):
         """Loop body of lib.rs:205-220 for an explicit candidate list -> errors (float64)."""

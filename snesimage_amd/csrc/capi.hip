@@ -8,6 +8,7 @@
 #include "kernels_sparse2.hpp"
 #include "kernels_batch.hpp"
 #include "kernels_shared.hpp"
+#include "kernels_tile.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -207,6 +208,7 @@ struct snesimage_ctx {
     struct snesimage_window *win = nullptr;  // slot windows of snesimage_run_slots (window_host.inc), created on first use
     bool win_pend = false;                   // snesimage_slots_begin without its snesimage_slots_commit yet
     bool pack_borrowed = false;              // a slot context of a --dither window: pack and subpalette planes are the parent's
+    struct snesimage_tilework *tile = nullptr; // workspace of the objective-scored tile moves (tile_host.inc), created on first use
 
     // cache keys
     bool tables_valid = false, src_valid = false, inc_valid = false;
@@ -367,6 +369,75 @@ int32_t run_prep(snesimage_ctx *c, int mode, int sp, int si) {
 // the transparent-pixel marker, which any mode provides (mode 1 is the cheapest).
 int32_t prep_for_slot(snesimage_ctx *c, int sp, int si) { return c->dither ? run_prep(c, 1, -1, -1) : run_prep(c, 2, sp, si); }
 
+// The scoring stages behind the candidates' pixels (downscale, H and V pass per scale, final score) on the planes, pack and
+// per-candidate maps of `V`: the context's own for score_chunk, the tile workspace's for tile_host.inc.
+struct DenseView {
+    const unsigned long long *pack, *packT, *packC4, *packR4; const uint8_t *subC4, *subR4, *tile_pal;
+    float *work, *cand_tab, *cand_lab; double *part; const uint8_t *maps, *mapsT, *mapsC4, *mapsR4;
+    bool use_maps, perceptual;
+};
+int32_t score_stages(snesimage_ctx *c, const DenseView &V, uint32_t nc, double *d_errors, int err_stride, int err_offset, snesimage_ctx::TimingRec *tr) {
+    const Geom &G = c->G;
+    const int npairs = (int)nc * 3;
+    if (G.nscales > 1) {
+        DownParams D{}; D.G = G; D.pack = V.pack; D.pal_lin = c->d_pal_lin; D.cand_tab = V.cand_tab; D.cand_lab = V.cand_lab; D.labpx = c->d_labpx;
+        D.work = V.work; D.ncol = c->ncol; D.perceptual = V.perceptual ? 1 : 0; D.use_maps = V.use_maps ? 1 : 0; D.fast_mask = c->fast_mask & ~1; D.maps = V.maps; D.tile_pal = V.tile_pal; D.sub_size = (int)c->sub_size;
+        hipLaunchKernelGGL(k_downscale_chain<true>, dim3(down_grid(G), nc), dim3(256), 0, c->stream, D);
+    }
+    const bool fast0 = (c->fast_mask & 1) && (V.use_maps || !V.perceptual); // scale 0 takes its pixels from the pack (RGB keys) or from the per-candidate maps (dither)
+    auto is_fast = [&](int s) { return s == 0 ? fast0 : ((c->fast_mask >> s) & 1) != 0; };
+    auto fast_params = [&](int s) {
+        FastParams F{}; F.G = G; F.K = c->K; F.s = s; F.npairs = npairs; F.ncol = c->ncol;
+        F.packC4 = V.packC4; F.packR4 = V.packR4; F.pal_xyb = c->d_pal_xyb; F.cand_tab = V.cand_tab;
+        F.use_maps = V.use_maps ? 1 : 0; F.mapsC4 = reinterpret_cast<const uint32_t *>(V.mapsC4); F.mapsR4 = reinterpret_cast<const uint32_t *>(V.mapsR4);
+        F.subC4 = reinterpret_cast<const uint32_t *>(V.subC4); F.subR4 = reinterpret_cast<const uint32_t *>(V.subR4);
+        F.img1C4 = c->d_img1C4 + G.src_off[s]; F.mu1R4 = c->d_mu1R4 + G.src_off[s]; F.sd1R4 = c->d_sd1R4 + G.src_off[s]; F.a1R4 = c->d_a1R4 + G.src_off[s]; F.r1R4 = c->d_r1R4 + G.src_off[s];
+        F.work = V.work; F.part = V.part;
+        return F;
+    };
+    for (int s = 0; s < G.nscales; s++) {
+        if (s == 0 && tr && c->timing == 1) HIPCHK(hipEventRecord(tr->ev[1], c->stream));
+        if (is_fast(s)) {
+            FastParams F = fast_params(s);
+            dim3 grid((unsigned)(npairs * (G.sh[s] / 64)));
+            if (s == 0) hipLaunchKernelGGL((k_hpass_fast<true>), grid, dim3(64), 0, c->stream, F);
+            else hipLaunchKernelGGL((k_hpass_fast<false>), grid, dim3(64), 0, c->stream, F);
+        } else {
+            HParams Hp{}; Hp.G = G; Hp.K = c->K; Hp.s = s; Hp.npairs = npairs; Hp.ncol = c->ncol; Hp.perceptual = V.perceptual ? 1 : 0; Hp.use_maps = V.use_maps ? 1 : 0; Hp.sub_size = (int)c->sub_size;
+            Hp.packT = V.packT; Hp.pal_xyb = c->d_pal_xyb; Hp.cand_tab = V.cand_tab; Hp.cand_lab = V.cand_lab; Hp.labpxT = c->d_labpxT;
+            Hp.in1T = c->d_img1T + G.src_off[s]; Hp.in2T = nullptr; Hp.work = V.work; Hp.mapsT = V.mapsT; Hp.tile_pal = V.tile_pal;
+            int ppw = 256 / G.sh[s];
+            dim3 grid((npairs + ppw - 1) / ppw);
+            if (s == 0) {
+                if (V.perceptual && !V.use_maps) hipLaunchKernelGGL((k_hpass<true, true>), grid, dim3(256), 0, c->stream, Hp);
+                else hipLaunchKernelGGL((k_hpass<true, false>), grid, dim3(256), 0, c->stream, Hp);
+            } else hipLaunchKernelGGL((k_hpass<false, false>), grid, dim3(256), 0, c->stream, Hp);
+        }
+        if (s == 0 && tr && c->timing == 1) HIPCHK(hipEventRecord(tr->ev[2], c->stream));
+        // the V pass of the same scale follows immediately, while its H output is still cache-resident
+        if (s == 0 && tr && c->timing) HIPCHK(hipEventRecord(tr->ev[3], c->stream));
+        int ppv = 256 / G.sw[s];
+        dim3 grid((npairs + ppv - 1) / ppv);
+        if (is_fast(s)) {
+            FastParams F = fast_params(s);
+            if (s == 0) hipLaunchKernelGGL((k_vpass_fast<true>), grid, dim3(256), 0, c->stream, F);
+            else hipLaunchKernelGGL((k_vpass_fast<false>), grid, dim3(256), 0, c->stream, F);
+        } else {
+            VParams Vp{}; Vp.G = G; Vp.K = c->K; Vp.s = s; Vp.npairs = npairs; Vp.ncol = c->ncol; Vp.perceptual = V.perceptual ? 1 : 0; Vp.use_maps = V.use_maps ? 1 : 0; Vp.sub_size = (int)c->sub_size;
+            Vp.pack = V.pack; Vp.pal_xyb = c->d_pal_xyb; Vp.cand_tab = V.cand_tab; Vp.cand_lab = V.cand_lab; Vp.labpx = c->d_labpx;
+            Vp.mu1 = c->d_mu1 + G.src_off[s]; Vp.sd1 = c->d_sd1 + G.src_off[s]; Vp.a1 = c->d_a1 + G.src_off[s]; Vp.r1 = c->d_r1 + G.src_off[s]; Vp.work = V.work; Vp.part = V.part;
+            Vp.maps = V.maps; Vp.tile_pal = V.tile_pal;
+            if (s == 0) {
+                if (V.perceptual && !V.use_maps) hipLaunchKernelGGL((k_vpass<true, false, true>), grid, dim3(256), 0, c->stream, Vp);
+                else hipLaunchKernelGGL((k_vpass<true, false, false>), grid, dim3(256), 0, c->stream, Vp);
+            } else hipLaunchKernelGGL((k_vpass<false, false, false>), grid, dim3(256), 0, c->stream, Vp);
+        }
+        if (s == 0 && tr && c->timing) HIPCHK(hipEventRecord(tr->ev[4], c->stream));
+    }
+    hipLaunchKernelGGL(k_final_score, dim3((nc + 63) / 64), dim3(64), 0, c->stream, V.part, (int)nc, G, d_errors, err_stride, err_offset);
+    return SNES_OK;
+}
+
 // k_dither instantiations: the 15-colour subpalettes of the SNES 4bpp modes get a fully unrolled entry search
 void launch_dither(snesimage_ctx *c, const DitherParams &Dp, uint32_t nblocks) {
     if (c->perceptual && c->dither4 && nblocks <= c->dither4_max) hipLaunchKernelGGL((k_dither4_lab<0>), dim3(nblocks), dim3(512), 0, c->stream, Dp); // (optimize() of the committed palette: one run)
@@ -380,8 +451,6 @@ void launch_dither(snesimage_ctx *c, const DitherParams &Dp, uint32_t nblocks) {
 // Score nc candidates (device rgb5 list) given a prepared pack; errors -> d_errors[err_offset + k*err_stride].
 // slot_ci: colour index of the slot being replaced (dither path), or -1.
 int32_t score_chunk(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t nc, double *d_errors, int err_stride, int err_offset, int sp, int si, uint8_t *d_maps_out) {
-    const Geom &G = c->G;
-    const int npairs = (int)nc * 3;
     const bool use_maps = c->dither;
     const uint32_t slot_ci = (sp >= 0) ? (uint32_t)(sp * (int)c->sub_size + si) : 0xffffffffu;
     snesimage_ctx::TimingRec tr{}; tr.n = nc;
@@ -404,62 +473,9 @@ int32_t score_chunk(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t nc, double
         M.npx = (int)c->npx; M.ncol = c->ncol; M.sub_size = (int)c->sub_size; M.si = si < 0 ? 0 : si; M.ncand = (int)nc; M.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_candidate_maps, dim3((unsigned)((c->npx + 255) / 256), nc), dim3(256), 0, c->stream, M);
     }
-    if (G.nscales > 1) {
-        DownParams D{}; D.G = G; D.pack = c->d_pack; D.pal_lin = c->d_pal_lin; D.cand_tab = c->d_cand_tab; D.cand_lab = c->d_cand_lab; D.labpx = c->d_labpx;
-        D.work = c->d_work; D.ncol = c->ncol; D.perceptual = c->perceptual ? 1 : 0; D.use_maps = use_maps ? 1 : 0; D.fast_mask = c->fast_mask & ~1; D.maps = c->d_maps; D.tile_pal = c->d_tile_pal; D.sub_size = (int)c->sub_size;
-        hipLaunchKernelGGL(k_downscale_chain<true>, dim3(down_grid(G), nc), dim3(256), 0, c->stream, D);
-    }
-    const bool fast0 = (c->fast_mask & 1) && (use_maps || !c->perceptual); // scale 0 takes its pixels from the pack (RGB keys) or from the per-candidate maps (dither)
-    auto is_fast = [&](int s) { return s == 0 ? fast0 : ((c->fast_mask >> s) & 1) != 0; };
-    auto fast_params = [&](int s) {
-        FastParams F{}; F.G = G; F.K = c->K; F.s = s; F.npairs = npairs; F.ncol = c->ncol;
-        F.packC4 = c->d_packC4; F.packR4 = c->d_packR4; F.pal_xyb = c->d_pal_xyb; F.cand_tab = c->d_cand_tab;
-        F.use_maps = use_maps ? 1 : 0; F.mapsC4 = reinterpret_cast<const uint32_t *>(c->d_mapsC4); F.mapsR4 = reinterpret_cast<const uint32_t *>(c->d_mapsR4);
-        F.subC4 = reinterpret_cast<const uint32_t *>(c->d_subC4); F.subR4 = reinterpret_cast<const uint32_t *>(c->d_subR4);
-        F.img1C4 = c->d_img1C4 + G.src_off[s]; F.mu1R4 = c->d_mu1R4 + G.src_off[s]; F.sd1R4 = c->d_sd1R4 + G.src_off[s]; F.a1R4 = c->d_a1R4 + G.src_off[s]; F.r1R4 = c->d_r1R4 + G.src_off[s];
-        F.work = c->d_work; F.part = c->d_part;
-        return F;
-    };
-    for (int s = 0; s < G.nscales; s++) {
-        if (s == 0 && c->timing == 1) HIPCHK(hipEventRecord(tr.ev[1], c->stream));
-        if (is_fast(s)) {
-            FastParams F = fast_params(s);
-            dim3 grid((unsigned)(npairs * (G.sh[s] / 64)));
-            if (s == 0) hipLaunchKernelGGL((k_hpass_fast<true>), grid, dim3(64), 0, c->stream, F);
-            else hipLaunchKernelGGL((k_hpass_fast<false>), grid, dim3(64), 0, c->stream, F);
-        } else {
-            HParams Hp{}; Hp.G = G; Hp.K = c->K; Hp.s = s; Hp.npairs = npairs; Hp.ncol = c->ncol; Hp.perceptual = c->perceptual ? 1 : 0; Hp.use_maps = use_maps ? 1 : 0; Hp.sub_size = (int)c->sub_size;
-            Hp.packT = c->d_packT; Hp.pal_xyb = c->d_pal_xyb; Hp.cand_tab = c->d_cand_tab; Hp.cand_lab = c->d_cand_lab; Hp.labpxT = c->d_labpxT;
-            Hp.in1T = c->d_img1T + G.src_off[s]; Hp.in2T = nullptr; Hp.work = c->d_work; Hp.mapsT = c->d_mapsT; Hp.tile_pal = c->d_tile_pal;
-            int ppw = 256 / G.sh[s];
-            dim3 grid((npairs + ppw - 1) / ppw);
-            if (s == 0) {
-                if (c->perceptual && !use_maps) hipLaunchKernelGGL((k_hpass<true, true>), grid, dim3(256), 0, c->stream, Hp);
-                else hipLaunchKernelGGL((k_hpass<true, false>), grid, dim3(256), 0, c->stream, Hp);
-            } else hipLaunchKernelGGL((k_hpass<false, false>), grid, dim3(256), 0, c->stream, Hp);
-        }
-        if (s == 0 && c->timing == 1) HIPCHK(hipEventRecord(tr.ev[2], c->stream));
-        // the V pass of the same scale follows immediately, while its H output is still cache-resident
-        if (s == 0 && c->timing) HIPCHK(hipEventRecord(tr.ev[3], c->stream));
-        int ppv = 256 / G.sw[s];
-        dim3 grid((npairs + ppv - 1) / ppv);
-        if (is_fast(s)) {
-            FastParams F = fast_params(s);
-            if (s == 0) hipLaunchKernelGGL((k_vpass_fast<true>), grid, dim3(256), 0, c->stream, F);
-            else hipLaunchKernelGGL((k_vpass_fast<false>), grid, dim3(256), 0, c->stream, F);
-        } else {
-            VParams Vp{}; Vp.G = G; Vp.K = c->K; Vp.s = s; Vp.npairs = npairs; Vp.ncol = c->ncol; Vp.perceptual = c->perceptual ? 1 : 0; Vp.use_maps = use_maps ? 1 : 0; Vp.sub_size = (int)c->sub_size;
-            Vp.pack = c->d_pack; Vp.pal_xyb = c->d_pal_xyb; Vp.cand_tab = c->d_cand_tab; Vp.cand_lab = c->d_cand_lab; Vp.labpx = c->d_labpx;
-            Vp.mu1 = c->d_mu1 + G.src_off[s]; Vp.sd1 = c->d_sd1 + G.src_off[s]; Vp.a1 = c->d_a1 + G.src_off[s]; Vp.r1 = c->d_r1 + G.src_off[s]; Vp.work = c->d_work; Vp.part = c->d_part;
-            Vp.maps = c->d_maps; Vp.tile_pal = c->d_tile_pal;
-            if (s == 0) {
-                if (c->perceptual && !use_maps) hipLaunchKernelGGL((k_vpass<true, false, true>), grid, dim3(256), 0, c->stream, Vp);
-                else hipLaunchKernelGGL((k_vpass<true, false, false>), grid, dim3(256), 0, c->stream, Vp);
-            } else hipLaunchKernelGGL((k_vpass<false, false, false>), grid, dim3(256), 0, c->stream, Vp);
-        }
-        if (s == 0 && c->timing) HIPCHK(hipEventRecord(tr.ev[4], c->stream));
-    }
-    hipLaunchKernelGGL(k_final_score, dim3((nc + 63) / 64), dim3(64), 0, c->stream, c->d_part, (int)nc, G, d_errors, err_stride, err_offset);
+    { DenseView V{c->d_pack, c->d_packT, c->d_packC4, c->d_packR4, c->d_subC4, c->d_subR4, c->d_tile_pal, c->d_work, c->d_cand_tab, c->d_cand_lab, c->d_part, c->d_maps, c->d_mapsT, c->d_mapsC4, c->d_mapsR4,
+                  use_maps, c->perceptual};
+      CHECK(score_stages(c, V, nc, d_errors, err_stride, err_offset, &tr)); }
     if (use_maps) hipLaunchKernelGGL(k_keep_best, dim3(1), dim3(1024), 0, c->stream, d_errors, err_stride, err_offset, (int)nc, c->d_maps, (int)c->npx, c->d_bestrec, c->d_bestmap);
     HIPCHK(hipGetLastError());
     if (c->timing) { tr.light = c->timing != 1; if (!tr.light) HIPCHK(hipEventRecord(tr.ev[5], c->stream)); c->t_pending.push_back(tr); }
@@ -1139,10 +1155,11 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
 
 void batch_forget(struct snesimage_batch *b, snesimage_ctx *c);
 void group_forget(struct snesimage_group *g, snesimage_ctx *c);
-namespace { void window_free(struct snesimage_window *w); }
+namespace { void window_free(struct snesimage_window *w); void tile_free(snesimage_ctx *c); }
 void snesimage_destroy(snesimage_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
+    if (c->tile) { if (c->stream) (void)hipStreamSynchronize(c->stream); tile_free(c); }
     if (c->win) { if (c->stream) (void)hipStreamSynchronize(c->stream); window_free(c->win); c->win = nullptr; } // its slot contexts borrow this context's planes
     if (c->owner) batch_forget(c->owner, c); // waits for the batch's stream and retires the batch
     if (c->group) group_forget(c->group, c); // retires the group: its other members are their own again
@@ -1567,3 +1584,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "window_host.inc"
 #include "shared_window_host.inc"
 #include "group_host.inc"
+#include "tile_host.inc"

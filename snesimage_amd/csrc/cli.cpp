@@ -64,6 +64,9 @@ void usage() {
             "      --preview <F>        write source | result as a PNG\n"
             "      --reassign-tiles <K> every K sweeps of the palette, move each tile to the subpalette that reproduces it best\n"
             "                           (off by default; not in the reference: its TODO.md lists it as missing)\n"
+            "      --tile-moves <K>     every K sweeps of the palette, try every tile in every other subpalette and keep the moves that\n"
+            "                           lower the error itself (dithering included); cannot be used with --reassign-tiles, which\n"
+            "                           moves tiles by colour distance and undoes these moves, nor with --devices\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
             "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only\n"
@@ -146,7 +149,7 @@ void write_json(snesimage_ctx *ctx, const std::string &target) { // src/lib.rs:1
 
 int main(int argc, char **argv) {
     std::vector<std::string> pos;
-    uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, window = 0; // src/config.rs:13-18 defaults
+    uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, tile_every = 0, window = 0; // src/config.rs:13-18 defaults
     uint64_t seed = 1;
     int device = 0;
     std::string tile_file, preview_file, resume_file;
@@ -170,6 +173,7 @@ int main(int argc, char **argv) {
         else if (a == "--tile-palettes") tile_file = need("--tile-palettes");
         else if (a == "--preview") preview_file = need("--preview");
         else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
+        else if (a == "--tile-moves") tile_every = (uint32_t)strtoul(need("--tile-moves"), nullptr, 10);
         else if (a == "--resume") resume_file = need("--resume");
         else if (a == "--share") {
             const std::string v = need("--share");
@@ -182,6 +186,10 @@ int main(int argc, char **argv) {
         else if (a == "-V" || a == "--version") { printf("snesimage 0.1.1 (%s)\n", snesimage_version()); return 0; }
         else if (!a.empty() && a[0] == '-' && a != "-") { fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str()); usage(); return 2; }
         else pos.push_back(a);
+    }
+    if (tile_every) { // objective-scored moves and the colour-distance proxy undo each other; no group entry point for the moves
+        const char *bad = !devices.empty() ? "'--devices'" : (reassign_every ? "'--reassign-tiles'" : nullptr);
+        if (bad) { fprintf(stderr, "error: the argument '--tile-moves <K>' cannot be used with %s\n", bad); return 2; }
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
@@ -301,6 +309,15 @@ int main(int argc, char **argv) {
             else for (snesimage_ctx *m : members) if (snesimage_reassign_tiles(m, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error());
             log_info("Reassigned " + std::to_string(moved) + " tiles");
         }
+        if (tile_every && step != sweep && step % tile_every == 0) { // one tile sweep over the whole image, each call decided by error()
+            const uint32_t ntile = 32 * (h / 8);
+            snesimage_run_stats ts{};
+            double e = 0.0;
+            if (set ? (snesimage_shared_tile_sweep(set, 0, ntile, 0, nullptr, &ts) != 0 || snesimage_shared_error(set, &e) != 0)
+                    : (snesimage_tile_sweep(ctx, 0, ntile, 0, nullptr, &ts) != 0 || snesimage_error(ctx, &e) != 0)) die(std::string("Unable to move tiles: ") + snesimage_last_error());
+            log_info("Moved " + std::to_string(ts.accepted) + " tiles in " + std::to_string(ts.windows) + " launch sets");
+            if (std::abs(e - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e)); last_error = e; }
+        }
         sweep = step;
     };
     if (ncand <= 64 && window != 1) {
@@ -314,7 +331,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every) { // calls left in the current sweep
+            if (reassign_every || tile_every) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { snesimage_schedule_next(count, size, nes, &p, &ix, &ch, &st, &m); k++; }
                 n = k;

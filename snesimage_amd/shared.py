@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .api import METHOD_RANDOM, SnesImageError, _p
+from .api import METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
 
 
 class SharedPalette:
@@ -122,6 +122,18 @@ class SharedPalette:
         moved = C.c_uint32()
         self._chk(self._L.snesimage_shared_reassign_tiles(self._s, C.byref(moved)))
         return moved.value
+
+    def tile_sweep(self, first_tile=0, n_tiles=None, window=0):
+        """OptimizedImage.tile_sweep on every member, member after member (each call decided on the member's own error).
+        Returns (log[F, n_tiles], stats)."""
+        if n_tiles is None:
+            n_tiles = (self.images[0].w // 8) * (self.images[0].h // 8) - int(first_tile)
+        F = len(self.images)
+        log = (_ffi.TileResult * max(1, F * n_tiles))()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_shared_tile_sweep(self._s, int(first_tile), int(n_tiles), int(window), log, C.byref(stats)))
+        out = np.array([(r.error, r.sub, r.changed) for r in log[:F * n_tiles]], dtype=TILE_LOG_DTYPE).reshape(F, n_tiles)
+        return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
     # -- state ------------------------------------------------------------------------------------
     @property
