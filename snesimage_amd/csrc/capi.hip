@@ -171,6 +171,10 @@ struct snesimage_ctx {
         bool vsplit = true; // B's wide V sweep with recurrences and maps on two waves (k_sparse_v2_base_split; SNES_VSPLIT=0: one wave does both)
         uint32_t scan4_max = 2048; // longest list whose scan deals a candidate's contested pixels to four waves (SNES_SCAN4_MAX; 0 = never)
         uint32_t hgrid = 8192; // most blocks per scale of k_sparse_h (grid-stride beyond)
+        // Candidates of one list with one colour are one image: the lowest index is scored, the others take its error (kernels.hpp,
+        // dedup_*).  Lists without dither of dedup_min candidates and more (SNES_DEDUP=0: never; SNES_DEDUP_MIN): a random
+        // list of 1,024 holds 16 repeats, one of 4,096 holds 245 (6 %), and a shorter call has nothing to pay a further launch with.
+        bool dedup = true; uint32_t dedup_min = 1024; int *holder = nullptr; bool holder_dirty = false; // holder_dirty: a call failed between marking and reset
         bool enabled = false, side = true; uint32_t min_n = 1; uint32_t cap = 0, lanes = 0; // min_n: shortest list that takes the group-sparse path (SNES_SPARSE_MIN; until round 4: 64 — a channel sweep's 32 candidates, or a rank's share of a 64-candidate call, went the dense way: 0.35 ms against 0.27, 1.7 ms with --perceptual-palettes) // cap = candidates per lane the arrays were sized for
         SparseGeom S{};
         float *store = nullptr, *cand_tab = nullptr, *cand_lab = nullptr, *ckf = nullptr, *ckh = nullptr; long long zeros_off = 0; uint32_t *bitmap = nullptr; double *cka = nullptr, *part = nullptr;
@@ -705,13 +709,18 @@ int32_t sparse_base_pass(snesimage_ctx *c, int sp_idx, int si, uint32_t n_cand) 
     return SNES_OK;
 }
 
-int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, const uint8_t *d_rgb5, uint32_t nc, double *d_errors, int err_stride, int err_offset) {
+// list0 >= 0: the list's duplicate colours are scored once (score_list), and this launch group starts at candidate list0 of the list
+int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, const uint8_t *d_rgb5, uint32_t nc, double *d_errors, int err_stride, int err_offset, int list0 = -1) {
     auto &sp = c->sp;
     const Geom &G = c->G;
     SparseParams P = sparse_params(c, lane);
     P.is_base = 0; P.ncand = (int)nc; P.k0 = (int)(lane * sp.cap);
+    if (list0 >= 0) { P.holder = sp.holder; P.list0 = list0; }
     snesimage_ctx::TimingRec tr{}; tr.n = nc;
     if (c->timing) { for (int i = 0; i < 6; i++) HIPCHK(hipEventCreate(&tr.ev[i])); if (c->timing == 1) HIPCHK(hipEventRecord(tr.ev[0], stream)); }
+    // (the marking rides on the launch that has a thread per candidate anyway: nothing is added in front of the scan)
+    if (list0 >= 0) hipLaunchKernelGGL(k_candidate_tables_mark, dim3((nc + 63) / 64), dim3(64), 0, stream, d_rgb5, (int)nc, c->d_eotf, sp.cand_tab + 8 * (size_t)P.k0, sp.holder, list0);
+    else
     hipLaunchKernelGGL(k_candidate_tables, dim3((nc + 63) / 64), dim3(64), 0, stream, d_rgb5, (int)nc, c->d_eotf, sp.cand_tab + 8 * (size_t)P.k0);
     if (c->dither) { // first pixel each candidate takes from B, then its own Floyd-Steinberg run from that 4-row group on
         if (c->perceptual) {
@@ -871,6 +880,21 @@ int32_t score_list(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t n, double *
         c->sp.base_sp = sp; c->sp.base_si = si;
     }
     if (c->dither) { hipLaunchKernelGGL(k_reset_best, dim3(1), dim3(64), 0, c->stream, c->d_bestrecs_all, (int)c->nlanes); c->best_valid = true; }
+    // Duplicate colours.  Every launch group marks its own candidates in front of its own scan, so with several groups on two
+    // lanes a group may scan before an earlier group has marked: both holders of a colour are then scored, and the copy below,
+    // which reads the table once every group is through, still leaves the lowest index's error in both places.  The lowest
+    // index itself is always scored: nothing below it can be in the table.  (Marking the whole list up front would cost the
+    // head a launch of its own for nothing the result needs.)
+    const bool dedup = sparse && !c->dither && c->sp.dedup && n >= c->sp.dedup_min;
+    if (dedup) {
+        if (!c->sp.holder) { HIPCHK(dmalloc(&c->sp.holder, sizeof(int) * kDedupColours)); c->sp.holder_dirty = true; }
+        if (c->sp.holder_dirty) { // first use, or a call that failed half-way: never on the path of a sound call, whose copy kernel leaves the table clear
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (auto &L : c->extra) HIPCHK(hipStreamSynchronize(L.stream));
+            HIPCHK(hipMemsetAsync(c->sp.holder, kNoHolder & 0xff, sizeof(int) * kDedupColours, c->stream));
+        }
+        c->sp.holder_dirty = true;
+    }
     if (nl > 1) {
         HIPCHK(hipEventRecord(c->ev_ready, c->stream)); // pack, tables, candidates are ready
         for (uint32_t l = 1; l < nl; l++) HIPCHK(hipStreamWaitEvent(c->extra[l - 1].stream, c->ev_ready, 0));
@@ -881,13 +905,18 @@ int32_t score_list(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t n, double *
         const uint32_t lane = i % nl;
         uint8_t *mo = d_maps_out ? d_maps_out + (size_t)c0 * c->npx : nullptr;
         const int eo = err_offset + (int)c0 * err_stride;
-        if (sparse) { CHECK(sparse_score_chunk(c, lane, lane == 0 ? c->stream : c->extra[lane - 1].stream, d_rgb5 + 3 * (size_t)c0, nc, d_errors, err_stride, eo)); continue; }
+        if (sparse) { CHECK(sparse_score_chunk(c, lane, lane == 0 ? c->stream : c->extra[lane - 1].stream, d_rgb5 + 3 * (size_t)c0, nc, d_errors, err_stride, eo, dedup ? (int)c0 : -1)); continue; }
         if (lane == 0) CHECK(score_chunk(c, d_rgb5 + 3 * (size_t)c0, nc, d_errors, err_stride, eo, sp, si, mo));
         else { LaneScope ls(c, &c->extra[lane - 1]); CHECK(score_chunk(c, d_rgb5 + 3 * (size_t)c0, nc, d_errors, err_stride, eo, sp, si, mo)); }
     }
     for (uint32_t l = 1; l < nl; l++) {
         HIPCHK(hipEventRecord(c->extra[l - 1].done, c->extra[l - 1].stream));
         HIPCHK(hipStreamWaitEvent(c->stream, c->extra[l - 1].done, 0));
+    }
+    if (dedup) { // behind the lanes' join: the holders' errors to the other candidates of their colours, and the table cleared for the next call
+        hipLaunchKernelGGL(k_dedup_copy, dim3(1), dim3(1024), 0, c->stream, d_rgb5, (int)n, c->sp.holder, d_errors, err_stride, err_offset);
+        HIPCHK(hipGetLastError());
+        c->sp.holder_dirty = false;
     }
     return SNES_OK;
 }
@@ -1072,6 +1101,8 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (const char *e = getenv("SNES_H2Q_MAX")) { int v = atoi(e); if (v >= 0) c->sp.h2q_max = (uint32_t)v; }
     if (const char *e = getenv("SNES_HGRID")) { int v = atoi(e); if (v >= 1) c->sp.hgrid = (uint32_t)v; }
     if (const char *e = getenv("SNES_SPARSE_MIN")) { int v = atoi(e); if (v >= 1) c->sp.min_n = (uint32_t)v; }
+    if (const char *e = getenv("SNES_DEDUP")) c->sp.dedup = atoi(e) != 0;
+    if (const char *e = getenv("SNES_DEDUP_MIN")) { int v = atoi(e); if (v >= 1) c->sp.dedup_min = (uint32_t)v; }
     Geom &G = c->G;
     G.W = (int)w; G.H = (int)h; G.nscales = 0;
     // ssimulacra2's scale loop tests the size BEFORE downscaling (`if width < 8 || height < 8 { break }` then
@@ -1175,7 +1206,7 @@ void snesimage_destroy(snesimage_ctx *c) {
     for (auto &L : c->extra) { if (L.stream) (void)hipStreamSynchronize(L.stream); dfree(L.d_mapsC4); dfree(L.d_mapsR4); dfree(L.d_work); dfree(L.d_cand_tab); dfree(L.d_cand_lab); dfree(L.d_part); dfree(L.d_maps); dfree(L.d_mapsT); if (L.done) (void)hipEventDestroy(L.done); if (L.stream) (void)hipStreamDestroy(L.stream); }
     if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
     { auto &q = c->sp; for (int i = 0; i < 8; i++) if (q.h0_stream[i]) { (void)hipStreamSynchronize(q.h0_stream[i]); (void)hipStreamDestroy(q.h0_stream[i]); (void)hipEventDestroy(q.ev_scan[i]); (void)hipEventDestroy(q.ev_h0[i]); (void)hipEventDestroy(q.ev_hn[i]); (void)hipEventDestroy(q.ev_vn[i]); (void)hipEventDestroy(q.ev_v0[i]); }
-      if (q.base_stream) { (void)hipStreamSynchronize(q.base_stream); (void)hipStreamDestroy(q.base_stream); (void)hipEventDestroy(q.ev_base_in); (void)hipEventDestroy(q.ev_base_h); (void)hipEventDestroy(q.ev_base_narrow); (void)hipEventDestroy(q.ev_base_done); } dfree(q.store); dfree(q.cand_tab); dfree(q.ckf); dfree(q.cka); dfree(q.part); dfree(q.meta); dfree(q.items); dfree(q.item_count); dfree(q.plist); dfree(q.order); dfree(q.first); dfree(q.cand_lab); dfree(q.bitmap); dfree(q.ckh);
+      if (q.base_stream) { (void)hipStreamSynchronize(q.base_stream); (void)hipStreamDestroy(q.base_stream); (void)hipEventDestroy(q.ev_base_in); (void)hipEventDestroy(q.ev_base_h); (void)hipEventDestroy(q.ev_base_narrow); (void)hipEventDestroy(q.ev_base_done); } dfree(q.store); dfree(q.cand_tab); dfree(q.ckf); dfree(q.cka); dfree(q.part); dfree(q.meta); dfree(q.items); dfree(q.item_count); dfree(q.plist); dfree(q.order); dfree(q.first); dfree(q.holder); dfree(q.cand_lab); dfree(q.bitmap); dfree(q.ckh);
       dfree(q.dmaps); dfree(q.dmapsC4); dfree(q.bmap); dfree(q.bmapC4); dfree(q.bcand); dfree(q.dpack); dfree(q.ckd);
       dfree(q.rec_lab); dfree(q.ahead.blab); dfree(q.ahead.rec_lab); dfree(q.ahead.bmap); dfree(q.ahead.bmapC4); dfree(q.ahead.bcand); dfree(q.ahead.dpack); dfree(q.ahead.ckd); dfree(q.ahead.btab); dfree(q.ahead.ok); if (q.ahead.ev) (void)hipEventDestroy(q.ahead.ev); }
     kmeans_free(c->km);

@@ -86,6 +86,52 @@ __device__ __forceinline__ void candidate_tables_body(const uint8_t *__restrict_
     o[0] = r; o[1] = g; o[2] = b; o[3] = X; o[4] = Y; o[5] = B; o[6] = __uint_as_float(rgb8); o[7] = 0.0f;
 }
 
+// ---- duplicate colours of a list ------------------------------------------------------------------------
+// Everything a candidate contributes to its image derives from the 8-bit expansion of its colour, so two candidates of a
+// list with the same expansion on the same slot are the same image with the same error, bit for bit.  holder[colour] names
+// the lowest list index that carries the colour: that candidate is scored, the others win nothing in the scan (they cost
+// what a candidate without pixels costs) and take its error when the list is through.  The table is keyed by the 15-bit
+// colour; an expansion that no 5-bit triple below 32 produces (raw bytes >= 32 wrap, color.hpp) has no key and is scored
+// on its own.  Entries are kNoHolder between calls: whoever marks them resets them (dedup_copy_body).
+constexpr int kDedupColours = 32768;
+constexpr int kNoHolder = 0x7f7f7f7f; // (what a byte-wise memset can write)
+__device__ __forceinline__ int dedup_key(uint32_t rgb8) {
+    const uint32_t r = (rgb8 >> 3) & 31u, g = (rgb8 >> 11) & 31u, b = (rgb8 >> 19) & 31u;
+    return rgb5_to_rgb8(r, g, b) == (rgb8 & 0x00ffffffu) ? (int)(r | (g << 5) | (b << 10)) : -1;
+}
+// candidate_tables_body plus the marking: candidate k of the launch is candidate list0 + k of the list
+__device__ __forceinline__ void candidate_tables_mark_body(const uint8_t *__restrict__ rgb5, int n, const float *__restrict__ eotf, float *__restrict__ cand_tab, int *__restrict__ holder, int list0) {
+    candidate_tables_body(rgb5, n, eotf, cand_tab);
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int key = dedup_key(rgb5_to_rgb8(rgb5[3 * k], rgb5[3 * k + 1], rgb5[3 * k + 2]));
+    if (key >= 0) atomicMin(&holder[key], list0 + k);
+}
+// does candidate `idx` of the list stand behind an earlier holder of its colour?  (The table as it stands when the scan runs:
+// a holder marked later by another launch group is missed here, the candidate is then scored like its holder, and
+// dedup_copy_body, which reads the final table, writes the same bits over its error.)
+__device__ __forceinline__ bool dedup_is_duplicate(const int *__restrict__ holder, uint32_t rgb8, int idx) {
+    const int key = dedup_key(rgb8);
+    return key >= 0 && holder[key] != idx;
+}
+// One block behind the list's last final score: every candidate that is not the holder of its colour takes the holder's
+// error; then, behind a barrier, the entries the list touched are reset.  (A holder's own error is never written here, so
+// the reads of the first phase race with nothing.)  One block whatever the list holds, because the reset must wait for every copy:
+// two strided passes of n / 1,024 iterations each, a few microseconds at the 65,535 candidates a launch group can take.
+__device__ __forceinline__ void dedup_copy_body(const uint8_t *__restrict__ rgb5, int n, int *__restrict__ holder, double *__restrict__ errors, int err_stride, int err_offset) {
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const int key = dedup_key(rgb5_to_rgb8(rgb5[3 * j], rgb5[3 * j + 1], rgb5[3 * j + 2]));
+        if (key < 0) continue;
+        const int h = holder[key];
+        if (h != j && (unsigned)h < (unsigned)n) errors[(size_t)err_offset + (size_t)j * err_stride] = errors[(size_t)err_offset + (size_t)h * err_stride];
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const int key = dedup_key(rgb5_to_rgb8(rgb5[3 * j], rgb5[3 * j + 1], rgb5[3 * j + 2]));
+        if (key >= 0) holder[key] = kNoHolder;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Remap preparation (no dither): nearest-entry argmin of lib.rs:762-795 per pixel.
 //   mode 0: argmin over the whole subpalette -> palette_map (this IS optimize() without dither), thr = 0
@@ -784,6 +830,8 @@ __device__ __forceinline__ void final_score_wave_body(const double *__restrict__
 
 // ---- kernel entry points of the bodies above (kernels_batch.hpp holds the many-images flavours) ----
 __global__ void k_candidate_tables(const uint8_t *__restrict__ rgb5, int n, const float *__restrict__ eotf, float *__restrict__ cand_tab) { candidate_tables_body(rgb5, n, eotf, cand_tab); }
+__global__ void k_candidate_tables_mark(const uint8_t *__restrict__ rgb5, int n, const float *__restrict__ eotf, float *__restrict__ cand_tab, int *__restrict__ holder, int list0) { candidate_tables_mark_body(rgb5, n, eotf, cand_tab, holder, list0); }
+__global__ __launch_bounds__(1024) void k_dedup_copy(const uint8_t *__restrict__ rgb5, int n, int *__restrict__ holder, double *__restrict__ errors, int err_stride, int err_offset) { dedup_copy_body(rgb5, n, holder, errors, err_stride, err_offset); }
 __global__ __launch_bounds__(256) void k_prep(PrepParams P) { prep_body(P); }
 __global__ void k_final_score(const double *__restrict__ part, int ncand, Geom G, double *__restrict__ errors, int err_stride, int err_offset, int *__restrict__ zero = nullptr, int nzero = 0) {
     final_score_body(part, ncand, G, errors, err_stride, err_offset, zero, nzero);

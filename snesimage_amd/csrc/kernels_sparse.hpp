@@ -77,6 +77,7 @@ struct SparseParams {
     int s_first; // the general H and V bodies skip scales below this one (the wide scales run the bodies of kernels_sparse2.hpp)
     int *first;       // per candidate: first changed group of scale 0 (H/4 if none), written by the scan for k_sparse_order
     const int *order; // k_sparse_v: candidates of the launch, longest column sweeps first (k_sparse_order); nullptr = as listed
+    const int *holder; int list0; // duplicate colours (kernels.hpp, dedup_*): the table, or nullptr; list index of the launch's first candidate
 };
 
 __device__ __forceinline__ uint32_t sparse_ci(uint32_t lo, uint32_t thr, uint32_t crgb, uint32_t ncol) {
@@ -209,7 +210,8 @@ __device__ __forceinline__ void sparse_scan_lab_body(const SparseParams &P) {
     const bool live = wi < P.ncand;
     const int k = P.k0 + (live ? wi : 0);
     unsigned long long mask = 0ull; int xmin = G.W, won = 0;
-    if (live) {
+    const bool dup = P.holder && live && dedup_is_duplicate(P.holder, __float_as_uint(P.cand_tab[8 * (size_t)k + 6]), P.list0 + wi); // as in sparse_scan_body
+    if (live && !dup) {
         Lab cl; cl.l = P.cand_lab[3 * (size_t)k]; cl.a = P.cand_lab[3 * (size_t)k + 1]; cl.b = P.cand_lab[3 * (size_t)k + 2];
         uint32_t *bm = P.bitmap + (size_t)k * (G.W * G.H / 32);
         const int n = *P.plist_count;
@@ -297,6 +299,7 @@ __device__ __forceinline__ void sparse_scan_body(const SparseParams &P) {
     if (P.is_base) { const int ng0 = G.sh[0] >> 2; mask = ng0 >= 64 ? ~0ull : ((1ull << ng0) - 1ull); xmin = 0; } // every group of the image (64 at 256 rows)
     else {
         const uint32_t crgb = __float_as_uint(P.cand_tab[8 * (size_t)k + 6]);
+        const bool dup = P.holder && live && dedup_is_duplicate(P.holder, crgb, P.list0 + wi); // its colour's holder is scored: this one wins nothing
         const int n = *P.plist_count;
         for (int t0 = 0; t0 < n; t0 += kScanTile) {
             const int nt = min(kScanTile, n - t0);
@@ -307,7 +310,7 @@ __device__ __forceinline__ void sparse_scan_body(const SparseParams &P) {
                 s_px[i] = (unsigned short)((e.x & (unsigned)(G.W - 1)) | ((e.x / (unsigned)G.W) >> 2) << 8);
             }
             __syncthreads();
-            if (live) {
+            if (live && !dup) {
                 for (int i = part * 64 + lane; i < nt; i += 64 * WPC) {
                     if (red_mean_key(crgb, s_rgb[i]) < s_thr[i]) {
                         const int px = s_px[i];
