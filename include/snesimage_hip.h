@@ -28,6 +28,35 @@ typedef struct snesimage_ctx snesimage_ctx;
 
 /* config.rs:20-30 (--dither, --perceptual-palettes, --nes) */
 enum { SNES_DITHER = 1, SNES_PERCEPTUAL = 2, SNES_NES = 4 };
+/* NOT a reference flag: the shared backdrop colour.  On the SNES a background tile reads index 0 of its subpalette as
+ * transparent, and where nothing lies behind the layer the PPU draws the backdrop colour, CGRAM word 0: a picture on the
+ * bottom layer has sub_size + 1 colours in every tile, the tile's own and one colour B that all tiles share (the reference
+ * writes 0 into slot 0 of every palette row, lib.rs:582-594).  A *backdrop context* (sub_count, sub_size, flags | SNES_BACKDROP)
+ * behaves exactly as the EXPANDED context (sub_count, sub_size + 1, flags) whose entries (p, sub_size), p < sub_count, hold B
+ * and only ever change together:
+ *   - every pixel chooses among its tile's sub_size regular entries and B; B is entry sub_size, so a regular entry wins a
+ *     tie (strict <, lowest index, lib.rs:788-791); --dither diffuses against B like against any entry;
+ *   - palette_map holds 0 .. sub_size, sub_size meaning backdrop; as_rgba paints such a pixel with B; transparent source
+ *     pixels stay (0,0,0,0) and error() treats them as the reference does (lib.rs:527-536);
+ *   - get/set_palette_rgb5 and get_palette_u16 keep their size, sub_count*sub_size regular entries; B has its own accessors;
+ *   - B starts, in snesimage_create, as the mean of the opaque pixels — per channel (sum + n/2) / n in integers, then >> 3;
+ *     (0,0,0) without an opaque pixel — snapped as new_nes_only does (lib.rs:640-660) with SNES_NES.  The initialisers are the
+ *     reference's on the regular entries (k-means with k = sub_size) and never move B; their closing optimize() sees it;
+ *   - sub_size <= 15 and sub_count*(sub_size + 1) <= 253, else SNES_ERR_ARG;
+ *   - THE BACKDROP SLOT is addressed as palette == sub_count, index == 0 in snesimage_score_candidates(_device),
+ *     snesimage_remap_candidates_device, snesimage_step(_async), snesimage_step_begin/_commit: a candidate replaces B in
+ *     every subpalette at once; the method rules (64 random / the 32 values of one channel of B / the 56 NES colours) and the
+ *     acceptance rule (lib.rs:216-219) are those of any entry.  Regular slots are (p < sub_count, i < sub_size); on a context
+ *     without the flag palette == sub_count stays SNES_ERR_ARG;
+ *   - snesimage_run_slots follows snesimage_schedule_next_backdrop: a window ends in front of a backdrop call, which is
+ *     stepped on its own; for every `window` the result equals call by call, bit for bit; log[j].rgb5 of such a call is B;
+ *   - snesimage_reassign_tiles, snesimage_score_tile_moves, snesimage_tile_step and snesimage_tile_sweep work as on the
+ *     expanded context (B counts as an entry of every subpalette);
+ *   - snesimage_as_json: slot 0 of every palette row holds B as a BGR555 word; `tiles` holds 0 for a transparent or a backdrop
+ *     pixel, else map + 1;
+ *   - snesimage_batch_create, snesimage_group_create, snesimage_shared_create, snesimage_slots_begin and _commit refuse a
+ *     backdrop context with SNES_ERR_UNSUPPORTED (their hosts do not carry the backdrop schedule). */
+enum { SNES_BACKDROP = 8 };
 /* optimizer methods: lib.rs:191 (random), :286 (channel), :242 (nes) */
 enum { SNES_METHOD_RANDOM = 0, SNES_METHOD_CHANNEL = 1, SNES_METHOD_NES = 2 };
 
@@ -287,6 +316,10 @@ int32_t snesimage_set_tile_palettes(snesimage_ctx *ctx, const uint8_t *in /*1024
 int32_t snesimage_get_palette_rgb5(snesimage_ctx *ctx, uint8_t *out /*count*size*3*/);
 int32_t snesimage_set_palette_rgb5(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_get_palette_u16(snesimage_ctx *ctx, uint16_t *out /*count*size; lib.rs:679-681*/);
+/* The backdrop colour B of a backdrop context (SNES_ERR_ARG on any other), raw 5-bit r,g,b.  Setting it invalidates
+ * palette_map as snesimage_set_palette_rgb5 does: call snesimage_optimize() before reading the map or the error. */
+int32_t snesimage_get_backdrop_rgb5(snesimage_ctx *ctx, uint8_t *out /*3*/);
+int32_t snesimage_set_backdrop_rgb5(snesimage_ctx *ctx, const uint8_t *in /*3*/);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);
@@ -301,6 +334,13 @@ void snesimage_random_candidates(uint64_t seed, uint64_t step_id, uint32_t n, ui
  * advances (palette, index, channel, step). */
 void snesimage_schedule_next(uint32_t sub_count, uint32_t sub_size, int32_t nes, uint32_t *palette,
                              uint32_t *index, uint32_t *channel, uint32_t *step, uint32_t *method);
+
+/* The scheduler of a backdrop context: the reference's with one more slot per sweep — behind (sub_count - 1, sub_size - 1)
+ * comes the backdrop slot (sub_count, 0), then the wrap to the next step; the backdrop slot gets three channel calls in a
+ * channel sweep like every entry.  Equivalently snesimage_schedule_next for geometry (1, sub_count*sub_size + 1) with linear
+ * index L: L < sub_count*sub_size is (L / sub_size, L % sub_size), L == sub_count*sub_size the backdrop slot. */
+void snesimage_schedule_next_backdrop(uint32_t sub_count, uint32_t sub_size, int32_t nes, uint32_t *palette,
+                                      uint32_t *index, uint32_t *channel, uint32_t *step, uint32_t *method);
 
 /* Device-side evaluation of the deterministic math used by the kernels, for bit-parity tests:
  * op 0 sin, 1 cos, 2 exp(x<=0), 3 cbrt, 4 atan2(y,x), 5 CIEDE2000(lab x[3i..], lab y[3i..]),

@@ -102,12 +102,15 @@ SIGNATURES = [
     ("snesimage_get_palette_rgb5", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_palette_rgb5", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_get_palette_u16", C.c_int32, [C.c_void_p, _u16p]),
+    ("snesimage_get_backdrop_rgb5", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_set_backdrop_rgb5", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_get_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_as_rgba", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_as_json", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     ("snesimage_random_candidates", None, [C.c_uint64, C.c_uint64, C.c_uint32, _u8p]),
     ("snesimage_schedule_next", None, [C.c_uint32, C.c_uint32, C.c_int32, _u32p, _u32p, _u32p, _u32p, _u32p]),
+    ("snesimage_schedule_next_backdrop", None, [C.c_uint32, C.c_uint32, C.c_int32, _u32p, _u32p, _u32p, _u32p, _u32p]),
     ("snesimage_debug_math", C.c_int32, [C.c_int32, C.c_int32, _f32p, _f32p, C.c_uint32, _f32p]),
     ("snesimage_debug_fail_alloc", None, [C.c_int32]),
     ("snesimage_debug_poison_alloc", None, [C.c_int32]),

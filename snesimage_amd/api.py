@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _ffi
 
-DITHER, PERCEPTUAL, NES = 1, 2, 4
+DITHER, PERCEPTUAL, NES, BACKDROP = 1, 2, 4, 8
 METHOD_RANDOM, METHOD_CHANNEL, METHOD_NES = 0, 1, 2
 TILE_LOG_DTYPE = np.dtype([("error", np.float64), ("sub", np.int32), ("changed", np.uint8)])  # one record of a tile sweep's log
 
@@ -32,29 +32,36 @@ def random_candidates(seed, step_id, n):
     return out
 
 
-def schedule(sub_count, sub_size, n_calls, nes=False):
-    """Replay the slot scheduler of lib.rs:881-933: [(method, palette, index, channel, step)]."""
+def schedule(sub_count, sub_size, n_calls, nes=False, backdrop=False):
+    """Replay the slot scheduler of lib.rs:881-933: [(method, palette, index, channel, step)].
+    backdrop: the schedule of a backdrop context — every sweep ends with the backdrop slot (sub_count, 0)."""
     L = _ffi.load()
+    nxt = L.snesimage_schedule_next_backdrop if backdrop else L.snesimage_schedule_next
     p, i, ch, st, m = (C.c_uint32(0) for _ in range(5))
     out = []
     for _ in range(n_calls):
         cur = (p.value, i.value, ch.value, st.value)
-        L.snesimage_schedule_next(sub_count, sub_size, int(nes), C.byref(p), C.byref(i), C.byref(ch), C.byref(st),
+        nxt(sub_count, sub_size, int(nes), C.byref(p), C.byref(i), C.byref(ch), C.byref(st),
                                   C.byref(m))
         out.append((m.value,) + cur)
     return out
 
 
 class OptimizedImage:
-    """`OptimizedImage::new(source, palette_count, palette_size, dither, perceptual_palettes, nes)`."""
+    """`OptimizedImage::new(source, palette_count, palette_size, dither, perceptual_palettes, nes)`.
 
-    def __init__(self, rgba, sub_count, sub_size, dither=False, perceptual=False, nes=False, device=0):
+    backdrop=True (not in the reference): every tile additionally draws from one shared colour, the SNES backdrop
+    (`.backdrop`).  `palette_map` then holds 0 .. sub_size, sub_size meaning backdrop, and the backdrop slot is addressed
+    as (sub_count, 0) in `score_candidates`, `step` and their kin; `palette` keeps the sub_count * sub_size regular entries."""
+
+    def __init__(self, rgba, sub_count, sub_size, dither=False, perceptual=False, nes=False, device=0, backdrop=False):
         rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
         if rgba.ndim != 3 or rgba.shape[2] != 4:
             raise ValueError("rgba must be an (H, W, 4) uint8 array")
         self.h, self.w = int(rgba.shape[0]), int(rgba.shape[1])
         self.sub_count, self.sub_size = int(sub_count), int(sub_size)
-        self.flags = (DITHER if dither else 0) | (PERCEPTUAL if perceptual else 0) | (NES if nes else 0)
+        self.flags = (DITHER if dither else 0) | (PERCEPTUAL if perceptual else 0) | (NES if nes else 0) | (BACKDROP if backdrop else 0)
+        self.has_backdrop = bool(backdrop)
         self._L = _ffi.load()
         ctx = C.c_void_p()
         rc = self._L.snesimage_create(_p(rgba, _ffi._u8p), self.w, self.h, self.sub_count, self.sub_size, self.flags,
@@ -259,6 +266,18 @@ class OptimizedImage:
         out = np.zeros(self.sub_count * self.sub_size, np.uint16)
         self._chk(self._L.snesimage_get_palette_u16(self._c, _p(out, _ffi._u16p)))
         return out
+
+    @property
+    def backdrop(self):
+        """The backdrop colour B, raw 5-bit (r, g, b); setting it invalidates palette_map as setting `palette` does."""
+        out = np.zeros(3, np.uint8)
+        self._chk(self._L.snesimage_get_backdrop_rgb5(self._c, _p(out, _ffi._u8p)))
+        return out
+
+    @backdrop.setter
+    def backdrop(self, v):
+        v = np.ascontiguousarray(v, np.uint8).reshape(3)
+        self._chk(self._L.snesimage_set_backdrop_rgb5(self._c, _p(v, _ffi._u8p)))
 
     @property
     def palette_map(self):

@@ -78,6 +78,7 @@ int32_t enqueue_batched_scoring(hipStream_t st, const snes::BatchArgs *A, uint32
     hipStream_t bs = side && side->stream ? side->stream : st;
     const bool split = bs != st;
     const bool dith = c0->dither;
+    const bool sub16 = c0->sub_size == 16; // (15 + the backdrop)
     const bool sub15 = c0->sub_size == 15; // the 15-colour subpalettes of the SNES 4bpp modes get a fully unrolled entry search
     const bool whole = split && side->whole;
     hipStream_t ps = whole ? bs : st;              // stream of the pack, the contested list and B's downscale
@@ -88,6 +89,7 @@ int32_t enqueue_batched_scoring(hipStream_t st, const snes::BatchArgs *A, uint32
         hipLaunchKernelGGL(kb_dither_prep, dim3(1, 1, K), dim3(64), 0, ps, A, bdead);
         if (c0->perceptual) hipLaunchKernelGGL(kb_dither_base_lab, dim3(1, 1, K), dim3(512), 0, ps, A, bdead);
         else if (sub15) hipLaunchKernelGGL(kb_dither_base<15>, dim3(1, 1, K), dim3(512), 0, ps, A, bdead);
+        else if (sub16) hipLaunchKernelGGL(kb_dither_base<16>, dim3(1, 1, K), dim3(512), 0, ps, A, bdead);
         else hipLaunchKernelGGL(kb_dither_base<0>, dim3(1, 1, K), dim3(512), 0, ps, A, bdead);
     }
     hipLaunchKernelGGL(kb_build_plist, dim3(npx_blocks, 1, K), dim3(256), 0, ps, A, bdead);
@@ -122,10 +124,13 @@ int32_t enqueue_batched_scoring(hipStream_t st, const snes::BatchArgs *A, uint32
         if (c0->sp.lpt) hipLaunchKernelGGL(kb_sparse_order, dim3(1, 1, K), dim3(1024), 0, st, A, dead);
         const bool quad_fs = c0->dither4 && (size_t)n * K <= c0->dither4_max;
         if (quad_fs && sub15) hipLaunchKernelGGL(kb_dither_run4<15>, dim3(n, 1, K), dim3(512), 0, st, A, dead);
+        else if (quad_fs && sub16) hipLaunchKernelGGL(kb_dither_run4<16>, dim3(n, 1, K), dim3(512), 0, st, A, dead);
         else if (quad_fs) hipLaunchKernelGGL(kb_dither_run4<0>, dim3(n, 1, K), dim3(512), 0, st, A, dead);
         else if (c0->ditherw && sub15) hipLaunchKernelGGL(kb_dither_runw<15>, dim3((n + 3) / 4, 1, K), dim3(256), 0, st, A, dead);
+        else if (c0->ditherw && sub16) hipLaunchKernelGGL(kb_dither_runw<16>, dim3((n + 3) / 4, 1, K), dim3(256), 0, st, A, dead);
         else if (c0->ditherw && c0->sub_size > 1) hipLaunchKernelGGL(kb_dither_runw<0>, dim3((n + 3) / 4, 1, K), dim3(256), 0, st, A, dead);
         else if (sub15) hipLaunchKernelGGL(kb_dither_run<15>, dim3(n, 1, K), dim3(128), 0, st, A, dead);
+        else if (sub16) hipLaunchKernelGGL(kb_dither_run<16>, dim3(n, 1, K), dim3(128), 0, st, A, dead);
         else hipLaunchKernelGGL(kb_dither_run<0>, dim3(n, 1, K), dim3(128), 0, st, A, dead);
         hipLaunchKernelGGL(kb_dither_diff, dim3((n + 3) / 4, 1, K), dim3(1024), 0, st, A, dead);
     } else if ((size_t)n * K <= c0->sp.scan4_max) hipLaunchKernelGGL(kb_sparse_scan4, dim3((n + 3) / 4, 1, K), dim3(1024), 0, st, A, dead);
@@ -197,6 +202,7 @@ int32_t snesimage_batch_create(snesimage_ctx **ctxs, uint32_t n, snesimage_batch
         snesimage_ctx *c = ctxs[i];
         if (!c) return fail(SNES_ERR_ARG, "null context in batch");
         if (c->owner) return fail(SNES_ERR_STATE, "context already belongs to a batch");
+        if (c->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
         if (c->device != c0->device || c->W != c0->W || c->H != c0->H || c->sub_count != c0->sub_count || c->sub_size != c0->sub_size || c->chunk != c0->chunk)
             return fail(SNES_ERR_ARG, "contexts of a batch must share device, image size, palette geometry and chunk");
         if (c->perceptual != c0->perceptual) return fail(SNES_ERR_ARG, "contexts of a batch must share their flags");

@@ -111,6 +111,11 @@ struct snesimage_ctx {
     uint32_t W = 0, H = 0, sub_count = 0, sub_size = 0, flags = 0;
     int ncol = 0;
     bool dither = false, perceptual = false, nes = false;
+    // SNES_BACKDROP: the context is kept as the expanded context (sub_count, user_size + 1) whose last column — entry user_size of
+    // every subpalette, the *tied* entries — holds the backdrop colour B; sub_size and ncol are the expanded ones throughout.
+    // Regular slots run as on that context; the tied slot (palette == sub_count, index == 0 at the interface) takes the dense
+    // path with pack mode 3 and writes its winner to all tied entries.  tied_call: such a call is being scored.
+    bool backdrop = false, tied_call = false; uint32_t user_size = 0;
     // Floyd-Steinberg with a quad of lanes per row (k_dither4; RGB distance): a third of the step's latency for ~20 % more
     // instructions and half the runs per CU — B's own run always, the candidates' while they are few (SNES_DITHER4=0: never;
     // SNES_DITHER4_MAX: most runs per launch that still take it)
@@ -350,7 +355,7 @@ int32_t ensure_source(snesimage_ctx *c) {
 }
 
 int32_t run_prep(snesimage_ctx *c, int mode, int sp, int si) {
-    if (c->pack_valid && c->pack_mode == mode && (mode != 2 || (c->pack_sp == sp && c->pack_si == si))) return SNES_OK;
+    if (c->pack_valid && c->pack_mode == mode && ((mode != 2 && mode != 3) || (c->pack_sp == sp && c->pack_si == si))) return SNES_OK;
     CHECK(ensure_tables(c));
     if (c->perceptual) CHECK(ensure_source(c));
     PrepParams P{};
@@ -371,7 +376,7 @@ int32_t run_prep(snesimage_ctx *c, int mode, int sp, int si) {
 // Without dither the pack carries, per pixel, the best non-slot entry and the key the candidate must beat
 // (mode 2).  With dither every candidate gets its own map from k_dither; the pack is then only consulted for
 // the transparent-pixel marker, which any mode provides (mode 1 is the cheapest).
-int32_t prep_for_slot(snesimage_ctx *c, int sp, int si) { return c->dither ? run_prep(c, 1, -1, -1) : run_prep(c, 2, sp, si); }
+int32_t prep_for_slot(snesimage_ctx *c, int sp, int si) { return c->dither ? run_prep(c, 1, -1, -1) : (c->tied_call ? run_prep(c, 3, -1, si) : run_prep(c, 2, sp, si)); } // (tied slot: entry si of every subpalette)
 
 // The scoring stages behind the candidates' pixels (downscale, H and V pass per scale, final score) on the planes, pack and
 // per-candidate maps of `V`: the context's own for score_chunk, the tile workspace's for tile_host.inc.
@@ -447,8 +452,10 @@ void launch_dither(snesimage_ctx *c, const DitherParams &Dp, uint32_t nblocks) {
     if (c->perceptual && c->dither4 && nblocks <= c->dither4_max) hipLaunchKernelGGL((k_dither4_lab<0>), dim3(nblocks), dim3(512), 0, c->stream, Dp); // (optimize() of the committed palette: one run)
     else if (c->perceptual) hipLaunchKernelGGL((k_dither<true, 0>), dim3(nblocks), dim3(128), 0, c->stream, Dp);
     else if (c->dither4 && nblocks <= c->dither4_max && c->sub_size == 15) hipLaunchKernelGGL((k_dither4<15, 0>), dim3(nblocks), dim3(512), 0, c->stream, Dp); // a quad of lanes per row: few runs
+    else if (c->dither4 && nblocks <= c->dither4_max && c->sub_size == 16) hipLaunchKernelGGL((k_dither4<16, 0>), dim3(nblocks), dim3(512), 0, c->stream, Dp); // (15 + the backdrop)
     else if (c->dither4 && nblocks <= c->dither4_max) hipLaunchKernelGGL((k_dither4<0, 0>), dim3(nblocks), dim3(512), 0, c->stream, Dp);
     else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither<false, 15>), dim3(nblocks), dim3(128), 0, c->stream, Dp);
+    else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither<false, 16>), dim3(nblocks), dim3(128), 0, c->stream, Dp);
     else hipLaunchKernelGGL((k_dither<false, 0>), dim3(nblocks), dim3(128), 0, c->stream, Dp);
 }
 
@@ -456,7 +463,7 @@ void launch_dither(snesimage_ctx *c, const DitherParams &Dp, uint32_t nblocks) {
 // slot_ci: colour index of the slot being replaced (dither path), or -1.
 int32_t score_chunk(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t nc, double *d_errors, int err_stride, int err_offset, int sp, int si, uint8_t *d_maps_out) {
     const bool use_maps = c->dither;
-    const uint32_t slot_ci = (sp >= 0) ? (uint32_t)(sp * (int)c->sub_size + si) : 0xffffffffu;
+    const uint32_t slot_ci = c->tied_call ? (kTiedSlot | (c->sub_size << 8) | (uint32_t)si) : (sp >= 0) ? (uint32_t)(sp * (int)c->sub_size + si) : 0xffffffffu;
     snesimage_ctx::TimingRec tr{}; tr.n = nc;
     if (c->timing) { for (int i = 0; i < 6; i++) HIPCHK(hipEventCreate(&tr.ev[i])); if (c->timing == 1) HIPCHK(hipEventRecord(tr.ev[0], c->stream)); }
     hipLaunchKernelGGL(k_candidate_tables, dim3((nc + 63) / 64), dim3(64), 0, c->stream, d_rgb5, (int)nc, c->d_eotf, c->d_cand_tab);
@@ -644,8 +651,10 @@ int32_t sparse_base_pass(snesimage_ctx *c, int sp_idx, int si, uint32_t n_cand) 
                 if (c->dither4) hipLaunchKernelGGL((k_dither4_lab<1>), dim3(1), dim3(512), 0, c->stream, Dp); else hipLaunchKernelGGL((k_dither<true, 0, 1>), dim3(1), dim3(128), 0, c->stream, Dp);
             } else
             if (c->dither4 && c->sub_size == 15) hipLaunchKernelGGL((k_dither4<15, 1>), dim3(1), dim3(512), 0, c->stream, Dp);
+            else if (c->dither4 && c->sub_size == 16) hipLaunchKernelGGL((k_dither4<16, 1>), dim3(1), dim3(512), 0, c->stream, Dp);
             else if (c->dither4) hipLaunchKernelGGL((k_dither4<0, 1>), dim3(1), dim3(512), 0, c->stream, Dp);
             else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither<false, 15, 1>), dim3(1), dim3(128), 0, c->stream, Dp);
+            else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither<false, 16, 1>), dim3(1), dim3(128), 0, c->stream, Dp);
             else hipLaunchKernelGGL((k_dither<false, 0, 1>), dim3(1), dim3(128), 0, c->stream, Dp);
             win_pack = sp.dpack;
         }
@@ -697,8 +706,10 @@ int32_t sparse_base_pass(snesimage_ctx *c, int sp_idx, int si, uint32_t n_cand) 
                 if (c->dither4) hipLaunchKernelGGL((k_dither4_lab<1>), dim3(1), dim3(512), 0, bs, Dn); else hipLaunchKernelGGL((k_dither<true, 0, 1>), dim3(1), dim3(128), 0, bs, Dn);
             } else
             if (c->dither4 && c->sub_size == 15) hipLaunchKernelGGL((k_dither4<15, 1>), dim3(1), dim3(512), 0, bs, Dn);
+            else if (c->dither4 && c->sub_size == 16) hipLaunchKernelGGL((k_dither4<16, 1>), dim3(1), dim3(512), 0, bs, Dn);
             else if (c->dither4) hipLaunchKernelGGL((k_dither4<0, 1>), dim3(1), dim3(512), 0, bs, Dn);
             else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither<false, 15, 1>), dim3(1), dim3(128), 0, bs, Dn);
+            else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither<false, 16, 1>), dim3(1), dim3(128), 0, bs, Dn);
             else hipLaunchKernelGGL((k_dither<false, 0, 1>), dim3(1), dim3(128), 0, bs, Dn);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(ah.ev, bs));
@@ -741,10 +752,13 @@ int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, 
             if (c->dither4 && nc <= c->dither4_max) hipLaunchKernelGGL((k_dither4_lab<2>), dim3(nc), dim3(512), 0, stream, Dp); else hipLaunchKernelGGL((k_dither<true, 0, 2>), dim3(nc), dim3(128), 0, stream, Dp);
         } else
         if (c->dither4 && nc <= c->dither4_max && c->sub_size == 15) hipLaunchKernelGGL((k_dither4<15, 2>), dim3(nc), dim3(512), 0, stream, Dp);
+        else if (c->dither4 && nc <= c->dither4_max && c->sub_size == 16) hipLaunchKernelGGL((k_dither4<16, 2>), dim3(nc), dim3(512), 0, stream, Dp);
         else if (c->dither4 && nc <= c->dither4_max) hipLaunchKernelGGL((k_dither4<0, 2>), dim3(nc), dim3(512), 0, stream, Dp);
         else if (c->ditherw && c->sub_size == 15) hipLaunchKernelGGL((k_ditherw<15>), dim3((nc + 3) / 4), dim3(256), 0, stream, Dp, (int)nc);
+        else if (c->ditherw && c->sub_size == 16) hipLaunchKernelGGL((k_ditherw<16>), dim3((nc + 3) / 4), dim3(256), 0, stream, Dp, (int)nc);
         else if (c->ditherw && c->sub_size > 1) hipLaunchKernelGGL((k_ditherw<0>), dim3((nc + 3) / 4), dim3(256), 0, stream, Dp, (int)nc);
         else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither<false, 15, 2>), dim3(nc), dim3(128), 0, stream, Dp);
+        else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither<false, 16, 2>), dim3(nc), dim3(128), 0, stream, Dp);
         else hipLaunchKernelGGL((k_dither<false, 0, 2>), dim3(nc), dim3(128), 0, stream, Dp);
         hipLaunchKernelGGL(k_dither_diff, dim3((nc + 3) / 4), dim3(1024), 0, stream, P); // changed groups = where the maps differ
     } else if (c->perceptual) {
@@ -865,9 +879,10 @@ int32_t score_list(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t n, double *
     uint32_t chunk = (c->dither || c->perceptual) ? (n + c->nlanes - 1) / c->nlanes : n;
     if (chunk < 64) chunk = 64;
     if (chunk > c->chunk) chunk = c->chunk;
+    if (c->tied_call && chunk > 1024) chunk = 1024; // (the dense workspace is 4.5 MB per candidate and lane)
     // (--dither with one-entry subpalettes stays on the dense path: B then has no other entry to stand in for the slot's, so
     // the slot's index appears in B's map as well and a map comparison cannot tell the candidate's pixels from B's)
-    const bool sparse = c->sp.enabled && !d_maps_out && sp >= 0 && n >= c->sp.min_n && c->pack_mode == (c->dither ? 1 : 2) && !(c->dither && c->sub_size == 1);
+    const bool sparse = c->sp.enabled && !c->tied_call && !d_maps_out && sp >= 0 && n >= c->sp.min_n && c->pack_mode == (c->dither ? 1 : 2) && !(c->dither && c->sub_size == 1);
     const uint32_t nchunks = (n + chunk - 1) / chunk;
     const uint32_t nl = nchunks < c->nlanes ? nchunks : c->nlanes;
     CHECK(alloc_workspace(c, sparse ? 1 : chunk, nl));
@@ -972,9 +987,21 @@ int32_t ensure_incumbent(snesimage_ctx *c) {
 
 int32_t check_slot(snesimage_ctx *c, uint32_t palette, uint32_t index) {
     if (!c) return fail(SNES_ERR_ARG, "null context");
-    if (palette >= c->sub_count || index >= c->sub_size) return fail(SNES_ERR_ARG, "palette slot out of range");
+    if (c->backdrop && palette == c->sub_count && index == 0) return SNES_OK; // the backdrop slot
+    if (palette >= c->sub_count || index >= (c->backdrop ? c->user_size : c->sub_size)) return fail(SNES_ERR_ARG, "palette slot out of range");
     return SNES_OK;
 }
+// A slot address of the interface in the context's own terms: the backdrop slot is entry user_size of subpalette 0, the
+// first of the tied entries.  While the scope lives, a call on it is scored and committed as the tied slot.
+struct SlotScope {
+    snesimage_ctx *c; uint32_t sp, si; bool saved;
+    SlotScope(snesimage_ctx *c_, uint32_t palette, uint32_t index) : c(c_), sp(palette), si(index), saved(c_->tied_call) {
+        c->tied_call = c->backdrop && palette == c->sub_count;
+        if (c->tied_call) { sp = 0; si = c->user_size; }
+    }
+    ~SlotScope() { c->tied_call = saved; }
+};
+const char *kBackdropRefused = "SNES_BACKDROP contexts are not supported here: the backdrop schedule is not carried through batches, groups, shared-palette sets and split-phase slot windows";
 
 int32_t batch_quiesce(struct snesimage_batch *b);
 int32_t set_device(snesimage_ctx *c) { HIPCHK(hipSetDevice(c->device)); return c->owner ? batch_quiesce(c->owner) : SNES_OK; }
@@ -1023,7 +1050,7 @@ int32_t commit(snesimage_ctx *c, const double *d_errors, uint32_t n, uint32_t me
         T.eotf = c->d_eotf; T.lab_eotf = c->d_lab_eotf; T.rgb8 = c->d_pal_rgb8; T.lin = c->d_pal_lin; T.xyb = c->d_pal_xyb; T.lab = c->perceptual ? c->d_pal_lab : nullptr;
     }
     hipLaunchKernelGGL(k_commit, dim3(1), dim3(256), 0, c->stream, d_errors, (int)n, c->d_cand, c->d_colors, (int)(palette * c->sub_size + index), method == SNES_METHOD_NES ? 1 : 0, c->d_inc_err,
-                       c->d_last, T);
+                       c->d_last, T, c->tied_call ? (int)c->sub_count : 0, (int)c->sub_size); // (the tied slot: every subpalette's copy of B and its table rows, on the device)
     HIPCHK(hipGetLastError());
     c->pack_valid = false; c->epoch++; c->epoch_by_commit = true;
     const bool was_synced = c->map_synced;
@@ -1052,6 +1079,24 @@ int32_t commit(snesimage_ctx *c, const double *d_errors, uint32_t n, uint32_t me
 
 #include "kmeans_host.inc"
 
+namespace {
+// B into every tied entry of the device palette; what depends on the palette is invalidated as by snesimage_set_palette_rgb5
+int32_t write_backdrop(snesimage_ctx *c, const uint8_t *b) {
+    CHECK(ensure_map(c));
+    for (uint32_t p = 0; p < c->sub_count; p++)
+        HIPCHK(hipMemcpyAsync(c->d_colors + 3 * ((size_t)p * c->sub_size + c->user_size), b, 3, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->tables_valid = false; c->pack_valid = false; c->inc_valid = false; c->map_synced = false; c->epoch++; c->epoch_by_commit = false;
+    return SNES_OK;
+}
+// the interface's palette (sub_count * user_size regular entries) <-> the device palette (the expanded context's)
+int32_t read_colors(snesimage_ctx *c, uint8_t *all /*ncol*3*/) {
+    HIPCHK(hipMemcpyAsync(all, c->d_colors, 3 * (size_t)c->ncol, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SNES_OK;
+}
+} // namespace
+
 extern "C" {
 
 const char *snesimage_last_error(void) { return g_err.c_str(); }
@@ -1066,12 +1111,16 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (w != 256) return fail(SNES_ERR_ARG, "image width must be 256 (tile stride is fixed at 32, lib.rs:58)");
     if (h < 8 || h > 256 || (h % 8) != 0) return fail(SNES_ERR_ARG, "image height must be a multiple of 8 in [8,256]");
     if (sub_count < 1 || sub_size < 1 || sub_count > 253 || sub_size > 253 || sub_count * sub_size > 253) return fail(SNES_ERR_ARG, "sub_count*sub_size must be in [1,253]");
+    const bool backdrop = (flags & SNES_BACKDROP) != 0;
+    if (backdrop && (sub_size > 15 || sub_count * (sub_size + 1) > 253)) return fail(SNES_ERR_ARG, "with SNES_BACKDROP sub_size must be at most 15 and sub_count*(sub_size+1) at most 253");
     if (device < 0) return fail(SNES_ERR_ARG, "device must be a HIP device ordinal >= 0 (this library has no CPU path)");
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device >= ndev) return fail(SNES_ERR_ARG, "no such HIP device");
     HIPCHK(hipSetDevice(device));
     snesimage_ctx *c = new snesimage_ctx();
+    c->backdrop = backdrop; c->user_size = sub_size;
+    if (backdrop) sub_size += 1; // the expanded context: B is the last entry of every subpalette
     c->device = device; c->W = w; c->H = h; c->sub_count = sub_count; c->sub_size = sub_size; c->flags = flags; c->ncol = (int)(sub_count * sub_size);
     c->dither = flags & SNES_DITHER; c->perceptual = flags & SNES_PERCEPTUAL; c->nes = flags & SNES_NES;
     c->npx = (size_t)w * h;
@@ -1176,6 +1225,15 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
         HIPCHK(hipMemcpyAsync(c->d_lab_eotf, c->h_lab_eotf, sizeof(c->h_lab_eotf), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         CHECK(ensure_cand_capacity(c, 64));
+        if (c->backdrop) { // B starts as the mean of the opaque pixels, rounded per channel, then cut to 5 bits (--nes: snapped to the table)
+            unsigned long long sum[3] = {0, 0, 0}, cnt = 0;
+            for (size_t px = 0; px < c->npx; px++)
+                if (rgba[4 * px + 3] != 0) { sum[0] += rgba[4 * px]; sum[1] += rgba[4 * px + 1]; sum[2] += rgba[4 * px + 2]; cnt++; }
+            uint8_t b[3] = {0, 0, 0};
+            if (cnt) for (int ch = 0; ch < 3; ch++) b[ch] = (uint8_t)(((sum[ch] + cnt / 2) / cnt) >> 3);
+            if (c->nes) { uint8_t raw[3] = {b[0], b[1], b[2]}; host_new_nes_only(raw, c->perceptual, c->h_lab_eotf, b); }
+            CHECK(write_backdrop(c, b));
+        }
         return SNES_OK;
     };
     rc = body();
@@ -1259,8 +1317,9 @@ int32_t snesimage_score_candidates_device(snesimage_ctx *c, uint32_t palette, ui
     if (!d_rgb5 || !d_errors) return fail(SNES_ERR_ARG, "null pointer");
     if (n == 0) return SNES_OK;
     CHECK(set_device(c));
-    CHECK(prep_for_slot(c, (int)palette, (int)index));
-    CHECK(score_list(c, d_rgb5, n, d_errors, 1, 0, (int)palette, (int)index, d_maps_out));
+    SlotScope s(c, palette, index);
+    CHECK(prep_for_slot(c, (int)s.sp, (int)s.si));
+    CHECK(score_list(c, d_rgb5, n, d_errors, 1, 0, (int)s.sp, (int)s.si, d_maps_out));
     return SNES_OK;
 }
 
@@ -1293,8 +1352,10 @@ int32_t snesimage_remap_candidates_device(snesimage_ctx *c, uint32_t palette, ui
     }
     CHECK(ensure_tables(c));
     if (c->perceptual) CHECK(ensure_source(c));
-    CHECK(prep_for_slot(c, (int)palette, (int)index));
-    const uint32_t slot_ci = palette * c->sub_size + index;
+    SlotScope s(c, palette, index);
+    index = s.si;
+    CHECK(prep_for_slot(c, (int)s.sp, (int)s.si));
+    const uint32_t slot_ci = c->tied_call ? (kTiedSlot | (c->sub_size << 8) | s.si) : s.sp * c->sub_size + s.si;
     for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
         const uint32_t nc = (n - c0 < chunk) ? (n - c0) : chunk;
         const uint8_t *rgb5 = d_rgb5 + 3 * (size_t)c0;
@@ -1334,10 +1395,11 @@ int32_t snesimage_step_async(snesimage_ctx *c, uint32_t method, uint32_t palette
     const uint32_t n = method_count(method, n_random);
     CHECK(ensure_cand_capacity(c, n));
     if (method != SNES_METHOD_NES) CHECK(ensure_incumbent(c)); // lib.rs:199, 294 (nes: f64::MAX, lib.rs:250)
-    CHECK(gen_candidates(c, method, palette, index, channel, seed, step_id, n));
-    CHECK(prep_for_slot(c, (int)palette, (int)index));
-    CHECK(score_list(c, c->d_cand, n, c->d_errs, 1, 0, (int)palette, (int)index, nullptr));
-    CHECK(commit(c, c->d_errs, n, method, palette, index));
+    SlotScope s(c, palette, index);
+    CHECK(gen_candidates(c, method, s.sp, s.si, channel, seed, step_id, n));
+    CHECK(prep_for_slot(c, (int)s.sp, (int)s.si));
+    CHECK(score_list(c, c->d_cand, n, c->d_errs, 1, 0, (int)s.sp, (int)s.si, nullptr));
+    CHECK(commit(c, c->d_errs, n, method, s.sp, s.si));
     return SNES_OK;
 }
 
@@ -1367,12 +1429,13 @@ int32_t snesimage_step_begin(snesimage_ctx *c, uint32_t method, uint32_t palette
     const uint32_t n = method_count(method, n_total);
     CHECK(ensure_cand_capacity(c, n));
     if (method != SNES_METHOD_NES) CHECK(ensure_incumbent(c));
-    CHECK(gen_candidates(c, method, palette, index, channel, seed, step_id, n, shard_rank, shard_count, d_errors)); // + this shard's list, errors preset to +inf
+    SlotScope s(c, palette, index);
+    CHECK(gen_candidates(c, method, s.sp, s.si, channel, seed, step_id, n, shard_rank, shard_count, d_errors)); // + this shard's list, errors preset to +inf
     const uint32_t n_own = (n > shard_rank) ? (n - shard_rank + shard_count - 1) / shard_count : 0;
     if (n_own) {
-        CHECK(prep_for_slot(c, (int)palette, (int)index));
+        CHECK(prep_for_slot(c, (int)s.sp, (int)s.si));
         // candidate j of the shard is global candidate shard_rank + j*shard_count
-        CHECK(score_list(c, c->d_cand_sel, n_own, d_errors, (int)shard_count, (int)shard_rank, (int)palette, (int)index, nullptr));
+        CHECK(score_list(c, c->d_cand_sel, n_own, d_errors, (int)shard_count, (int)shard_rank, (int)s.sp, (int)s.si, nullptr));
     }
     if (!n_own) c->best_valid = false;
     c->pend = true; c->pend_n = n; c->pend_sp = palette; c->pend_si = index; c->pend_method = method;
@@ -1384,7 +1447,8 @@ int32_t snesimage_step_commit(snesimage_ctx *c, const double *d_errors) {
     if (!c->pend) return fail(SNES_ERR_STATE, "step_commit without step_begin");
     CHECK(set_device(c));
     c->pend = false;
-    return commit(c, d_errors, c->pend_n, c->pend_method, c->pend_sp, c->pend_si);
+    SlotScope s(c, c->pend_sp, c->pend_si);
+    return commit(c, d_errors, c->pend_n, c->pend_method, s.sp, s.si);
 }
 
 int32_t snesimage_get_tile_palettes(snesimage_ctx *c, uint8_t *out) {
@@ -1407,14 +1471,37 @@ int32_t snesimage_set_tile_palettes(snesimage_ctx *c, const uint8_t *in) {
 int32_t snesimage_get_palette_rgb5(snesimage_ctx *c, uint8_t *out) {
     if (!c || !out) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(set_device(c));
+    if (c->backdrop) { // the regular entries only
+        std::vector<uint8_t> all(3 * (size_t)c->ncol);
+        CHECK(read_colors(c, all.data()));
+        for (uint32_t p = 0; p < c->sub_count; p++) memcpy(out + 3 * (size_t)p * c->user_size, &all[3 * (size_t)p * c->sub_size], 3 * (size_t)c->user_size);
+        return SNES_OK;
+    }
     HIPCHK(hipMemcpyAsync(out, c->d_colors, 3 * (size_t)c->ncol, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return SNES_OK;
+}
+int32_t snesimage_get_backdrop_rgb5(snesimage_ctx *c, uint8_t *out) {
+    if (!c || !out) return fail(SNES_ERR_ARG, "null pointer");
+    if (!c->backdrop) return fail(SNES_ERR_ARG, "the context was created without SNES_BACKDROP");
+    CHECK(set_device(c));
+    HIPCHK(hipMemcpyAsync(out, c->d_colors + 3 * (size_t)c->user_size, 3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SNES_OK;
+}
+int32_t snesimage_set_backdrop_rgb5(snesimage_ctx *c, const uint8_t *in) {
+    if (!c || !in) return fail(SNES_ERR_ARG, "null pointer");
+    if (!c->backdrop) return fail(SNES_ERR_ARG, "the context was created without SNES_BACKDROP");
+    if (in[0] > 31 || in[1] > 31 || in[2] > 31) return fail(SNES_ERR_ARG, "backdrop channels are 5-bit values");
+    CHECK(set_device(c));
+    return write_backdrop(c, in);
 }
 int32_t snesimage_set_palette_rgb5(snesimage_ctx *c, const uint8_t *in) {
     if (!c || !in) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(set_device(c));
     CHECK(ensure_map(c));
+    if (c->backdrop) for (uint32_t p = 0; p < c->sub_count; p++) HIPCHK(hipMemcpyAsync(c->d_colors + 3 * (size_t)p * c->sub_size, in + 3 * (size_t)p * c->user_size, 3 * (size_t)c->user_size, hipMemcpyHostToDevice, c->stream)); // (B stays)
+    else
     HIPCHK(hipMemcpyAsync(c->d_colors, in, 3 * (size_t)c->ncol, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->tables_valid = false; c->pack_valid = false; c->inc_valid = false; c->map_synced = false; c->epoch++; c->epoch_by_commit = false;
@@ -1424,7 +1511,7 @@ int32_t snesimage_get_palette_u16(snesimage_ctx *c, uint16_t *out) {
     if (!c || !out) return fail(SNES_ERR_ARG, "null pointer");
     std::vector<uint8_t> raw(3 * (size_t)c->ncol);
     CHECK(snesimage_get_palette_rgb5(c, raw.data()));
-    for (int i = 0; i < c->ncol; i++) out[i] = rgb5_as_u16(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
+    for (int i = 0; i < (int)(c->sub_count * c->user_size); i++) out[i] = rgb5_as_u16(raw[3 * i], raw[3 * i + 1], raw[3 * i + 2]);
     return SNES_OK;
 }
 int32_t snesimage_get_palette_map(snesimage_ctx *c, uint8_t *out) {
@@ -1452,7 +1539,7 @@ int32_t snesimage_as_rgba(snesimage_ctx *c, uint8_t *out) {
     std::vector<uint8_t> map(c->npx), tp(1024), col(3 * (size_t)c->ncol), orig(c->npx * 4);
     CHECK(snesimage_get_palette_map(c, map.data()));
     CHECK(snesimage_get_tile_palettes(c, tp.data()));
-    CHECK(snesimage_get_palette_rgb5(c, col.data()));
+    CHECK(read_colors(c, col.data())); // (a backdrop pixel's map value is user_size: the tied entry of its subpalette)
     HIPCHK(hipMemcpy(orig.data(), c->d_orig, c->npx * 4, hipMemcpyDeviceToHost));
     memset(out, 0, c->npx * 4);
     for (uint32_t y = 0; y < c->H; y++)
@@ -1470,14 +1557,16 @@ int32_t snesimage_as_rgba(snesimage_ctx *c, uint8_t *out) {
 int64_t snesimage_as_json(snesimage_ctx *c, char *out, int64_t cap) {
     if (!c) return fail(SNES_ERR_ARG, "null context");
     std::vector<uint8_t> map(c->npx), tp(1024), col(3 * (size_t)c->ncol), orig(c->npx * 4);
-    if (snesimage_get_palette_map(c, map.data()) || snesimage_get_tile_palettes(c, tp.data()) || snesimage_get_palette_rgb5(c, col.data())) return SNES_ERR_HIP;
+    if (snesimage_get_palette_map(c, map.data()) || snesimage_get_tile_palettes(c, tp.data()) || read_colors(c, col.data())) return SNES_ERR_HIP;
+    // SNES_BACKDROP: slot 0 of every row holds B (the hardware reads CGRAM word 0), and a backdrop pixel is index 0 like a transparent one
+    const unsigned b16 = c->backdrop ? rgb5_as_u16(col[3 * c->user_size], col[3 * c->user_size + 1], col[3 * c->user_size + 2]) : 0u;
     if (hipMemcpy(orig.data(), c->d_orig, c->npx * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(SNES_ERR_HIP, "hipMemcpy failed");
     const uint32_t wt = c->W / 8, ht = c->H / 8;
     std::string s = "{\"palette\":[";
     for (uint32_t p = 0; p < c->sub_count; p++)
         for (uint32_t i = 0; i < 16; i++) {
-            unsigned v = 0;
-            if (i != 0 && i <= c->sub_size) { size_t k = (size_t)p * c->sub_size + i - 1; v = rgb5_as_u16(col[3 * k], col[3 * k + 1], col[3 * k + 2]); }
+            unsigned v = i == 0 ? b16 : 0u;
+            if (i != 0 && i <= c->user_size) { size_t k = (size_t)p * c->sub_size + i - 1; v = rgb5_as_u16(col[3 * k], col[3 * k + 1], col[3 * k + 2]); }
             if (p || i) s += ',';
             s += std::to_string(v);
         }
@@ -1491,7 +1580,7 @@ int64_t snesimage_as_json(snesimage_ctx *c, char *out, int64_t cap) {
             for (uint32_t y = 0; y < 8; y++)
                 for (uint32_t x = 0; x < 8; x++) {
                     size_t px = (size_t)(ty * 8 + y) * c->W + (tx * 8 + x);
-                    unsigned v = orig[4 * px + 3] == 0 ? 0u : (unsigned)(uint8_t)(map[px] + 1);
+                    unsigned v = (orig[4 * px + 3] == 0 || (c->backdrop && map[px] == c->user_size)) ? 0u : (unsigned)(uint8_t)(map[px] + 1);
                     if (x || y) s += ',';
                     s += std::to_string(v);
                 }
@@ -1519,6 +1608,19 @@ void snesimage_schedule_next(uint32_t sub_count, uint32_t sub_size, int32_t nes,
     if (*channel == 3 || random) {
         *channel = 0; *index += 1;
         if (*index == sub_size) { *index = 0; *palette += 1; if (*palette == sub_count) { *palette = 0; *step += 1; } }
+    }
+}
+
+// The same with one more slot per sweep: behind (sub_count - 1, sub_size - 1) comes the backdrop slot (sub_count, 0), then the wrap
+void snesimage_schedule_next_backdrop(uint32_t sub_count, uint32_t sub_size, int32_t nes, uint32_t *palette, uint32_t *index, uint32_t *channel, uint32_t *step, uint32_t *method) {
+    const bool random = (*step % 5) < 4;
+    if (method) *method = nes ? SNES_METHOD_NES : (random ? SNES_METHOD_RANDOM : SNES_METHOD_CHANNEL);
+    *channel += 1;
+    if (*channel == 3 || random) {
+        *channel = 0;
+        if (*palette >= sub_count) { *palette = 0; *index = 0; *step += 1; return; } // behind the backdrop slot
+        *index += 1;
+        if (*index == sub_size) { *index = 0; *palette += 1; } // (*palette == sub_count: the backdrop slot)
     }
 }
 

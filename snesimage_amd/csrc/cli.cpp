@@ -10,6 +10,8 @@
 // reference's TODO.md:38-39), --preview FILE.png (source | result side by side, the picture the SDL window of
 // src/lib.rs:937-960 shows).  The source image is a PNG (png_io.hpp restates `image::open(..).into_rgba8()`,
 // src/lib.rs:836, for that format), a raw RGBA8 file of 256*H*4 bytes, or `synth:SEED`.
+// --backdrop gives every tile one more colour, the SNES backdrop colour shared by all tiles (include/snesimage_hip.h:
+// SNES_BACKDROP), optimized like any entry; --backdrop-fixed R,G,B (5-bit) keeps it at the given colour.
 // --share SOURCE=TARGET (repeatable) optimizes one palette for the main image and every such image together (a set,
 // include/snesimage_hip.h): the frames of an animation share one CGRAM on the console.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
@@ -56,6 +58,10 @@ void usage() {
             "Arguments:\n  <SOURCE_FILENAME>  PNG image, raw RGBA8 file (256 x H x 4 bytes, H a multiple of 8 up to 256) or synth:SEED\n  <TARGET_FILENAME>  JSON output\n\n"
             "Options:\n  -c, --subpalette-count <N>  [default: 1]\n  -s, --subpalette-size <N>   [default: 7]\n"
             "  -d, --dither\n      --perceptual-palettes\n      --nes\n"
+            "      --backdrop           one more colour for every tile: the backdrop colour (CGRAM word 0) shows where a tile has index 0;\n"
+            "                           it is optimized like any entry and written to slot 0 of every palette row (needs -s <= 15,\n"
+            "                           c*(s+1) <= 253; not with --share or --devices)\n"
+            "      --backdrop-fixed <R,G,B>  the same with the backdrop colour given (5-bit channels) and never changed\n"
             "      --calls <N>          optimizer calls to run [default: 0]\n      --candidates <N>     random candidates per call [default: 64]\n"
             "      --window <N>         optimizer calls scored per launch set (0 = adaptive, 1 = call by call; same result) [default: 0]\n"
             "      --seed <N>           candidate RNG seed [default: 1]\n      --device <N>         HIP device [default: 0]\n"
@@ -156,6 +162,7 @@ int main(int argc, char **argv) {
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
+    bool backdrop = false, backdrop_fixed = false; uint8_t backdrop_rgb[3] = {0, 0, 0}; std::string backdrop_arg;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -164,6 +171,8 @@ int main(int argc, char **argv) {
         else if (a == "-d" || a == "--dither") flags |= SNES_DITHER;
         else if (a == "--perceptual-palettes") flags |= SNES_PERCEPTUAL;
         else if (a == "--nes") flags |= SNES_NES;
+        else if (a == "--backdrop") backdrop = true;
+        else if (a == "--backdrop-fixed") { backdrop_fixed = true; backdrop_arg = need("--backdrop-fixed"); }
         else if (a == "--calls") calls = (uint32_t)strtoul(need("--calls"), nullptr, 10);
         else if (a == "--candidates") ncand = (uint32_t)strtoul(need("--candidates"), nullptr, 10);
         else if (a == "--seed") seed = strtoull(need("--seed"), nullptr, 0);
@@ -197,6 +206,23 @@ int main(int argc, char **argv) {
         const char *bad = !resume_file.empty() ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--share <SOURCE=TARGET>' cannot be used with %s\n", bad); return 2; }
     }
+    if (backdrop || backdrop_fixed) { // said before any device is touched
+        const char *opt = backdrop_fixed ? "--backdrop-fixed" : "--backdrop";
+        if (backdrop_fixed) {
+            unsigned v[3]; char tail = 0;
+            if (sscanf(backdrop_arg.c_str(), "%u,%u,%u%c", &v[0], &v[1], &v[2], &tail) != 3 || v[0] > 31 || v[1] > 31 || v[2] > 31) {
+                fprintf(stderr, "error: invalid value '%s' for '--backdrop-fixed <R,G,B>': expected three 5-bit values, such as 0,0,31\n", backdrop_arg.c_str()); return 1; }
+            for (int k = 0; k < 3; k++) backdrop_rgb[k] = (uint8_t)v[k];
+        }
+        if (!shares.empty() || !devices.empty()) { fprintf(stderr, "error: '%s' cannot be used with '%s': sets and device groups do not carry the backdrop colour yet\n", opt, !shares.empty() ? "--share" : "--devices"); return 1; }
+        if (size > 15 || (unsigned long long)count * (size + 1) > 253) {
+            fprintf(stderr, "error: '%s' needs --subpalette-size <= 15 and count * (size + 1) <= 253: a row of 16 colours holds the backdrop colour and 15 of its own\n", opt); return 1; }
+        flags |= SNES_BACKDROP;
+    }
+    const bool bd = (flags & SNES_BACKDROP) != 0, bd_sched = bd && !backdrop_fixed; // --backdrop-fixed runs the plain schedule: B is never a call's slot
+    auto sched_next = [&](uint32_t *p, uint32_t *ix, uint32_t *ch, uint32_t *st, uint32_t *m) {
+        if (bd_sched) snesimage_schedule_next_backdrop(count, size, (flags & SNES_NES) ? 1 : 0, p, ix, ch, st, m); else snesimage_schedule_next(count, size, (flags & SNES_NES) ? 1 : 0, p, ix, ch, st, m);
+    };
     // the JSON keeps 15 colours per subpalette (src/lib.rs:583-593): a larger subpalette cannot be read back from it
     if (!resume_file.empty() && size > 15) die("--resume needs --subpalette-size <= 15: the output keeps 15 colours per subpalette");
 
@@ -222,6 +248,7 @@ int main(int argc, char **argv) {
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
     if (snesimage_create(rgba.data(), w, h, count, size, flags, device, &ctx) != 0) die(snesimage_last_error());
+    if (backdrop_fixed && snesimage_set_backdrop_rgb5(ctx, backdrop_rgb) != 0) die(snesimage_last_error()); // (the initialisers end with optimize(), which sees it)
     // --share: one context per image, every member's storage sized for one call's candidates (about 4.45 MB each), one set
     std::vector<snesimage_ctx *> frames{ctx};
     snesimage_shared *set = nullptr;
@@ -253,6 +280,12 @@ int main(int argc, char **argv) {
                 uint8_t *o = &rgb5[3 * ((size_t)p * size + i)];
                 o[0] = (uint8_t)(v & 31); o[1] = (uint8_t)((v >> 5) & 31); o[2] = (uint8_t)((v >> 10) & 31);
             }
+        if (bd && !backdrop_fixed) { // a backdrop run wrote B into slot 0 of every row (and 0 into `tiles` where a pixel shows it: optimize() below finds those again)
+            const long v = pal[0];
+            if (v < 0 || v > 0x7fff) die("resume file: colour out of range");
+            const uint8_t b[3] = {(uint8_t)(v & 31), (uint8_t)((v >> 5) & 31), (uint8_t)((v >> 10) & 31)};
+            if (snesimage_set_backdrop_rgb5(ctx, b) != 0) die(snesimage_last_error());
+        }
         if (snesimage_set_tile_palettes(ctx, tp8.data()) != 0 || snesimage_set_palette_rgb5(ctx, rgb5.data()) != 0 || snesimage_optimize(ctx) != 0) die(snesimage_last_error());
         log_info("Resumed from " + resume_file);
     } else if (set) { // the reference's initialisers on the images stacked top to bottom
@@ -292,8 +325,8 @@ int main(int argc, char **argv) {
     log_info("Beginning optimization"); // src/lib.rs:992
     uint32_t palette = 0, index = 0, channel = 0, step = 0, sweep = 0;
     double last_error = 1.7976931348623157e308;
-    std::vector<uint8_t> before(3 * (size_t)count * size), after(before.size());
-    const int nes = (flags & SNES_NES) ? 1 : 0;
+    std::vector<uint8_t> before(3 * ((size_t)count * size + 1)), after(before.size()); // (+ the backdrop colour, behind the last entry: slot (count, 0))
+    auto load_before = [&]() { if (snesimage_get_palette_rgb5(ctx, before.data()) != 0 || (bd && snesimage_get_backdrop_rgb5(ctx, &before[3 * (size_t)count * size]) != 0)) die(snesimage_last_error()); };
     auto report = [&](uint32_t p, uint32_t ix, const uint8_t *b, const uint8_t *best, double error) {
         if (b[0] != best[0] || b[1] != best[1] || b[2] != best[2]) { // src/lib.rs:222-234
             char m[160];
@@ -326,14 +359,14 @@ int main(int argc, char **argv) {
         // trajectory, call for call, as stepping one call at a time (--window 1).  A run ends with its sweep when tiles are
         // to be reassigned between sweeps.  --share: snesimage_shared_run_slots, the same for a set (the records carry E).
         std::vector<snesimage_call_result> log;
-        if (snesimage_get_palette_rgb5(ctx, before.data()) != 0) die(snesimage_last_error());
+        load_before();
         snesimage_run_stats total{};
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every) { // calls left in the current sweep
+            if (reassign_every || tile_every || backdrop_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
-                while (st == step && k < n) { snesimage_schedule_next(count, size, nes, &p, &ix, &ch, &st, &m); k++; }
+                while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;
             }
             log.resize(n);
@@ -343,9 +376,10 @@ int main(int argc, char **argv) {
                  : group ? snesimage_group_run_slots(group, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)
                          : snesimage_run_slots(ctx, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)) != 0) die(std::string("Unable to optimize palette: ") + snesimage_last_error());
             total.calls += rs.calls; total.accepted += rs.accepted; total.windows += rs.windows; total.scored += rs.scored; total.useful += rs.useful;
+            if (backdrop_fixed && palette == count) { palette = 0; index = 0; channel = 0; step += 1; } // the library's schedule has arrived at the backdrop slot: this run passes it by
             for (uint32_t j = 0; j < n; j++) {
                 const uint32_t cp = p, ci = ix;
-                snesimage_schedule_next(count, size, nes, &p, &ix, &ch, &st, &method);
+                sched_next(&p, &ix, &ch, &st, &method);
                 uint8_t *b = &before[3 * ((size_t)cp * size + ci)];
                 report(cp, ci, b, log[j].rgb5, log[j].error);
                 b[0] = log[j].rgb5[0]; b[1] = log[j].rgb5[1]; b[2] = log[j].rgb5[2];
@@ -362,8 +396,8 @@ int main(int argc, char **argv) {
     } else
     for (uint32_t call = 0; call < calls; call++) {
         uint32_t p = palette, ix = index, ch = channel, method = 0;
-        snesimage_schedule_next(count, size, nes, &palette, &index, &channel, &step, &method);
-        snesimage_get_palette_rgb5(ctx, before.data());
+        sched_next(&palette, &index, &channel, &step, &method);
+        load_before();
         double error = 0.0; uint8_t best[3];
         const int32_t rc = set ? snesimage_shared_step(set, method, p, ix, ch, seed, call, method == SNES_METHOD_RANDOM ? ncand : 0, &error, best)
                          : group ? snesimage_group_step(group, method, p, ix, ch, seed, call, method == SNES_METHOD_RANDOM ? ncand : 0, &error, best)

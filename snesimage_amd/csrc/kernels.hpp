@@ -137,11 +137,21 @@ __device__ __forceinline__ void dedup_copy_body(const uint8_t *__restrict__ rgb5
 //   mode 0: argmin over the whole subpalette -> palette_map (this IS optimize() without dither), thr = 0
 //   mode 1: ci from the stored palette_map (error() of the current state), thr = 0
 //   mode 2: argmin over the subpalette excluding slot (sp, si); thr = key the candidate must beat
+//   mode 3: the same with entry si excluded in EVERY subpalette (the tied slot of a backdrop context: one colour that is
+//           entry si of all of them), so every opaque pixel carries a key to beat
 // Distance: exact integer redmean key (lib.rs:1080-1088) or, with lab != null, CIEDE2000 in f32
 // (lib.rs:1090-1100) on precomputed Lab of the pixel (labpx) and of the entries (pal_lab).
 // Ties keep the lowest index (strict <, lib.rs:788-791): the candidate (index si) wins a tie
 // against base index j iff si < j, folded into thr (integer keys) or the tie flag bit (float keys).
 // ------------------------------------------------------------------------------------------------
+// The slot a map-reading stage gives the candidate's colour to: one colour index, or — the tied slot of a backdrop context —
+// entry si of every subpalette, written kTiedSlot | sub_size << 8 | si (0xffffffff matches nothing).
+constexpr uint32_t kTiedSlot = 0x7d000000u;
+__device__ __forceinline__ bool slot_hit(uint32_t ci, uint32_t slot_ci, uint32_t ncol) {
+    if ((slot_ci >> 24) != (kTiedSlot >> 24)) return ci == slot_ci;
+    return ci < ncol && ci % ((slot_ci >> 8) & 0xffu) == (slot_ci & 0xffu);
+}
+
 struct PrepParams {
     const uint8_t *orig; const uint8_t *tile_pal; const uint32_t *pal_rgb8; uint8_t *map;
     unsigned long long *pack, *packT, *packC4, *packR4;
@@ -175,7 +185,7 @@ __device__ __forceinline__ void prep_body(const PrepParams &P) {
     } else if (P.mode == 1) {
         ci = (uint32_t)(base + P.map[px]);
     } else {
-        bool excl = (P.mode == 2 && sub == P.sp);
+        bool excl = (P.mode == 2 && sub == P.sp) || P.mode == 3;
         int best = -1;
         if (!P.perceptual) {
             uint32_t bk = 0xffffffffu;
@@ -344,7 +354,7 @@ __global__ __launch_bounds__(256) void k_downscale_chain(DownParams P) {
                             if (ci != (uint32_t)P.ncol + 1u) ci = (uint32_t)P.tile_pal[(x0 >> 3) + (y0 >> 3) * (G.W >> 3)] * P.sub_size + P.maps[(size_t)cand * G.W * G.H + px];
                             // candidate colour sits at its real slot in use_maps mode (pal_lin patched per candidate is not possible), so
                             // the caller passes si via cand_tab[7]; see k_dither for the map producer
-                            if (ci == __float_as_uint(P.cand_tab[8 * (size_t)cand + 7])) ci = (uint32_t)P.ncol;
+                            if (slot_hit(ci, __float_as_uint(P.cand_tab[8 * (size_t)cand + 7]), (uint32_t)P.ncol)) ci = (uint32_t)P.ncol;
                         } else if (P.perceptual) ci = resolve_ci<true>(P.pack[px], crgb, cl, P.labpx + 3 * (size_t)px, (uint32_t)P.ncol);
                         else ci = resolve_ci<false>(P.pack[px], crgb, cl, nullptr, (uint32_t)P.ncol);
                         sum[0] += s_lin[3 * ci]; sum[1] += s_lin[3 * ci + 1]; sum[2] += s_lin[3 * ci + 2];
@@ -581,7 +591,7 @@ __global__ __launch_bounds__(256) void k_hpass(HParams P) {
                         ci = lo >> 24;
                         if (ci != (uint32_t)P.ncol + 1u) {
                             ci = (uint32_t)P.tile_pal[(xr >> 3) + (y >> 3) * (G.W >> 3)] * P.sub_size + P.mapsT[(size_t)cand * ns + idx];
-                            if (ci == cand_slot_ci) ci = (uint32_t)P.ncol;
+                            if (slot_hit(ci, cand_slot_ci, (uint32_t)P.ncol)) ci = (uint32_t)P.ncol;
                         }
                     } else ci = resolve_ci<PERCEPTUAL>(P.packT[idx], crgb, cl, PERCEPTUAL ? P.labpxT + 3 * idx : nullptr, (uint32_t)P.ncol);
                     v2 = (ci == (uint32_t)P.ncol) ? cand_v : s_lut[ch][ci];
@@ -736,7 +746,7 @@ __global__ __launch_bounds__(256) void k_vpass(VParams P) {
                             ci = lo >> 24;
                             if (ci != (uint32_t)P.ncol + 1u) {
                                 ci = (uint32_t)P.tile_pal[(x >> 3) + (n >> 3) * (G.W >> 3)] * P.sub_size + P.maps[(size_t)cand * ns + idx];
-                                if (ci == cand_slot_ci) ci = (uint32_t)P.ncol;
+                                if (slot_hit(ci, cand_slot_ci, (uint32_t)P.ncol)) ci = (uint32_t)P.ncol;
                             }
                         } else ci = resolve_ci<PERCEPTUAL>(P.pack[idx], crgb, cl, PERCEPTUAL ? P.labpx + 3 * idx : nullptr, (uint32_t)P.ncol);
                         i2 = (ci == (uint32_t)P.ncol) ? cand_v : s_lut[ch][ci];

@@ -47,7 +47,7 @@ __device__ __forceinline__ void resolve4_maps(uint32_t mw, uint32_t sw, uint32_t
     for (int j = 0; j < 4; j++) {
         const uint32_t sb = (sw >> (8 * j)) & 0xffu, m = (mw >> (8 * j)) & 0xffu;
         const uint32_t c = sb == 255u ? ncol + 1u : sb + m;
-        ci[j] = c == slot_ci ? ncol : c;
+        ci[j] = slot_hit(c, slot_ci, ncol) ? ncol : c;
     }
 }
 

@@ -121,11 +121,11 @@ __device__ __forceinline__ void dither_body(const DitherParams &P, const int blk
     const int sub_size = SUB ? SUB : P.sub_size;
     for (int i = j; i < P.ncol; i += NT) {
         uint32_t c = P.pal_rgb8[i];
-        if ((uint32_t)i == P.slot_ci) c = __float_as_uint(P.cand_tab[8 * (size_t)cand + 6]);
+        if (slot_hit((uint32_t)i, P.slot_ci, (uint32_t)P.ncol)) c = __float_as_uint(P.cand_tab[8 * (size_t)cand + 6]);
         const uint32_t r = c & 0xff, g = (c >> 8) & 0xff, b = (c >> 16) & 0xff;
         s_ent[i] = make_uint4(r | (b << 16), (8u * (1024u + r)) | ((8u * (1534u - r)) << 16), g << 7, c);
         if (PERC) {
-            const float *src = ((uint32_t)i == P.slot_ci) ? P.cand_lab + 3 * (size_t)cand : P.pal_lab + 3 * (size_t)i;
+            const float *src = slot_hit((uint32_t)i, P.slot_ci, (uint32_t)P.ncol) ? P.cand_lab + 3 * (size_t)cand : P.pal_lab + 3 * (size_t)i;
             s_lab[3 * i] = src[0]; s_lab[3 * i + 1] = src[1]; s_lab[3 * i + 2] = src[2];
         }
     }
@@ -349,11 +349,11 @@ __device__ __forceinline__ void dither4_body(const DitherParams &P, const int bl
     const int sub_size = SUB ? SUB : P.sub_size;
     for (int i = tid; i < P.ncol; i += 512) {
         uint32_t col = P.pal_rgb8[i];
-        if ((uint32_t)i == P.slot_ci) col = __float_as_uint(P.cand_tab[8 * (size_t)cand + 6]);
+        if (slot_hit((uint32_t)i, P.slot_ci, (uint32_t)P.ncol)) col = __float_as_uint(P.cand_tab[8 * (size_t)cand + 6]);
         const uint32_t r = col & 0xff, g = (col >> 8) & 0xff, b = (col >> 16) & 0xff;
         s_ent[i] = make_uint4(r | (b << 16), (8u * (1024u + r)) | ((8u * (1534u - r)) << 16), g << 7, col);
         if (PERC) {
-            const float *src = ((uint32_t)i == P.slot_ci) ? P.cand_lab + 3 * (size_t)cand : P.pal_lab + 3 * (size_t)i;
+            const float *src = slot_hit((uint32_t)i, P.slot_ci, (uint32_t)P.ncol) ? P.cand_lab + 3 * (size_t)cand : P.pal_lab + 3 * (size_t)i;
             s_lab[3 * i] = src[0]; s_lab[3 * i + 1] = src[1]; s_lab[3 * i + 2] = src[2];
         }
     }
@@ -823,6 +823,17 @@ __device__ __forceinline__ void commit_decide(const double min_e, const int min_
     commit_apply(best, best_k, cand, colors, slot, inc_err, last, T);
 }
 
+// entries slot + p * stride, 0 < p < count, := entry slot: colour and the rows of every palette table
+__device__ __forceinline__ void tied_spread(uint8_t *__restrict__ colors, int slot, int count, int stride, const PaletteTables &T) {
+    for (int p = 1; p < count; p++) {
+        const int d = slot + p * stride;
+        for (int ch = 0; ch < 3; ch++) colors[3 * d + ch] = colors[3 * slot + ch];
+        if (!T.rgb8) continue;
+        T.rgb8[d] = T.rgb8[slot];
+        for (int ch = 0; ch < 3; ch++) { T.lin[3 * d + ch] = T.lin[3 * slot + ch]; T.xyb[3 * d + ch] = T.xyb[3 * slot + ch]; if (T.lab) T.lab[3 * d + ch] = T.lab[3 * slot + ch]; }
+    }
+}
+
 __device__ __forceinline__ void commit_body(const double *__restrict__ errors, int n, const uint8_t *__restrict__ cand, uint8_t *__restrict__ colors, int slot, int nes, double *__restrict__ inc_err,
                                             StepResult *__restrict__ last, const PaletteTables &T) {
     // The sequential scan "for k ascending: if e_k < best" ends on the FIRST index attaining the minimum, provided that
@@ -1091,8 +1102,11 @@ __global__ void k_gen_candidates(int method, int n, unsigned long long key, cons
     gen_candidates_body(method, n, key, colors, slot, channel, cand, rank, count, sel, errors);
 }
 __global__ __launch_bounds__(256) void k_commit(const double *__restrict__ errors, int n, const uint8_t *__restrict__ cand, uint8_t *__restrict__ colors, int slot, int nes, double *__restrict__ inc_err,
-                                               StepResult *__restrict__ last, PaletteTables T) {
+                                               StepResult *__restrict__ last, PaletteTables T, int tied_count = 0, int tied_stride = 0) {
     commit_body(errors, n, cand, colors, slot, nes, inc_err, last, T);
+    // the tied slot of a backdrop context: `slot` is the first of tied_count entries, tied_stride apart, that hold one colour —
+    // the others take the first one's colour and table rows (thread 0 wrote them above)
+    if (threadIdx.x == 0 && tied_count > 1 && last->best_k >= 0) tied_spread(colors, slot, tied_count, tied_stride, T);
 }
 
 } // namespace snes

@@ -133,7 +133,7 @@ int32_t kmeans_recalculate(snesimage_ctx *c, const std::vector<uint32_t> &which)
         }
         n.push_back((int)((long long)index.size() - off.back()));
     }
-    const int k = (int)c->sub_size;
+    const int k = (int)c->user_size; // (a backdrop context: the regular entries; B is not an initialiser's to move)
     for (size_t p = 0; p < n.size(); p++)
         if (!(2 <= k && k < n[p])) return fail(SNES_ERR_KMEANS, "k-means precondition 2 <= k < n violated (the reference panics here)");
     CHECK(kmeans_reserve(c, index.size() ? index.size() : 1, (int)which.size(), k));
@@ -214,10 +214,11 @@ int32_t kmeans_initialize_tiles(snesimage_ctx *c) { // lib.rs:79-189
     HIPCHK(hipStreamSynchronize(c->stream));
     for (size_t t = 0; t < map.size(); t++) tp[map[t]] = (uint8_t)assign[t]; // lib.rs:133-138
     std::vector<uint8_t> col(3 * (size_t)c->ncol);
+    if (c->backdrop) { HIPCHK(hipMemcpyAsync(col.data(), c->d_colors, col.size(), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); } // (B stays)
     for (int i = 0; i < k; i++) {
         uint8_t color[3];
         host_centre_to_color(c, &centres[3 * (size_t)i], color);
-        for (uint32_t j = 0; j < c->sub_size; j++) memcpy(&col[3 * ((size_t)i * c->sub_size + j)], color, 3); // lib.rs:181-183
+        for (uint32_t j = 0; j < c->user_size; j++) memcpy(&col[3 * ((size_t)i * c->sub_size + j)], color, 3); // lib.rs:181-183
     }
     HIPCHK(hipMemcpyAsync(c->d_tile_pal, tp.data(), 1024, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_colors, col.data(), col.size(), hipMemcpyHostToDevice, c->stream));

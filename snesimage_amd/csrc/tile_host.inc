@@ -125,8 +125,10 @@ int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map,
         if (c->perceptual && quad) hipLaunchKernelGGL((k_dither4_tile<0, true>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
         else if (c->perceptual) hipLaunchKernelGGL((k_dither_tile<true, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
         else if (quad && c->sub_size == 15) hipLaunchKernelGGL((k_dither4_tile<15, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
+        else if (quad && c->sub_size == 16) hipLaunchKernelGGL((k_dither4_tile<16, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
         else if (quad) hipLaunchKernelGGL((k_dither4_tile<0, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
         else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither_tile<false, 15>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
+        else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither_tile<false, 16>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
         else hipLaunchKernelGGL((k_dither_tile<false, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
     } else {
         TileRemapParams R{};

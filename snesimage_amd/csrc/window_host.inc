@@ -82,6 +82,11 @@ uint32_t window_max() { // most calls per window (every call keeps ~0.3 GB of ca
 }
 
 // What a window can speculate on: the group-sparse path (the batched kernels cover nothing else).
+// the scheduler a context's runs follow
+void ctx_schedule_next(const snesimage_ctx *c, int nes, uint32_t *palette, uint32_t *index, uint32_t *channel, uint32_t *step, uint32_t *method) {
+    if (c->backdrop) snesimage_schedule_next_backdrop(c->sub_count, c->user_size, nes, palette, index, channel, step, method);
+    else snesimage_schedule_next(c->sub_count, c->sub_size, nes, palette, index, channel, step, method);
+}
 bool window_capable(const snesimage_ctx *c) { return c->sp.enabled && !c->owner && !(c->dither && c->sub_size == 1); } // (one-entry subpalettes with --dither: dense path, see score_list)
 
 void window_release_child(snesimage_ctx *k) {
@@ -99,7 +104,7 @@ void window_release_child(snesimage_ctx *k) {
 // general H pass only) and group-sparse storage for one call's candidates plus B.
 int32_t window_make_child(snesimage_ctx *c, snesimage_ctx **out) {
     std::unique_ptr<snesimage_ctx, void (*)(snesimage_ctx *)> k(new snesimage_ctx(), window_release_child);
-    k->device = c->device; k->W = c->W; k->H = c->H; k->sub_count = c->sub_count; k->sub_size = c->sub_size; k->flags = c->flags; k->ncol = c->ncol;
+    k->device = c->device; k->W = c->W; k->H = c->H; k->sub_count = c->sub_count; k->sub_size = c->sub_size; k->user_size = c->sub_size; k->flags = c->flags; /* (a slot context scores regular slots of the expanded context: no backdrop of its own) */ k->ncol = c->ncol;
     k->dither_rec = c->dither_rec; k->dither4 = c->dither4; k->dither4_max = c->dither4_max; k->ditherw = c->ditherw; k->sp.ahead.on = false; // (slot contexts take the batched launches: their base images come a window ahead, not a call ahead)
     k->dither = c->dither; k->perceptual = c->perceptual; k->nes = c->nes; k->G = c->G; k->K = c->K; k->npx = c->npx; k->src_floats = c->src_floats; k->fast_mask = c->fast_mask;
     k->chunk = kMemberCand; k->nlanes = 1;
@@ -196,7 +201,8 @@ int32_t window_enqueue(snesimage_ctx *c, WindowRec &r, uint32_t n_slots, uint64_
     { uint32_t p = palette, i = index, ch = channel, st = step, m = 0, m0 = 0;
       while (K < n_slots) {
           const uint32_t cp = p, ci = i, cc = ch;
-          snesimage_schedule_next(c->sub_count, c->sub_size, c->nes ? 1 : 0, &p, &i, &ch, &st, &m);
+          if (c->backdrop && cp == c->sub_count) break; // a window ends in front of a backdrop call (snesimage_run_slots steps it on its own)
+          ctx_schedule_next(c, c->nes ? 1 : 0, &p, &i, &ch, &st, &m);
           if (K == 0) m0 = m; else if (m != m0) break;
           calls[K++] = Call{m, cp, ci, cc};
       } }
@@ -323,6 +329,7 @@ int32_t snesimage_slots_begin(snesimage_ctx *c, uint32_t n_slots, uint64_t seed,
     if (channel > 2 || n_slots == 0 || shard_count == 0 || shard_rank >= shard_count) return fail(SNES_ERR_ARG, "bad slots_begin arguments");
     if (!window_capable(c)) return fail(SNES_ERR_UNSUPPORTED, "slot windows cover the group-sparse path (not with SNES_SPARSE=0), with --dither subpalettes of two entries and more, and not a context lent to a batch");
     if (c->pend || c->win_pend) return fail(SNES_ERR_STATE, "a split-phase step is pending");
+    if (c->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
     CHECK(set_device(c));
     { uint32_t cap = window_max() * shard_count; if (cap > (uint32_t)snes::kMaxWindow) cap = snes::kMaxWindow; // a rank scores at most SNES_WINDOW_MAX calls of a window
       if (n_slots > cap) n_slots = cap; }
@@ -342,6 +349,7 @@ int32_t snesimage_slots_begin(snesimage_ctx *c, uint32_t n_slots, uint64_t seed,
 int32_t snesimage_slots_commit(snesimage_ctx *c, const double *d_errors, uint32_t *consumed, uint32_t *accepted, snesimage_call_result *log) {
     if (!c) return fail(SNES_ERR_ARG, "null context");
     snesimage_window *w = c->win;
+    if (c->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
     if (!w || !c->win_pend) return fail(SNES_ERR_STATE, "slots_commit without slots_begin");
     CHECK(set_device(c));
     c->win_pend = false;
@@ -367,11 +375,11 @@ int32_t snesimage_run_slots(snesimage_ctx *c, uint32_t n_calls, uint64_t seed, u
     Flight fl[snesimage_window::kRing]; uint32_t nfl = 0; int next_rec = 0; uint32_t win_seq = 0;
     uint32_t q_done = 0, qp = *palette, qi = *index, qch = *channel, qst = *step; // where the next window to enqueue starts if all in flight stay clean
     while (done < n_calls) {
-        if (!windows || !c->map_synced) {
+        if (!windows || !c->map_synced || (c->backdrop && nfl == 0 && *palette == c->sub_count)) {
             // One call on its own: configurations the windows do not cover, and a first call that starts from a palette_map
             // which is not optimize() of the palette (it changes the map even if it accepts nothing: lib.rs:237)
             uint32_t p = *palette, i = *index, ch = *channel;
-            snesimage_schedule_next(c->sub_count, c->sub_size, nes, palette, index, channel, step, &method);
+            ctx_schedule_next(c, nes, palette, index, channel, step, &method);
             CHECK(snesimage_step_async(c, method, p, i, ch, seed, first_step_id + done, n_random));
             snes::StepResult r;
             HIPCHK(hipMemcpyAsync(&r, c->d_last, sizeof(r), hipMemcpyDeviceToHost, c->stream));
@@ -389,7 +397,7 @@ int32_t snesimage_run_slots(snesimage_ctx *c, uint32_t n_calls, uint64_t seed, u
         // a window ahead only while windows come back clean: behind an acceptance the B phase computed ahead is thrown away
         // (measured right after the k-means start, 23 % acceptance: 0.34 -> 0.28 M useful cand/s with a window always ahead)
         const uint32_t eff_depth = (w->depth > 1 && w->clean_streak >= 2) ? w->depth : 1;
-        while (nfl < eff_depth && q_done < n_calls) {
+        while (nfl < eff_depth && q_done < n_calls && !(c->backdrop && qp == c->sub_count)) { // (a backdrop call is stepped on its own once the windows in front of it are in)
             uint32_t K = window ? window : w->adapt;
             if (K > n_calls - q_done) K = n_calls - q_done;
             if (K > window_max()) K = window_max();
@@ -405,7 +413,7 @@ int32_t snesimage_run_slots(snesimage_ctx *c, uint32_t n_calls, uint64_t seed, u
             CHECK(window_enqueue_commit(c, r, nullptr, log != nullptr));
             fl[nfl++] = Flight{next_rec, q_done, r.K, qp, qi, qch, qst};
             next_rec = (next_rec + 1) % snesimage_window::kRing;
-            for (uint32_t j = 0; j < r.K; j++) snesimage_schedule_next(c->sub_count, c->sub_size, nes, &qp, &qi, &qch, &qst, &method);
+            for (uint32_t j = 0; j < r.K; j++) ctx_schedule_next(c, nes, &qp, &qi, &qch, &qst, &method);
             q_done += r.K;
         }
         // the oldest window's result
@@ -416,7 +424,7 @@ int32_t snesimage_run_slots(snesimage_ctx *c, uint32_t n_calls, uint64_t seed, u
         uint32_t used = 0, acc = 0;
         CHECK(window_collect(c, r, &used, &acc, log ? log + f.first : nullptr));
         *palette = f.p; *index = f.i; *channel = f.ch; *step = f.st;
-        for (uint32_t j = 0; j < used; j++) snesimage_schedule_next(c->sub_count, c->sub_size, nes, palette, index, channel, step, &method);
+        for (uint32_t j = 0; j < used; j++) ctx_schedule_next(c, nes, palette, index, channel, step, &method);
         done = f.first + used;
         S.calls += used; S.windows++; S.scored += (uint64_t)f.taken * r.stride; S.useful += (uint64_t)used * r.stride; S.accepted += acc;
         if (acc) { // the windows behind it were built for the old palette: the device has voided them, collect and forget them
