@@ -344,7 +344,11 @@ void snesimage_schedule_next_backdrop(uint32_t sub_count, uint32_t sub_size, int
 
 /* Device-side evaluation of the deterministic math used by the kernels, for bit-parity tests:
  * op 0 sin, 1 cos, 2 exp(x<=0), 3 cbrt, 4 atan2(y,x), 5 CIEDE2000(lab x[3i..], lab y[3i..]),
- * 6 sRGB8->Lab (x holds r,g,b as floats, out 3 per item). Host pointers. */
+ * 6 sRGB8->Lab (x holds r,g,b as floats, out 3 per item),
+ * 7 and 8 the two sure "no"s of the CIEDE2000 win test for candidate lab x[3i..] and target lab y[3i..], with the bound
+ * set to the pair's own distance d = CIEDE2000(x, y) computed on the device: 7 the lightness test, 8 the lightness and
+ * a-b plane test (1.0f = "cannot beat d", 0.0f otherwise; a correct test never says 1.0f at a pair's own distance).
+ * Any other op is SNES_ERR_ARG.  Host pointers. */
 int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const float *y, uint32_t n,
                              float *out);
 /* Fault injection for tests: the (n+1)-th workspace allocation made by the library from now on fails as if the

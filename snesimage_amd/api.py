@@ -309,7 +309,7 @@ def debug_math(op, x, y=None, device=0):
     L = _ffi.load()
     x = np.ascontiguousarray(x, np.float32)
     yy = x if y is None else np.ascontiguousarray(y, np.float32)
-    per_in = 3 if op in (5, 6) else 1
+    per_in = 3 if op in (5, 6, 7, 8) else 1
     n = x.size // per_in
     out = np.zeros(n * (3 if op == 6 else 1), np.float32)
     rc = L.snesimage_debug_math(device, op, _p(x, _ffi._f32p), _p(yy, _ffi._f32p), n, _p(out, _ffi._f32p))

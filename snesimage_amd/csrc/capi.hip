@@ -1691,8 +1691,9 @@ void snesimage_debug_poison_alloc(int32_t on) { g_poison_alloc.store(on != 0); }
 
 int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const float *y, uint32_t n, float *out) {
     if (!x || !out || n == 0) return fail(SNES_ERR_ARG, "bad arguments");
+    if (op < 0 || op > 8) return fail(SNES_ERR_ARG, "debug_math: op must be 0 .. 8"); // (the kernel's default branch is op 6: 3 floats per item)
     HIPCHK(hipSetDevice(device));
-    const uint32_t per_in = (op == 5 || op == 6) ? 3 : 1, per_out = (op == 6) ? 3 : 1;
+    const uint32_t per_in = (op >= 5 && op <= 8) ? 3 : 1, per_out = (op == 6) ? 3 : 1;
     float *dx = nullptr, *dy = nullptr, *dout = nullptr, *dlut = nullptr;
     HIPCHK(hipMalloc(&dx, sizeof(float) * n * per_in));
     HIPCHK(hipMalloc(&dy, sizeof(float) * n * per_in));

@@ -867,6 +867,12 @@ __global__ void k_debug_math(int op, const float *__restrict__ x, const float *_
     case 3: out[i] = d_cbrtf(x[i]); break;
     case 4: out[i] = d_atan2f(y[i], x[i]); break;
     case 5: { Lab a{x[3 * i], x[3 * i + 1], x[3 * i + 2]}, b{y[3 * i], y[3 * i + 1], y[3 * i + 2]}; out[i] = ciede2000(a, b); break; }
+    case 7: case 8: { // the two sure "no"s of color.hpp with the bound set to the pair's own distance: a "yes" here is a wrong map
+        Lab a{x[3 * i], x[3 * i + 1], x[3 * i + 2]}, b{y[3 * i], y[3 * i + 1], y[3 * i + 2]};
+        const float d = ciede2000(a, b);
+        const bool no = op == 7 ? ciede2000_cannot_beat(a, b, d) : ciede2000_cannot_beat_ab(a, sqrtf(a.a * a.a + a.b * a.b), b, d);
+        out[i] = no ? 1.0f : 0.0f; break;
+    }
     default: {
         Lab l = linear_to_lab(lab_eotf[(int)x[3 * i] & 255], lab_eotf[(int)x[3 * i + 1] & 255], lab_eotf[(int)x[3 * i + 2] & 255]);
         out[3 * i] = l.l; out[3 * i + 1] = l.a; out[3 * i + 2] = l.b; break;
