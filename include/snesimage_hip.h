@@ -320,6 +320,41 @@ int32_t snesimage_get_palette_u16(snesimage_ctx *ctx, uint16_t *out /*count*size
  * palette_map as snesimage_set_palette_rgb5 does: call snesimage_optimize() before reading the map or the error. */
 int32_t snesimage_get_backdrop_rgb5(snesimage_ctx *ctx, uint8_t *out /*3*/);
 int32_t snesimage_set_backdrop_rgb5(snesimage_ctx *ctx, const uint8_t *in /*3*/);
+/* NOT a reference mode: ordered dithering.  The reference's only dithering is Floyd-Steinberg error diffusion (SNES_DITHER,
+ * lib.rs:425-501): a serial pass per candidate, and unstable from frame to frame.  An ORDERED-DITHER TABLE is n*n offsets
+ * (n = 2, 4, 8 or 16; int8_t, row-major, indexed [y % n][x % n]; any values: a Bayer matrix, a blue-noise tile) added to the
+ * picture before the nearest-colour choice.  With a table set the context keeps a TARGET IMAGE T beside the original:
+ * T.c = clamp(orig.c + d[y % n][x % n], 0, 255) for c = r, g, b (one offset for the three channels), T.a = orig.a — the
+ * clamp of lib.rs:773-778 on an integer.  Everything in integers, so every result stays bit-exact.
+ *   - T replaces the original wherever the nearest-colour choice of lib.rs:762-795 is made: snesimage_optimize(), the
+ *     candidates' remap in snesimage_score_candidates(_device), snesimage_remap_candidates_device, the steps, windows, batches,
+ *     sets and groups, the costs of snesimage_reassign_tiles and the tile moves; with SNES_PERCEPTUAL the distances are taken
+ *     from Lab(T);
+ *   - the original stays what error() compares with (lib.rs:503-548: the optimizer sees the dithering when it scores a
+ *     palette, TODO.md:21-26), what both k-means initialisers cluster (their closing optimize() sees T), what the backdrop's
+ *     initial mean is taken from, and what as_rgba's alpha and the JSON's transparency rule read;
+ *   - a pixel's target depends on no other pixel: a context with a table takes every path of a context without SNES_DITHER
+ *     (the group-sparse scorer, slot windows, duplicate sharing, batches, sets, groups, tile moves, the backdrop: B is one
+ *     more entry in the choice against T);
+ *   - without a table T is the original itself (the same buffer) and the context issues exactly the launches it always did;
+ *     an all-zero table gives T == orig value for value.
+ * snesimage_set_ordered_dither: n = 0 (offsets may be NULL) switches the table off.  It invalidates what
+ * snesimage_set_palette_rgb5 invalidates — call snesimage_optimize() before reading the map or the error — and what the slot
+ * windows and the tile moves keep per image; the source side of error() stays valid.  Refusals: SNES_ERR_ARG for a null
+ * context, n outside {0, 2, 4, 8, 16} or a null table with n > 0; SNES_ERR_UNSUPPORTED for n > 0 on a SNES_DITHER context (the
+ * two are alternatives); SNES_ERR_STATE between the phases of a split-phase step or window and on a context lent to a batch,
+ * group or set.  snesimage_batch_create, snesimage_group_create and snesimage_shared_create refuse members whose tables
+ * differ (SNES_ERR_ARG), as they refuse differing flags.  The JSON does not record the table.
+ * snesimage_get_ordered_dither: the table (256 bytes, zeros behind the n*n offsets) and *n (0: none).
+ * snesimage_get_target_rgba: T as w*h*4 bytes (the original while no table is set).
+ * snesimage_bayer_offsets (host helper): the Bayer table of side n and amplitude A in 1..255 — M_1 = [0],
+ * M_2n = [[4M, 4M+2], [4M+3, 4M+1]]; num = A*(2*M + 1 - n*n), den = 2*n*n, d = sign(num) * ((2*|num| + den) / (2*den)) in
+ * integer division: A*((M + 1/2)/(n*n) - 1/2) rounded half away from zero.  Every such table sums to 0; (2, 64) is
+ * [-24, 8, 24, -8].  Any other n or A writes nothing. */
+int32_t snesimage_set_ordered_dither(snesimage_ctx *ctx, const int8_t *offsets /* n*n */, uint32_t n);
+int32_t snesimage_get_ordered_dither(snesimage_ctx *ctx, int8_t *out /* 256 */, uint32_t *n);
+int32_t snesimage_get_target_rgba(snesimage_ctx *ctx, uint8_t *out /* w*h*4: T */);
+void    snesimage_bayer_offsets(uint32_t n, uint32_t amplitude, int8_t *out /* n*n */);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);

@@ -5,5 +5,5 @@ package is the thin Python host side used by the tests and the benchmark.  Impor
 loads the library and fails loudly when it has not been built — there is no CPU fallback.
 """
 from .api import (BACKDROP, DITHER, METHOD_CHANNEL, METHOD_NES, METHOD_RANDOM, NES, PERCEPTUAL, OptimizedImage,  # noqa: F401
-                  SnesImageError, debug_math, random_candidates, schedule)
+                  SnesImageError, bayer_offsets, debug_math, random_candidates, schedule)
 from .shared import SharedPalette  # noqa: F401,E402

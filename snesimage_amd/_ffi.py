@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libsnesimage_hip.so")
 
 _u8p = C.POINTER(C.c_uint8)
+_i8p = C.POINTER(C.c_int8)
 _u16p = C.POINTER(C.c_uint16)
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
@@ -104,6 +105,10 @@ SIGNATURES = [
     ("snesimage_get_palette_u16", C.c_int32, [C.c_void_p, _u16p]),
     ("snesimage_get_backdrop_rgb5", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_backdrop_rgb5", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_set_ordered_dither", C.c_int32, [C.c_void_p, _i8p, C.c_uint32]),
+    ("snesimage_get_ordered_dither", C.c_int32, [C.c_void_p, _i8p, _u32p]),
+    ("snesimage_get_target_rgba", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_bayer_offsets", None, [C.c_uint32, C.c_uint32, _i8p]),
     ("snesimage_get_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_as_rgba", C.c_int32, [C.c_void_p, _u8p]),

@@ -32,6 +32,31 @@ def random_candidates(seed, step_id, n):
     return out
 
 
+def bayer_offsets(n, amplitude=32):
+    """The Bayer ordered-dither table of side n (2, 4, 8 or 16) and amplitude 1..255: (n, n) int8, summing to 0
+    (include/snesimage_hip.h: snesimage_bayer_offsets)."""
+    n, amplitude = int(n), int(amplitude)
+    if n not in (2, 4, 8, 16) or not 1 <= amplitude <= 255:
+        raise ValueError("bayer_offsets: n must be 2, 4, 8 or 16 and the amplitude in 1..255")
+    out = np.zeros((n, n), np.int8)
+    _ffi.load().snesimage_bayer_offsets(n, amplitude, _p(out, _ffi._i8p))
+    return out
+
+
+def _ordered_table(table):
+    """An ordered-dither table as the library takes it: contiguous (n, n) int8, or None."""
+    if table is None:
+        return None
+    t = np.asarray(table)
+    if t.ndim == 1 and t.size in (4, 16, 64, 256):
+        t = t.reshape(int(round(t.size ** 0.5)), -1)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] not in (2, 4, 8, 16):
+        raise ValueError("an ordered-dither table is (n, n) with n = 2, 4, 8 or 16")
+    if t.min() < -128 or t.max() > 127:
+        raise ValueError("ordered-dither offsets are int8")
+    return np.ascontiguousarray(t, np.int8)
+
+
 def schedule(sub_count, sub_size, n_calls, nes=False, backdrop=False):
     """Replay the slot scheduler of lib.rs:881-933: [(method, palette, index, channel, step)].
     backdrop: the schedule of a backdrop context — every sweep ends with the backdrop slot (sub_count, 0)."""
@@ -289,6 +314,30 @@ class OptimizedImage:
     def palette_map(self, v):
         v = np.ascontiguousarray(v, np.uint8).reshape(self.h, self.w)
         self._chk(self._L.snesimage_set_palette_map(self._c, _p(v, _ffi._u8p)))
+
+    def set_ordered_dither(self, table):
+        """Ordered dithering (not in the reference): `table` is (n, n) int8 offsets, n = 2, 4, 8 or 16 — `bayer_offsets(n, A)`
+        or any other threshold tile — added to the picture before the nearest-colour choice; None switches it off.
+        Invalidates palette_map as setting `palette` does: call optimize() before reading the map or the error."""
+        t = _ordered_table(table)
+        if t is None:
+            self._chk(self._L.snesimage_set_ordered_dither(self._c, None, 0))
+        else:
+            self._chk(self._L.snesimage_set_ordered_dither(self._c, _p(t, _ffi._i8p), t.shape[0]))
+
+    @property
+    def ordered_dither(self):
+        """The ordered-dither table in force, (n, n) int8, or None."""
+        out = np.zeros(256, np.int8)
+        n = C.c_uint32(0)
+        self._chk(self._L.snesimage_get_ordered_dither(self._c, _p(out, _ffi._i8p), C.byref(n)))
+        return out[:n.value * n.value].reshape(n.value, n.value).copy() if n.value else None
+
+    def target_rgba(self):
+        """The image the nearest-colour choice is made against: the original plus the table's offsets, clamped; alpha kept."""
+        out = np.zeros((self.h, self.w, 4), np.uint8)
+        self._chk(self._L.snesimage_get_target_rgba(self._c, _p(out, _ffi._u8p)))
+        return out
 
     def as_rgba(self):  # lib.rs:550
         out = np.zeros((self.h, self.w, 4), np.uint8)

@@ -23,8 +23,8 @@ int32_t batch_quiesce(snesimage_batch *b) {
 
 snes::PrepParams make_prep(snesimage_ctx *c, int mode, int sp, int si) {
     snes::PrepParams P{};
-    P.orig = c->d_orig; P.tile_pal = c->d_tile_pal; P.pal_rgb8 = c->d_pal_rgb8; P.map = c->d_map; P.pack = c->d_pack; P.packT = c->d_packT; P.packC4 = c->d_packC4; P.packR4 = c->d_packR4;
-    P.subC4 = c->d_subC4; P.subR4 = c->d_subR4; P.labpx = c->d_labpx; P.pal_lab = c->d_pal_lab;
+    P.orig = c->d_target; P.tile_pal = c->d_tile_pal; P.pal_rgb8 = c->d_pal_rgb8; P.map = c->d_map; P.pack = c->d_pack; P.packT = c->d_packT; P.packC4 = c->d_packC4; P.packR4 = c->d_packR4;
+    P.subC4 = c->d_subC4; P.subR4 = c->d_subR4; P.labpx = c->d_labpx_t; P.pal_lab = c->d_pal_lab;
     P.W = (int)c->W; P.H = (int)c->H; P.sub_size = (int)c->sub_size; P.ncol = c->ncol; P.mode = mode; P.sp = sp; P.si = si; P.perceptual = c->perceptual ? 1 : 0;
     return P;
 }
@@ -208,6 +208,7 @@ int32_t snesimage_batch_create(snesimage_ctx **ctxs, uint32_t n, snesimage_batch
         if (c->perceptual != c0->perceptual) return fail(SNES_ERR_ARG, "contexts of a batch must share their flags");
         if (!c->sp.enabled || (c->dither && c->sub_size == 1)) return fail(SNES_ERR_UNSUPPORTED, "batched calls cover the group-sparse path (not with SNES_SPARSE=0), and with --dither subpalettes of two entries and more");
         if (c->dither != c0->dither) return fail(SNES_ERR_ARG, "contexts of a batch must share their flags");
+        if (!ordered_tables_equal(c, c0)) return fail(SNES_ERR_ARG, "contexts of a batch must share their ordered-dither table");
     }
     std::unique_ptr<snesimage_batch> b(new snesimage_batch());
     b->device = c0->device;

@@ -138,6 +138,12 @@ struct snesimage_ctx {
     uint32_t *d_pal_rgb8 = nullptr; float *d_pal_lin = nullptr, *d_pal_xyb = nullptr, *d_pal_lab = nullptr;
     float *d_lin0 = nullptr, *d_img1 = nullptr, *d_img1T = nullptr, *d_mu1 = nullptr, *d_sd1 = nullptr;
     float *d_labpx = nullptr, *d_labpxT = nullptr;
+    // Ordered dithering: while a table is set, everything that is the nearest-colour choice (the pack, the contested
+    // list, the remap's Lab plane, the tile costs) reads the target image T = clamp(orig + d[y % n][x % n]) and its Lab plane;
+    // without one these alias d_orig / d_labpx / d_labpxT and nothing changes.  The source side of error(), the k-means
+    // initialisers, as_rgba and the JSON keep reading d_orig.  The *_own buffers exist only while a table is set.
+    uint8_t *d_target = nullptr, *d_target_own = nullptr; float *d_labpx_t = nullptr, *d_labpxT_t = nullptr, *d_labpx_t_own = nullptr, *d_labpxT_t_own = nullptr;
+    uint32_t od_n = 0; int8_t od_tab[256] = {}; // the table: od_n * od_n offsets, row-major; od_n == 0: none
     // per-chunk workspace
     float *d_work = nullptr, *d_cand_tab = nullptr, *d_cand_lab = nullptr;
     double *d_part = nullptr;
@@ -359,8 +365,8 @@ int32_t run_prep(snesimage_ctx *c, int mode, int sp, int si) {
     CHECK(ensure_tables(c));
     if (c->perceptual) CHECK(ensure_source(c));
     PrepParams P{};
-    P.orig = c->d_orig; P.tile_pal = c->d_tile_pal; P.pal_rgb8 = c->d_pal_rgb8; P.map = c->d_map; P.pack = c->d_pack; P.packT = c->d_packT; P.packC4 = c->d_packC4; P.packR4 = c->d_packR4; P.subC4 = c->d_subC4; P.subR4 = c->d_subR4;
-    P.labpx = c->d_labpx; P.pal_lab = c->d_pal_lab;
+    P.orig = c->d_target; P.tile_pal = c->d_tile_pal; P.pal_rgb8 = c->d_pal_rgb8; P.map = c->d_map; P.pack = c->d_pack; P.packT = c->d_packT; P.packC4 = c->d_packC4; P.packR4 = c->d_packR4; P.subC4 = c->d_subC4; P.subR4 = c->d_subR4;
+    P.labpx = c->d_labpx_t; P.pal_lab = c->d_pal_lab;
     P.W = (int)c->W; P.H = (int)c->H; P.sub_size = (int)c->sub_size; P.ncol = c->ncol; P.mode = mode; P.sp = sp; P.si = si; P.perceptual = c->perceptual ? 1 : 0;
     c->sp.counters_cleared = false;
     if (mode == 2 && c->sp.plist_count) { // the contested-pixel count of the slot
@@ -389,7 +395,7 @@ int32_t score_stages(snesimage_ctx *c, const DenseView &V, uint32_t nc, double *
     const Geom &G = c->G;
     const int npairs = (int)nc * 3;
     if (G.nscales > 1) {
-        DownParams D{}; D.G = G; D.pack = V.pack; D.pal_lin = c->d_pal_lin; D.cand_tab = V.cand_tab; D.cand_lab = V.cand_lab; D.labpx = c->d_labpx;
+        DownParams D{}; D.G = G; D.pack = V.pack; D.pal_lin = c->d_pal_lin; D.cand_tab = V.cand_tab; D.cand_lab = V.cand_lab; D.labpx = c->d_labpx_t;
         D.work = V.work; D.ncol = c->ncol; D.perceptual = V.perceptual ? 1 : 0; D.use_maps = V.use_maps ? 1 : 0; D.fast_mask = c->fast_mask & ~1; D.maps = V.maps; D.tile_pal = V.tile_pal; D.sub_size = (int)c->sub_size;
         hipLaunchKernelGGL(k_downscale_chain<true>, dim3(down_grid(G), nc), dim3(256), 0, c->stream, D);
     }
@@ -413,7 +419,7 @@ int32_t score_stages(snesimage_ctx *c, const DenseView &V, uint32_t nc, double *
             else hipLaunchKernelGGL((k_hpass_fast<false>), grid, dim3(64), 0, c->stream, F);
         } else {
             HParams Hp{}; Hp.G = G; Hp.K = c->K; Hp.s = s; Hp.npairs = npairs; Hp.ncol = c->ncol; Hp.perceptual = V.perceptual ? 1 : 0; Hp.use_maps = V.use_maps ? 1 : 0; Hp.sub_size = (int)c->sub_size;
-            Hp.packT = V.packT; Hp.pal_xyb = c->d_pal_xyb; Hp.cand_tab = V.cand_tab; Hp.cand_lab = V.cand_lab; Hp.labpxT = c->d_labpxT;
+            Hp.packT = V.packT; Hp.pal_xyb = c->d_pal_xyb; Hp.cand_tab = V.cand_tab; Hp.cand_lab = V.cand_lab; Hp.labpxT = c->d_labpxT_t;
             Hp.in1T = c->d_img1T + G.src_off[s]; Hp.in2T = nullptr; Hp.work = V.work; Hp.mapsT = V.mapsT; Hp.tile_pal = V.tile_pal;
             int ppw = 256 / G.sh[s];
             dim3 grid((npairs + ppw - 1) / ppw);
@@ -433,7 +439,7 @@ int32_t score_stages(snesimage_ctx *c, const DenseView &V, uint32_t nc, double *
             else hipLaunchKernelGGL((k_vpass_fast<false>), grid, dim3(256), 0, c->stream, F);
         } else {
             VParams Vp{}; Vp.G = G; Vp.K = c->K; Vp.s = s; Vp.npairs = npairs; Vp.ncol = c->ncol; Vp.perceptual = V.perceptual ? 1 : 0; Vp.use_maps = V.use_maps ? 1 : 0; Vp.sub_size = (int)c->sub_size;
-            Vp.pack = V.pack; Vp.pal_xyb = c->d_pal_xyb; Vp.cand_tab = V.cand_tab; Vp.cand_lab = V.cand_lab; Vp.labpx = c->d_labpx;
+            Vp.pack = V.pack; Vp.pal_xyb = c->d_pal_xyb; Vp.cand_tab = V.cand_tab; Vp.cand_lab = V.cand_lab; Vp.labpx = c->d_labpx_t;
             Vp.mu1 = c->d_mu1 + G.src_off[s]; Vp.sd1 = c->d_sd1 + G.src_off[s]; Vp.a1 = c->d_a1 + G.src_off[s]; Vp.r1 = c->d_r1 + G.src_off[s]; Vp.work = V.work; Vp.part = V.part;
             Vp.maps = V.maps; Vp.tile_pal = V.tile_pal;
             if (s == 0) {
@@ -480,7 +486,7 @@ int32_t score_chunk(snesimage_ctx *c, const uint8_t *d_rgb5, uint32_t nc, double
                            reinterpret_cast<uint32_t *>(c->d_mapsR4), (c->fast_mask & 1) ? (uint32_t *)nullptr : reinterpret_cast<uint32_t *>(c->d_mapsT));
         if (d_maps_out) HIPCHK(hipMemcpyAsync(d_maps_out, c->d_maps, c->npx * (size_t)nc, hipMemcpyDeviceToDevice, c->stream));
     } else if (d_maps_out) {
-        MapsParams M{}; M.pack = c->d_pack; M.cand_tab = c->d_cand_tab; M.cand_lab = c->d_cand_lab; M.labpx = c->d_labpx; M.maps = d_maps_out;
+        MapsParams M{}; M.pack = c->d_pack; M.cand_tab = c->d_cand_tab; M.cand_lab = c->d_cand_lab; M.labpx = c->d_labpx_t; M.maps = d_maps_out;
         M.npx = (int)c->npx; M.ncol = c->ncol; M.sub_size = (int)c->sub_size; M.si = si < 0 ? 0 : si; M.ncand = (int)nc; M.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_candidate_maps, dim3((unsigned)((c->npx + 255) / 256), nc), dim3(256), 0, c->stream, M);
     }
@@ -597,7 +603,7 @@ SparseParams sparse_params(snesimage_ctx *c, uint32_t lane) {
     P.G = c->G; P.S = sp.S; P.K = c->K; P.ncol = c->ncol; P.base = (int)(sp.lanes * sp.cap);
     P.pack = c->d_pack; P.packC4 = c->d_packC4; P.packR4 = c->d_packR4; P.plist = sp.plist; P.plist_count = sp.plist_count;
     P.pal_lin = c->d_pal_lin; P.pal_xyb = c->d_pal_xyb; P.cand_tab = sp.cand_tab;
-    P.perceptual = c->perceptual ? 1 : 0; P.labpx = c->d_labpx; P.cand_lab = sp.cand_lab; P.bitmap = sp.bitmap;
+    P.perceptual = c->perceptual ? 1 : 0; P.labpx = c->d_labpx_t; P.cand_lab = sp.cand_lab; P.bitmap = sp.bitmap;
     P.img1C4 = c->d_img1C4; P.mu1R4 = c->d_mu1R4; P.sd1R4 = c->d_sd1R4; P.a1R4 = c->d_a1R4; P.r1R4 = c->d_r1R4;
     P.store = sp.store; P.meta = sp.meta;
     P.items = sp.items + (size_t)lane * sp.item_stride * kItemLists; P.item_count = sp.item_count + (size_t)lane * kItemLists; P.item_stride = sp.item_stride; // lane == nlanes: B
@@ -1001,6 +1007,8 @@ struct SlotScope {
     }
     ~SlotScope() { c->tied_call = saved; }
 };
+// the members of a batch, a set or a group are scored by shared launches and summed or compared: one ordered-dither table for all
+bool ordered_tables_equal(const snesimage_ctx *a, const snesimage_ctx *b) { return a->od_n == b->od_n && (a->od_n == 0 || memcmp(a->od_tab, b->od_tab, (size_t)a->od_n * a->od_n) == 0); }
 const char *kBackdropRefused = "SNES_BACKDROP contexts are not supported here: the backdrop schedule is not carried through batches, groups, shared-palette sets and split-phase slot windows";
 
 int32_t batch_quiesce(struct snesimage_batch *b);
@@ -1103,7 +1111,7 @@ const char *snesimage_last_error(void) { return g_err.c_str(); }
 #ifndef SNES_SRC_HASH
 #define SNES_SRC_HASH "unknown"
 #endif
-const char *snesimage_version(void) { return "snesimage_hip 0.2.0 (gfx950) src:" SNES_SRC_HASH; } // src: hash of the library's sources (csrc/Makefile)
+const char *snesimage_version(void) { return "snesimage_hip 0.3.0 (gfx950) src:" SNES_SRC_HASH; } // src: hash of the library's sources (csrc/Makefile)
 
 int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t sub_count, uint32_t sub_size, uint32_t flags, int32_t device, snesimage_ctx **out) {
     if (!rgba || !out) return fail(SNES_ERR_ARG, "null pointer");
@@ -1209,6 +1217,7 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
         HIPCHK(hipMalloc(&c->d_mu1R4, c->src_floats * 4));
         HIPCHK(hipMalloc(&c->d_sd1R4, c->src_floats * 4));
         if (c->perceptual) { HIPCHK(hipMalloc(&c->d_labpx, c->npx * 3 * 4)); HIPCHK(hipMalloc(&c->d_labpxT, c->npx * 3 * 4)); }
+        c->d_target = c->d_orig; c->d_labpx_t = c->d_labpx; c->d_labpxT_t = c->d_labpxT; // no ordered-dither table: the target is the original
         HIPCHK(hipMalloc(&c->d_inc_err, sizeof(double)));
         HIPCHK(hipMalloc(&c->d_scratch_err, sizeof(double)));
         HIPCHK(hipMalloc(&c->d_last, sizeof(StepResult)));
@@ -1259,6 +1268,7 @@ void snesimage_destroy(snesimage_ctx *c) {
     dfree(c->d_orig); dfree(c->d_tile_pal); dfree(c->d_colors); dfree(c->d_map); dfree(c->d_pack); dfree(c->d_packT); dfree(c->d_eotf); dfree(c->d_lab_eotf);
     dfree(c->d_pal_rgb8); dfree(c->d_pal_lin); dfree(c->d_pal_xyb); dfree(c->d_pal_lab); dfree(c->d_lin0); dfree(c->d_img1); dfree(c->d_img1T); dfree(c->d_mu1); dfree(c->d_sd1);
     dfree(c->d_bestmaps_all); dfree(c->d_bestrecs_all); dfree(c->d_skip); dfree(c->d_rplist); dfree(c->d_rcount); dfree(c->d_rtab); dfree(c->d_rlab); dfree(c->d_tile_cost); dfree(c->d_tile_any); dfree(c->d_tile_moved);
+    dfree(c->d_target_own); dfree(c->d_labpx_t_own); dfree(c->d_labpxT_t_own);
     dfree(c->d_labpx); dfree(c->d_labpxT); dfree(c->d_work); dfree(c->d_cand_tab); dfree(c->d_cand_lab); dfree(c->d_part); dfree(c->d_maps); dfree(c->d_mapsT);
     dfree(c->d_cand); dfree(c->d_cand_sel); dfree(c->d_errs); dfree(c->d_errs_sel); dfree(c->d_inc_err); dfree(c->d_last); dfree(c->d_scratch_err); dfree(c->d_dummy_cand);
     for (auto &L : c->extra) { if (L.stream) (void)hipStreamSynchronize(L.stream); dfree(L.d_mapsC4); dfree(L.d_mapsR4); dfree(L.d_work); dfree(L.d_cand_tab); dfree(L.d_cand_lab); dfree(L.d_part); dfree(L.d_maps); dfree(L.d_mapsT); if (L.done) (void)hipEventDestroy(L.done); if (L.stream) (void)hipStreamDestroy(L.stream); }
@@ -1370,7 +1380,7 @@ int32_t snesimage_remap_candidates_device(snesimage_ctx *c, uint32_t palette, ui
             Dp.W = (int)c->W; Dp.H = (int)c->H; Dp.sub_size = (int)c->sub_size; Dp.ncol = c->ncol; Dp.slot_ci = slot_ci; Dp.perceptual = c->perceptual ? 1 : 0;
             launch_dither(c, Dp, nc);
         } else {
-            MapsParams M{}; M.pack = c->d_pack; M.cand_tab = c->d_rtab; M.cand_lab = c->d_rlab; M.labpx = c->d_labpx; M.maps = maps;
+            MapsParams M{}; M.pack = c->d_pack; M.cand_tab = c->d_rtab; M.cand_lab = c->d_rlab; M.labpx = c->d_labpx_t; M.maps = maps;
             M.npx = (int)c->npx; M.ncol = c->ncol; M.sub_size = (int)c->sub_size; M.si = (int)index; M.ncand = (int)nc; M.perceptual = c->perceptual ? 1 : 0;
             const dim3 grid((unsigned)((c->npx / 4 + 255) / 256), (nc + kRemapCands - 1) / kRemapCands);
             if (c->perceptual) { // B's map for everyone, then the CIEDE2000 win tests over the slot's contested pixels only
@@ -1651,7 +1661,7 @@ int32_t snesimage_reassign_tiles(snesimage_ctx *c, uint32_t *moved_out) {
     }
     unsigned int moved = 0;
     HIPCHK(hipMemsetAsync(c->d_tile_moved, 0, sizeof(unsigned int), c->stream));
-    hipLaunchKernelGGL(k_tile_costs, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_orig, c->d_pal_rgb8, c->d_pal_lab, c->d_labpx, (int)c->W, (int)c->H, (int)c->sub_count,
+    hipLaunchKernelGGL(k_tile_costs, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_target, c->d_pal_rgb8, c->d_pal_lab, c->d_labpx_t, (int)c->W, (int)c->H, (int)c->sub_count,
                        (int)c->sub_size, c->perceptual ? 1 : 0, c->d_tile_cost, c->d_tile_any);
     hipLaunchKernelGGL(k_tile_move, dim3((ntile + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost, c->d_tile_any, ntile, (int)c->sub_count, c->d_tile_pal, c->d_tile_moved);
     HIPCHK(hipGetLastError());
@@ -1719,3 +1729,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "shared_window_host.inc"
 #include "group_host.inc"
 #include "tile_host.inc"
+#include "ordered_host.inc"

@@ -14,6 +14,9 @@
 // SNES_BACKDROP), optimized like any entry; --backdrop-fixed R,G,B (5-bit) keeps it at the given colour.
 // --share SOURCE=TARGET (repeatable) optimizes one palette for the main image and every such image together (a set,
 // include/snesimage_hip.h): the frames of an animation share one CGRAM on the console.
+// --ordered-dither N [--dither-amplitude A] adds the N x N Bayer pattern of amplitude A to the picture before the nearest-colour
+// choice (include/snesimage_hip.h: snesimage_set_ordered_dither): the alternative to -d that keeps animation frames steady.
+// The JSON does not record it: a --resume run names the option again.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -62,6 +65,11 @@ void usage() {
             "                           it is optimized like any entry and written to slot 0 of every palette row (needs -s <= 15,\n"
             "                           c*(s+1) <= 253; not with --share or --devices)\n"
             "      --backdrop-fixed <R,G,B>  the same with the backdrop colour given (5-bit channels) and never changed\n"
+            "      --ordered-dither <N> ordered dithering with the N x N Bayer pattern (N = 2, 4, 8 or 16) instead of -d: a fixed pattern,\n"
+            "                           so frames of an animation do not shimmer against each other; works with every other option\n"
+            "                           but -d; the output does not record it: name it again with --resume\n"
+            "      --dither-amplitude <A>  peak-to-peak strength of that pattern in 8-bit steps, 1..255 [default: 32, four BGR555 steps:\n"
+            "                           a choice, not a measurement]\n"
             "      --calls <N>          optimizer calls to run [default: 0]\n      --candidates <N>     random candidates per call [default: 64]\n"
             "      --window <N>         optimizer calls scored per launch set (0 = adaptive, 1 = call by call; same result) [default: 0]\n"
             "      --seed <N>           candidate RNG seed [default: 1]\n      --device <N>         HIP device [default: 0]\n"
@@ -162,6 +170,7 @@ int main(int argc, char **argv) {
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
+    uint32_t ordered_n = 0, ordered_amp = 32; bool ordered_given = false, amp_given = false; std::string ordered_arg, amp_arg;
     bool backdrop = false, backdrop_fixed = false; uint8_t backdrop_rgb[3] = {0, 0, 0}; std::string backdrop_arg;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -173,6 +182,8 @@ int main(int argc, char **argv) {
         else if (a == "--nes") flags |= SNES_NES;
         else if (a == "--backdrop") backdrop = true;
         else if (a == "--backdrop-fixed") { backdrop_fixed = true; backdrop_arg = need("--backdrop-fixed"); }
+        else if (a == "--ordered-dither") { ordered_given = true; ordered_arg = need("--ordered-dither"); }
+        else if (a == "--dither-amplitude") { amp_given = true; amp_arg = need("--dither-amplitude"); }
         else if (a == "--calls") calls = (uint32_t)strtoul(need("--calls"), nullptr, 10);
         else if (a == "--candidates") ncand = (uint32_t)strtoul(need("--candidates"), nullptr, 10);
         else if (a == "--seed") seed = strtoull(need("--seed"), nullptr, 0);
@@ -206,6 +217,27 @@ int main(int argc, char **argv) {
         const char *bad = !resume_file.empty() ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--share <SOURCE=TARGET>' cannot be used with %s\n", bad); return 2; }
     }
+    if (ordered_given || amp_given) { // said before any device is touched
+        char *end = nullptr;
+        if (!ordered_given) { fprintf(stderr, "error: '--dither-amplitude <A>' needs '--ordered-dither <N>'\n"); return 2; }
+        const unsigned long n = strtoul(ordered_arg.c_str(), &end, 10);
+        if (ordered_arg.empty() || *end || (n != 2 && n != 4 && n != 8 && n != 16)) { fprintf(stderr, "error: invalid value '%s' for '--ordered-dither <N>': expected 2, 4, 8 or 16\n", ordered_arg.c_str()); return 2; }
+        ordered_n = (uint32_t)n;
+        if (amp_given) {
+            const unsigned long amp = strtoul(amp_arg.c_str(), &end, 10);
+            if (amp_arg.empty() || *end || amp < 1 || amp > 255) { fprintf(stderr, "error: invalid value '%s' for '--dither-amplitude <A>': expected 1..255\n", amp_arg.c_str()); return 2; }
+            ordered_amp = (uint32_t)amp;
+        }
+        if (flags & SNES_DITHER) { fprintf(stderr, "error: the argument '--ordered-dither <N>' cannot be used with '--dither': they are alternatives\n"); return 2; }
+    }
+    int8_t ordered_tab[256] = {};
+    if (ordered_n) snesimage_bayer_offsets(ordered_n, ordered_amp, ordered_tab);
+    // every context of the run gets the table before anything is computed on it (the initialisers end with optimize(), which sees it)
+    auto create = [&](const uint8_t *px, uint32_t cw, uint32_t chh, int dev, snesimage_ctx **out) -> int32_t {
+        int32_t rc = snesimage_create(px, cw, chh, count, size, flags, dev, out);
+        if (rc == 0 && ordered_n) rc = snesimage_set_ordered_dither(*out, ordered_tab, ordered_n);
+        return rc;
+    };
     if (backdrop || backdrop_fixed) { // said before any device is touched
         const char *opt = backdrop_fixed ? "--backdrop-fixed" : "--backdrop";
         if (backdrop_fixed) {
@@ -247,7 +279,8 @@ int main(int argc, char **argv) {
     }
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
-    if (snesimage_create(rgba.data(), w, h, count, size, flags, device, &ctx) != 0) die(snesimage_last_error());
+    if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
+    if (ordered_n) log_info("Ordered dithering: " + std::to_string(ordered_n) + " x " + std::to_string(ordered_n) + " Bayer pattern, amplitude " + std::to_string(ordered_amp));
     if (backdrop_fixed && snesimage_set_backdrop_rgb5(ctx, backdrop_rgb) != 0) die(snesimage_last_error()); // (the initialisers end with optimize(), which sees it)
     // --share: one context per image, every member's storage sized for one call's candidates (about 4.45 MB each), one set
     std::vector<snesimage_ctx *> frames{ctx};
@@ -255,7 +288,7 @@ int main(int argc, char **argv) {
     if (!shares.empty()) {
         for (const auto &other : shared_rgba) {
             snesimage_ctx *m = nullptr;
-            if (snesimage_create(other.data(), w, h, count, size, flags, device, &m) != 0) die(snesimage_last_error());
+            if (create(other.data(), w, h, device, &m) != 0) die(snesimage_last_error());
             frames.push_back(m);
         }
         uint32_t chunk = ncand > 32 ? ncand : 32; // the largest call of the schedule: random (ncand), channel (32) or NES (56)
@@ -314,7 +347,7 @@ int main(int argc, char **argv) {
         if (snesimage_get_tile_palettes(ctx, tp.data()) != 0 || snesimage_get_palette_rgb5(ctx, pal.data()) != 0) die(snesimage_last_error());
         for (size_t d = 1; d < devices.size(); d++) {
             snesimage_ctx *m = nullptr;
-            if (snesimage_create(rgba.data(), w, h, count, size, flags, devices[d], &m) != 0 || snesimage_set_tile_palettes(m, tp.data()) != 0 || snesimage_set_palette_rgb5(m, pal.data()) != 0 ||
+            if (create(rgba.data(), w, h, devices[d], &m) != 0 || snesimage_set_tile_palettes(m, tp.data()) != 0 || snesimage_set_palette_rgb5(m, pal.data()) != 0 ||
                 snesimage_optimize(m) != 0)
                 die(snesimage_last_error());
             members.push_back(m);

@@ -108,6 +108,7 @@ int32_t snesimage_group_create(snesimage_ctx **ctxs, uint32_t n, snesimage_group
         if (c->W != ctxs[0]->W || c->H != ctxs[0]->H || c->sub_count != ctxs[0]->sub_count || c->sub_size != ctxs[0]->sub_size || c->dither != ctxs[0]->dither ||
             c->perceptual != ctxs[0]->perceptual)
             return fail(SNES_ERR_ARG, "contexts of a group must hold the same image geometry, palette geometry and flags");
+        if (!ordered_tables_equal(c, ctxs[0])) return fail(SNES_ERR_ARG, "contexts of a group must share their ordered-dither table");
         for (int d : devs) if (d == c->device) return fail(SNES_ERR_ARG, "a group takes one context per device");
         devs.push_back(c->device);
     }

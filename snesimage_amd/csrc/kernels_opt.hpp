@@ -37,6 +37,38 @@ __global__ __launch_bounds__(256) void k_pixel_lab(const uint8_t *__restrict__ o
     labpxT[3 * pt] = l.l; labpxT[3 * pt + 1] = l.a; labpxT[3 * pt + 2] = l.b;
 }
 
+// Ordered dithering: the target image T = clamp(orig + d[y % n][x % n], 0, 255) on r, g, b, alpha kept — what the
+// nearest-colour choice of lib.rs:762-795 is made against while a table is set.  Four pixels (one uint4) per lane; the table
+// (n * n <= 256 offsets, n a power of two) arrives by value and is staged in LDS.  labpx != nullptr (--perceptual-palettes):
+// Lab(T) in both layouts of k_pixel_lab, through the same functions.  Runs once per table change.
+struct OrderedTable { int8_t d[256]; };
+__global__ __launch_bounds__(256) void k_build_target(const uint8_t *__restrict__ orig, OrderedTable tab, int n, const float *__restrict__ lab_eotf, int W, int H,
+                                                      uint8_t *__restrict__ target, float *__restrict__ labpx, float *__restrict__ labpxT) {
+    __shared__ int s_tab[256];
+    s_tab[threadIdx.x] = threadIdx.x < (unsigned)(n * n) ? (int)tab.d[threadIdx.x] : 0;
+    __syncthreads();
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= W * H / 4) return;
+    const int px0 = 4 * q, x0 = px0 % W, y = px0 / W; // (W is a multiple of 4: the four pixels share a row)
+    const uint4 o4 = reinterpret_cast<const uint4 *>(orig)[q];
+    const uint32_t in[4] = {o4.x, o4.y, o4.z, o4.w};
+    uint32_t out[4];
+    for (int i = 0; i < 4; i++) {
+        const int d = s_tab[(y & (n - 1)) * n + ((x0 + i) & (n - 1))];
+        const int r = min(max((int)(in[i] & 0xff) + d, 0), 255), g = min(max((int)((in[i] >> 8) & 0xff) + d, 0), 255), b = min(max((int)((in[i] >> 16) & 0xff) + d, 0), 255);
+        out[i] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16) | (in[i] & 0xff000000u);
+    }
+    reinterpret_cast<uint4 *>(target)[q] = make_uint4(out[0], out[1], out[2], out[3]);
+    if (!labpx) return;
+    for (int i = 0; i < 4; i++) {
+        const uint32_t o = out[i];
+        Lab l = linear_to_lab(lab_eotf[o & 0xff], lab_eotf[(o >> 8) & 0xff], lab_eotf[(o >> 16) & 0xff]);
+        const size_t px = (size_t)px0 + i, pt = (size_t)(x0 + i) * H + y;
+        labpx[3 * px] = l.l; labpx[3 * px + 1] = l.a; labpx[3 * px + 2] = l.b;
+        labpxT[3 * pt] = l.l; labpxT[3 * pt + 1] = l.a; labpxT[3 * pt + 2] = l.b;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // optimize() with Floyd-Steinberg error diffusion (lib.rs:425-501), one block per candidate.
 // The raster scan's dependency (x-1,y), (x-1..x+1,y-1) leaves the anti-diagonals t = x + 2y free:

@@ -90,7 +90,7 @@ int32_t tile_prepare(snesimage_ctx *c, uint32_t need, const uint8_t **base_map) 
     CHECK(tile_alloc(c, need));
     snesimage_tilework &t = *c->tile;
     PrepParams P{};
-    P.orig = c->d_orig; P.pal_rgb8 = c->d_pal_rgb8; P.pack = t.pack; P.packT = t.packT; P.packC4 = t.packC4; P.packR4 = t.packR4;
+    P.orig = c->d_target; P.pal_rgb8 = c->d_pal_rgb8; P.pack = t.pack; P.packT = t.packT; P.packC4 = t.packC4; P.packR4 = t.packR4;
     P.W = (int)c->W; P.H = (int)c->H; P.sub_size = (int)c->sub_size; P.ncol = c->ncol; P.sp = -1; P.si = -1;
     const dim3 grid((unsigned)((c->npx + 255) / 256));
     if (!t.planes_ready) { // mode 1 over a tile table of zeros: the pack's transparency marker, and subpalette planes of 0 (255 = transparent)
@@ -101,7 +101,7 @@ int32_t tile_prepare(snesimage_ctx *c, uint32_t need, const uint8_t **base_map) 
     *base_map = c->d_map;
     if (!c->dither && !c->map_synced) { // (mode 0 leaves the same transparency marker in the pack)
         P.tile_pal = c->d_tile_pal; P.map = t.basemap; P.mode = 0; P.subC4 = nullptr; P.subR4 = nullptr;
-        P.labpx = c->d_labpx; P.pal_lab = c->d_pal_lab; P.perceptual = c->perceptual ? 1 : 0;
+        P.labpx = c->d_labpx_t; P.pal_lab = c->d_pal_lab; P.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_prep, grid, dim3(256), 0, c->stream, P);
         *base_map = t.basemap;
     }
@@ -132,7 +132,7 @@ int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map,
         else hipLaunchKernelGGL((k_dither_tile<false, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
     } else {
         TileRemapParams R{};
-        R.orig = c->d_orig; R.base_map = base_map; R.tile_pal = c->d_tile_pal; R.pal_rgb8 = c->d_pal_rgb8; R.pal_lab = c->d_pal_lab; R.labpx = c->d_labpx;
+        R.orig = c->d_target; R.base_map = base_map; R.tile_pal = c->d_tile_pal; R.pal_rgb8 = c->d_pal_rgb8; R.pal_lab = c->d_pal_lab; R.labpx = c->d_labpx_t;
         R.tiles = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps; R.W = (int)c->W; R.H = (int)c->H; R.sub_size = (int)c->sub_size; R.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_tile_remap, dim3(nc), dim3(256), 0, st, R);
     }

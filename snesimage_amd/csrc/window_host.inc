@@ -93,7 +93,7 @@ void window_release_child(snesimage_ctx *k) {
     // borrowed from the parent: not ours to free
     k->d_orig = nullptr; k->d_tile_pal = nullptr; k->d_colors = nullptr; k->d_map = nullptr; k->d_eotf = nullptr; k->d_lab_eotf = nullptr;
     k->d_pal_rgb8 = nullptr; k->d_pal_lin = nullptr; k->d_pal_xyb = nullptr; k->d_pal_lab = nullptr; k->d_lin0 = nullptr; k->d_img1 = nullptr; k->d_img1T = nullptr; k->d_mu1 = nullptr; k->d_sd1 = nullptr;
-    k->d_a1 = nullptr; k->d_a1R4 = nullptr; k->d_r1 = nullptr; k->d_r1R4 = nullptr; k->d_img1C4 = nullptr; k->d_mu1R4 = nullptr; k->d_sd1R4 = nullptr; k->d_labpx = nullptr; k->d_labpxT = nullptr;
+    k->d_a1 = nullptr; k->d_a1R4 = nullptr; k->d_r1 = nullptr; k->d_r1R4 = nullptr; k->d_img1C4 = nullptr; k->d_mu1R4 = nullptr; k->d_sd1R4 = nullptr; k->d_labpx = nullptr; k->d_labpxT = nullptr; k->d_target = nullptr; k->d_labpx_t = nullptr; k->d_labpxT_t = nullptr;
     k->d_inc_err = nullptr; k->d_last = nullptr; k->d_scratch_err = nullptr; k->d_dummy_cand = nullptr;
     if (k->pack_borrowed) { k->d_pack = nullptr; k->d_packC4 = nullptr; k->d_packR4 = nullptr; k->d_subC4 = nullptr; k->d_subR4 = nullptr; }
     k->stream = nullptr; k->own_stream = nullptr;
@@ -111,7 +111,7 @@ int32_t window_make_child(snesimage_ctx *c, snesimage_ctx **out) {
     k->sp.enabled = true; k->sp.side = false; k->sp.lpt = c->sp.lpt; k->sp.down1 = c->sp.down1; k->sp.h2q_max = c->sp.h2q_max; k->sp.scan4_max = c->sp.scan4_max; k->sp.vsplit = c->sp.vsplit; k->sp.down_tiles = c->sp.down_tiles; k->sp.tiles_grid = c->sp.tiles_grid; k->sp.h0_min = c->sp.h0_min; k->sp.hgrid = c->sp.hgrid; k->sp.min_n = 1;
     k->d_orig = c->d_orig; k->d_tile_pal = c->d_tile_pal; k->d_colors = c->d_colors; k->d_map = c->d_map; k->d_eotf = c->d_eotf; k->d_lab_eotf = c->d_lab_eotf;
     k->d_pal_rgb8 = c->d_pal_rgb8; k->d_pal_lin = c->d_pal_lin; k->d_pal_xyb = c->d_pal_xyb; k->d_pal_lab = c->d_pal_lab;
-    k->d_img1C4 = c->d_img1C4; k->d_mu1R4 = c->d_mu1R4; k->d_sd1R4 = c->d_sd1R4; k->d_a1R4 = c->d_a1R4; k->d_r1R4 = c->d_r1R4; k->d_labpx = c->d_labpx; k->d_labpxT = c->d_labpxT;
+    k->d_img1C4 = c->d_img1C4; k->d_mu1R4 = c->d_mu1R4; k->d_sd1R4 = c->d_sd1R4; k->d_a1R4 = c->d_a1R4; k->d_r1R4 = c->d_r1R4; k->d_labpx = c->d_labpx; k->d_labpxT = c->d_labpxT; k->d_target = c->d_target; k->d_labpx_t = c->d_labpx_t; k->d_labpxT_t = c->d_labpxT_t; k->od_n = c->od_n; memcpy(k->od_tab, c->od_tab, sizeof k->od_tab);
     k->d_inc_err = c->d_inc_err; k->d_last = c->d_last;
     k->stream = c->stream; // (only sparse_alloc's housekeeping runs on it; the window's launches name their stream themselves)
     k->tables_valid = true; k->src_valid = true;

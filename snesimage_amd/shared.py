@@ -17,9 +17,14 @@ from .api import METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
 class SharedPalette:
     """A set over `images` (OptimizedImage, in member order).  Destroy the set (close) before its members."""
 
-    def __init__(self, images):
+    def __init__(self, images, ordered_dither=None):
+        """ordered_dither: an ordered-dither table (api.bayer_offsets or any (n, n) int8 tile) given to every member before the
+        set is formed; None leaves the members' tables as they are (the library refuses members whose tables differ)."""
         self.images = list(images)
         self._L = _ffi.load()
+        if ordered_dither is not None:
+            for img in self.images:
+                img.set_ordered_dither(ordered_dither)
         arr = (C.c_void_p * len(self.images))(*[img._c for img in self.images])
         h = C.c_void_p()
         self._chk(self._L.snesimage_shared_create(arr if self.images else None, len(self.images), C.byref(h)))

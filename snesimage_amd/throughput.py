@@ -27,10 +27,11 @@ def shard_images(n_images, rank, world):
 
 
 class ImageBatch:
-    """`images`: iterable of (global_index, rgba) pairs, all optimised with the same palette geometry and flags."""
+    """`images`: iterable of (global_index, rgba) pairs, all optimised with the same palette geometry, flags and
+    ordered-dither table (`ordered_dither`: api.bayer_offsets(n, A) or any (n, n) int8 tile; None = none)."""
 
     def __init__(self, images, sub_count, sub_size, device=0, candidates=64, host_threads=8, dither=False,
-                 perceptual=False, nes=False, batched=False, groups=4):
+                 perceptual=False, nes=False, batched=False, groups=4, ordered_dither=None):
         self.sub_count, self.sub_size, self.candidates, self.nes = int(sub_count), int(sub_size), int(candidates), bool(nes)
         self.batched, self._batches, self.groups = bool(batched), [], max(1, int(groups))
         self.ids = []
@@ -39,6 +40,8 @@ class ImageBatch:
             self.ids.append(int(gid))
             img = api.OptimizedImage(rgba, sub_count, sub_size, dither=dither, perceptual=perceptual, nes=nes, device=device)
             img.set_chunk(max(self.candidates, 64))  # workspace for one call's candidates, not the library's 1,024-candidate default
+            if ordered_dither is not None:  # every image gets the table before the initialisers (their closing optimize() sees it) and before a batch forms
+                img.set_ordered_dither(ordered_dither)
             self.images.append(img)
         self.host_threads = max(1, min(int(host_threads), len(self.images)))
         self.calls_done = 0
