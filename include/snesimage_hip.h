@@ -310,6 +310,70 @@ int32_t snesimage_tile_sweep(snesimage_ctx *ctx, uint32_t first_tile, uint32_t n
 int32_t snesimage_shared_tile_sweep(snesimage_shared *set, uint32_t first_tile, uint32_t n_tiles, uint32_t window,
                                     snesimage_tile_result *log, snesimage_run_stats *stats);
 
+/* The character budget — NOT a reference method.  The JSON gives every tile its own 64 indices; the SNES has 64 KB of VRAM for
+ * all layers, and a 256 x 224 picture of 896 distinct 4bpp characters takes 28 KB of it.  These calls count the distinct
+ * characters of the result, merge tiles until at most N are left — each merge chosen by error() itself — and write the tilemap
+ * the merges imply.  Off unless called; no other entry point changes.  All quantities are integers except the objective.
+ * Tiles are numbered as tile_palettes is indexed (t = ty * 32 + tx, ty < h/8; ntile = 32 * h/8).
+ *   CHARACTER of tile t: 64 bytes, row-major inside the tile, the values snesimage_as_json writes into `tiles`: 0 where the
+ *     source alpha is 0; 0 where, in a backdrop context, the map value is the backdrop; map + 1 otherwise.
+ *   FLIP f in 0..3, bit 0 horizontal, bit 1 vertical (bits 14 and 15 of the tilemap word):
+ *     flip_f(c)[y][x] = c[y ^ (f & 2 ? 7 : 0)][x ^ (f & 1 ? 7 : 0)].
+ *   SAME CHARACTER: c_t == flip_f(c_u) for some f — an equivalence, the flips being a group.  rep(t) is the lowest tile index
+ *     of t's class, flip_of(t) the lowest f with c_t == flip_f(c_rep(t)), U the number of classes.  Subpalettes play no part:
+ *     the tilemap entry selects the palette, so tiles of different subpalettes with equal index patterns share a character.
+ *   PINNED TILE: one with a pixel of source alpha 0.  It is never changed and never donates (the library has no map value for
+ *     "transparent", so a merge across such a tile could not be drawn as the hardware draws it).  Pinned tiles count in U; all
+ *     fully transparent tiles form one class.
+ *   MERGE CANDIDATE (t, b, f), t != b, both unpinned: for every pixel (x, y) of t, map(t; x, y) := map(b; x ^ .., y ^ ..),
+ *     flipped as above.  tile_palettes is untouched — t keeps its subpalette and takes b's INDICES — and nothing else changes.
+ *     Its ERROR is error() of that stored map: no optimize(), no re-dither.  Its PROXY COST is the sum over t's 64 pixels of
+ *     red_mean_key(original pixel, 8-bit expansion of entry (tile_palettes[t], new map value)), the exact integer key of
+ *     lib.rs:1080-1088 without the square root, in a uint64_t (below 2^37).  The proxy reads the ORIGINAL image, not an
+ *     ordered-dither target, and is this integer key whatever SNES_PERCEPTUAL says; a backdrop map value takes B.  The proxy
+ *     only shortlists; the objective decides.
+ *   ONE REDUCTION STEP with shortlist length K: recipients are the unpinned tiles that are ALONE in their class (a character
+ *     already shared is kept); a recipient's donors are the class representatives that are unpinned and not the recipient.
+ *     The shortlist is the K candidates lowest in (cost, t, b, f), compared lexicographically — fewer if fewer exist.  All of
+ *     it is scored; the winner is the lowest (error, rank in the shortlist), a NaN never wins.  The winner is applied
+ *     UNCONDITIONALLY — a budget is a constraint, there is no comparison with the incumbent.  Afterwards the map is the
+ *     candidate's, the incumbent error is the candidate's scored bits and U has fallen by exactly one.
+ *   REDUCTION to max_unique: steps while U > max_unique and a recipient with a donor exists.  Running out of eligible pairs is
+ *     no error: SNES_OK, and the U that was reached is reported.  Exact duplicates cost nothing: they are one class when U is
+ *     first counted.
+ *   STATE AFTERWARDS: as after snesimage_set_palette_map, with the error known: the map is a stored map, which error(), as_rgba
+ *     and as_json read; the epoch advances.  Every call that re-runs optimize() replaces it — steps, windows,
+ *     snesimage_reassign_tiles, tile moves, the palette, tile-palette, backdrop and table setters followed by optimize().
+ *     REDUCTION IS THEREFORE THE LAST STAGE OF A RUN.
+ * The default shortlist length, 16, is a choice, not a measurement.
+ * Refusals: SNES_ERR_ARG for a null context, a tile beyond the image, a pinned tile named explicitly, t == b, f > 3,
+ * max_unique == 0, shortlist > 64; SNES_ERR_STATE between the phases of a split-phase step or window and on a context lent to a
+ * batch, a set or a group; SNES_ERR_HIP after a failed workspace allocation, the context usable and unchanged. */
+typedef struct { double error; uint64_t cost; uint16_t tile, donor; uint8_t flip, rank; uint16_t unique; } snesimage_merge_result; /* 24 bytes; unique = U after the step */
+/* U, and optionally rep (ntile), flip_of (ntile) and the characters (ntile * 64) of the image as it stands. */
+int32_t snesimage_characters(snesimage_ctx *ctx, uint32_t *unique, uint16_t *rep /*ntile, opt*/, uint8_t *flip /*ntile, opt*/,
+                             uint8_t *chars /*ntile*64, opt*/);
+/* The shortlist a reduction step with length k (1..64, 0 = 16) would score, in rank order; *n = min(k, candidates that exist).
+ * Output arrays (each optional) hold k entries.  The state is unchanged. */
+int32_t snesimage_merge_shortlist(snesimage_ctx *ctx, uint32_t k, uint16_t *tiles, uint16_t *donors, uint8_t *flips,
+                                  uint64_t *costs, uint32_t *n);
+/* errors[j] of n explicit candidates (tiles[j], donors[j], flips[j]) — any unpinned pair, not only recipients and donors —
+ * against the current state, which is left unchanged.  A candidate that changes nothing returns the incumbent error bit for
+ * bit.  maps_out (optional, n*w*h bytes): each candidate's palette_map.  Host pointers; synchronous; n may exceed the chunk
+ * (launch groups as in snesimage_score_tile_moves). */
+int32_t snesimage_score_merges(snesimage_ctx *ctx, const uint16_t *tiles, const uint16_t *donors, const uint8_t *flips,
+                               uint32_t n, double *errors, uint8_t *maps_out /*opt, n*w*h*/);
+/* The reduction.  log (optional): the first log_cap steps' records; *merges: steps taken; *unique: U afterwards.  A budget
+ * already met takes no step and leaves the state untouched bit for bit.  If a step fails (SNES_ERR_HIP) the steps before it
+ * stand: *merges and *unique report them, and the map is a stored map whose error is recomputed when next asked for. */
+int32_t snesimage_reduce_characters(snesimage_ctx *ctx, uint32_t max_unique, uint32_t shortlist /*1..64, 0 = 16*/,
+                                    snesimage_merge_result *log, uint32_t log_cap, uint32_t *merges, uint32_t *unique);
+/* The tilemap of the image as it stands; conventions of snesimage_as_json (keys sorted, no spaces, the byte count returned):
+ * "character": per tile, its class's position in "characters"; "characters": one 64-value array per class, classes ordered by
+ * representative, in the representative's own orientation; "hflip", "vflip": per tile, 0 or 1, from flip_of; "palette": per
+ * tile, tile_palettes.  Tile t is drawn as flip_f(characters[character[t]]), f = hflip[t] + 2 * vflip[t]. */
+int64_t snesimage_as_tilemap_json(snesimage_ctx *ctx, char *out, int64_t cap);
+
 /* State access (the reference mutates these fields directly: lib.rs:1015 and the GUI). */
 int32_t snesimage_get_tile_palettes(snesimage_ctx *ctx, uint8_t *out /*1024*/);
 int32_t snesimage_set_tile_palettes(snesimage_ctx *ctx, const uint8_t *in /*1024*/);

@@ -36,6 +36,12 @@ class TileResult(C.Structure):
     _fields_ = [("error", C.c_double), ("sub", C.c_int32), ("changed", C.c_uint8)]
 
 
+class MergeResult(C.Structure):
+    """snesimage_merge_result: one step of a character reduction."""
+    _fields_ = [("error", C.c_double), ("cost", C.c_uint64), ("tile", C.c_uint16), ("donor", C.c_uint16), ("flip", C.c_uint8), ("rank", C.c_uint8),
+                ("unique", C.c_uint16)]
+
+
 # every symbol include/snesimage_hip.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("snesimage_create", C.c_int32, [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
@@ -53,6 +59,11 @@ SIGNATURES = [
     ("snesimage_tile_step", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(TileResult)]),
     ("snesimage_tile_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
     ("snesimage_shared_tile_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
+    ("snesimage_characters", C.c_int32, [C.c_void_p, _u32p, _u16p, _u8p, _u8p]),
+    ("snesimage_merge_shortlist", C.c_int32, [C.c_void_p, C.c_uint32, _u16p, _u16p, _u8p, _u64p, _u32p]),
+    ("snesimage_score_merges", C.c_int32, [C.c_void_p, _u16p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_reduce_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(MergeResult), C.c_uint32, _u32p, _u32p]),
+    ("snesimage_as_tilemap_json", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     ("snesimage_score_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _f64p]),
     ("snesimage_score_candidates_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]),

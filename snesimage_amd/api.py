@@ -13,6 +13,9 @@ from . import _ffi
 DITHER, PERCEPTUAL, NES, BACKDROP = 1, 2, 4, 8
 METHOD_RANDOM, METHOD_CHANNEL, METHOD_NES = 0, 1, 2
 TILE_LOG_DTYPE = np.dtype([("error", np.float64), ("sub", np.int32), ("changed", np.uint8)])  # one record of a tile sweep's log
+# one record of a character reduction's log (snesimage_merge_result)
+MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("cost", np.uint64), ("tile", np.uint16), ("donor", np.uint16), ("flip", np.uint8), ("rank", np.uint8),
+                            ("unique", np.uint16)])
 
 
 class SnesImageError(RuntimeError):
@@ -189,6 +192,61 @@ class OptimizedImage:
         self._chk(self._L.snesimage_tile_sweep(self._c, int(first_tile), int(n_tiles), int(window), log, C.byref(stats)))
         out = np.array([(r.error, r.sub, r.changed) for r in log[:n_tiles]], dtype=TILE_LOG_DTYPE)
         return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    # -- the character budget (not in the reference; include/snesimage_hip.h) ---------------------------------------
+    def characters(self):
+        """The distinct characters of the image as it stands, equal under the tilemap's flips counted once.
+        Returns (unique, rep[ntile], flip[ntile], chars[ntile, 64])."""
+        ntile = (self.w // 8) * (self.h // 8)
+        unique = C.c_uint32(0)
+        rep, flip, chars = np.zeros(ntile, np.uint16), np.zeros(ntile, np.uint8), np.zeros((ntile, 64), np.uint8)
+        self._chk(self._L.snesimage_characters(self._c, C.byref(unique), _p(rep, _ffi._u16p), _p(flip, _ffi._u8p), _p(chars, _ffi._u8p)))
+        return unique.value, rep, flip, chars
+
+    def merge_shortlist(self, k=0):
+        """The k (1..64, 0 = 16) merge candidates lowest in (proxy cost, tile, donor, flip); the state is left unchanged.
+        Returns (tiles, donors, flips, costs), each as long as the shortlist that exists."""
+        cap = 64
+        tiles, donors, flips, costs = np.zeros(cap, np.uint16), np.zeros(cap, np.uint16), np.zeros(cap, np.uint8), np.zeros(cap, np.uint64)
+        n = C.c_uint32(0)
+        self._chk(self._L.snesimage_merge_shortlist(self._c, int(k), _p(tiles, _ffi._u16p), _p(donors, _ffi._u16p), _p(flips, _ffi._u8p), _p(costs, _ffi._u64p),
+                                                    C.byref(n)))
+        return tiles[:n.value].copy(), donors[:n.value].copy(), flips[:n.value].copy(), costs[:n.value].copy()
+
+    def score_merges(self, tiles, donors, flips, want_maps=False):
+        """error() of the image with tile tiles[j] taking the indices of tile donors[j] under flip flips[j], for every j; the
+        state is left unchanged.  Returns errors (float64), or (errors, maps[n, h, w]) with want_maps."""
+        tiles = np.ascontiguousarray(tiles, np.uint16).reshape(-1)
+        donors = np.ascontiguousarray(donors, np.uint16).reshape(-1)
+        flips = np.ascontiguousarray(flips, np.uint8).reshape(-1)
+        if not tiles.size == donors.size == flips.size:
+            raise ValueError("tiles, donors and flips differ in length")
+        errs = np.zeros(tiles.size, np.float64)
+        maps = np.zeros((tiles.size, self.h, self.w), np.uint8) if want_maps else None
+        self._chk(self._L.snesimage_score_merges(self._c, _p(tiles, _ffi._u16p), _p(donors, _ffi._u16p), _p(flips, _ffi._u8p), tiles.size, _p(errs, _ffi._f64p),
+                                                 _p(maps, _ffi._u8p) if want_maps else None))
+        return (errs, maps) if want_maps else errs
+
+    def reduce_characters(self, max_unique, shortlist=0):
+        """Merge tiles until at most max_unique distinct characters are left (or no eligible pair is); every merge is the
+        one of the proxy's `shortlist` (1..64, 0 = 16) best with the lowest error().  The last stage of a run: anything that
+        re-runs optimize() replaces the merged map.  Returns (records, unique): a structured array (MERGE_LOG_DTYPE), one
+        record per merge, and the count reached."""
+        cap = (self.w // 8) * (self.h // 8)
+        log = (_ffi.MergeResult * cap)()
+        merges, unique = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.snesimage_reduce_characters(self._c, int(max_unique), int(shortlist), log, cap, C.byref(merges), C.byref(unique)))
+        out = np.array([(r.error, r.cost, r.tile, r.donor, r.flip, r.rank, r.unique) for r in log[:merges.value]], dtype=MERGE_LOG_DTYPE)
+        return out, unique.value
+
+    def as_tilemap_json(self):
+        """The tilemap the characters imply: characters, and per tile character, hflip, vflip and palette."""
+        need = self._L.snesimage_as_tilemap_json(self._c, None, 0)
+        if need < 0:
+            raise SnesImageError(int(need), self._L.snesimage_last_error().decode())
+        buf = C.create_string_buffer(int(need))
+        self._L.snesimage_as_tilemap_json(self._c, buf, need)
+        return buf.value.decode()
 
     def score_candidates(self, palette, index, rgb5):
         """Loop body of lib.rs:205-220 for an explicit candidate list -> errors (float64)."""

@@ -17,6 +17,9 @@
 // --ordered-dither N [--dither-amplitude A] adds the N x N Bayer pattern of amplitude A to the picture before the nearest-colour
 // choice (include/snesimage_hip.h: snesimage_set_ordered_dither): the alternative to -d that keeps animation frames steady.
 // The JSON does not record it: a --resume run names the option again.
+// --max-tiles N merges tiles after the last optimizer call until at most N distinct characters are left (the VRAM budget;
+// include/snesimage_hip.h: snesimage_reduce_characters), --merge-shortlist K sets how many merges each step scores, and
+// --tilemap FILE writes the characters and the tilemap (snesimage_as_tilemap_json), with or without --max-tiles.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -81,6 +84,12 @@ void usage() {
             "      --tile-moves <K>     every K sweeps of the palette, try every tile in every other subpalette and keep the moves that\n"
             "                           lower the error itself (dithering included); cannot be used with --reassign-tiles, which\n"
             "                           moves tiles by colour distance and undoes these moves, nor with --devices\n"
+            "      --max-tiles <N>      after the last optimizer call, merge tiles until at most N distinct characters are left (tiles equal\n"
+            "                           under the tilemap's flips count once); each merge is the one with the lowest error among the\n"
+            "                           --merge-shortlist cheapest by colour distance; not with --share or --devices\n"
+            "      --merge-shortlist <K>  merges scored per step, 1..64 [default: 16: a choice, not a measurement]; needs --max-tiles\n"
+            "      --tilemap <F>        write the distinct characters and the tilemap (character, hflip, vflip, palette per tile) as JSON;\n"
+            "                           not with --share or --devices\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
             "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only\n"
@@ -166,7 +175,8 @@ int main(int argc, char **argv) {
     uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, tile_every = 0, window = 0; // src/config.rs:13-18 defaults
     uint64_t seed = 1;
     int device = 0;
-    std::string tile_file, preview_file, resume_file;
+    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg;
+    bool max_tiles_given = false, merge_short_given = false; uint32_t max_tiles = 0, merge_short = 0;
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
@@ -195,6 +205,9 @@ int main(int argc, char **argv) {
         else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
         else if (a == "--tile-moves") tile_every = (uint32_t)strtoul(need("--tile-moves"), nullptr, 10);
         else if (a == "--resume") resume_file = need("--resume");
+        else if (a == "--max-tiles") { max_tiles_given = true; max_tiles_arg = need("--max-tiles"); }
+        else if (a == "--merge-shortlist") { merge_short_given = true; merge_short_arg = need("--merge-shortlist"); }
+        else if (a == "--tilemap") tilemap_file = need("--tilemap");
         else if (a == "--share") {
             const std::string v = need("--share");
             const size_t eq = v.find('=');
@@ -210,6 +223,23 @@ int main(int argc, char **argv) {
     if (tile_every) { // objective-scored moves and the colour-distance proxy undo each other; no group entry point for the moves
         const char *bad = !devices.empty() ? "'--devices'" : (reassign_every ? "'--reassign-tiles'" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--tile-moves <K>' cannot be used with %s\n", bad); return 2; }
+    }
+    if (max_tiles_given || merge_short_given || !tilemap_file.empty()) { // said before any file or device is touched
+        char *end = nullptr;
+        if (merge_short_given && !max_tiles_given) { fprintf(stderr, "error: '--merge-shortlist <K>' needs '--max-tiles <N>'\n"); return 2; }
+        const char *opt = max_tiles_given ? "--max-tiles <N>" : "--tilemap <F>";
+        const char *bad = !shares.empty() ? "'--share'" : (!devices.empty() ? "'--devices'" : nullptr); // characters are counted in one image on one device
+        if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
+        if (max_tiles_given) {
+            const unsigned long n = strtoul(max_tiles_arg.c_str(), &end, 10);
+            if (max_tiles_arg.empty() || *end || n < 1 || n > 1024) { fprintf(stderr, "error: invalid value '%s' for '--max-tiles <N>': expected 1..1024\n", max_tiles_arg.c_str()); return 2; }
+            max_tiles = (uint32_t)n;
+        }
+        if (merge_short_given) {
+            const unsigned long k = strtoul(merge_short_arg.c_str(), &end, 10);
+            if (merge_short_arg.empty() || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--merge-shortlist <K>': expected 1..64\n", merge_short_arg.c_str()); return 2; }
+            merge_short = (uint32_t)k;
+        }
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
@@ -439,11 +469,31 @@ int main(int argc, char **argv) {
         report(p, ix, &before[3 * ((size_t)p * size + ix)], best, error);
         end_of_sweep();
     }
+    if (max_tiles_given) { // the last stage: anything that re-runs optimize() would replace the merged map
+        uint32_t u0 = 0, u1 = 0, merges = 0;
+        double e0 = 0.0, e1 = 0.0;
+        if (snesimage_characters(ctx, &u0, nullptr, nullptr, nullptr) != 0 || snesimage_error(ctx, &e0) != 0) die(std::string("Unable to count characters: ") + snesimage_last_error());
+        if (snesimage_reduce_characters(ctx, max_tiles, merge_short, nullptr, 0, &merges, &u1) != 0 || snesimage_error(ctx, &e1) != 0) die(std::string("Unable to merge tiles: ") + snesimage_last_error());
+        log_info("Characters: " + std::to_string(u0) + " -> " + std::to_string(u1) + " in " + std::to_string(merges) + " merges (budget " + std::to_string(max_tiles) + ")");
+        log_info("Error: " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        if (u1 > max_tiles) log_info("No tile is left that may be merged: the budget is not met");
+    }
     log_info("Writing output to " + target); // src/lib.rs:1000-1002
     write_json(ctx, target);
     for (size_t i = 0; i < shares.size(); i++) {
         log_info("Writing output to " + shares[i].second);
         write_json(frames[i + 1], shares[i].second);
+    }
+    if (!tilemap_file.empty()) {
+        const int64_t need = snesimage_as_tilemap_json(ctx, nullptr, 0);
+        if (need < 0) die(snesimage_last_error());
+        std::vector<char> json((size_t)need);
+        snesimage_as_tilemap_json(ctx, json.data(), need);
+        FILE *f = fopen(tilemap_file.c_str(), "wb");
+        if (!f) die("cannot create " + tilemap_file);
+        fwrite(json.data(), 1, (size_t)need - 1, f);
+        fclose(f);
+        log_info("Wrote tilemap to " + tilemap_file);
     }
     if (!preview_file.empty()) { // left: source, right: as_rgba() of the result (src/lib.rs:940-957)
         std::vector<uint8_t> result((size_t)w * h * 4), both((size_t)2 * w * h * 4), png;

@@ -82,7 +82,8 @@ int32_t tile_alloc(snesimage_ctx *c, uint32_t need) {
 
 // What every tile entry point needs first.  *base_map: the optimize() of the state as it stands, which the candidates of a
 // context without --dither start from — the stored map, or one made here if the stored map does not belong to the palette.
-int32_t tile_prepare(snesimage_ctx *c, uint32_t need, const uint8_t **base_map) {
+// stored_base: the candidates start from the stored map whatever it belongs to (the character merges, char_host.inc).
+int32_t tile_prepare(snesimage_ctx *c, uint32_t need, const uint8_t **base_map, bool stored_base = false) {
     CHECK(ensure_map(c)); // an optimize() still owed belongs to the state the candidates are compared with
     CHECK(ensure_tables(c));
     CHECK(ensure_source(c));
@@ -99,7 +100,7 @@ int32_t tile_prepare(snesimage_ctx *c, uint32_t need, const uint8_t **base_map) 
         t.planes_ready = true;
     }
     *base_map = c->d_map;
-    if (!c->dither && !c->map_synced) { // (mode 0 leaves the same transparency marker in the pack)
+    if (!c->dither && !c->map_synced && !stored_base) { // (mode 0 leaves the same transparency marker in the pack)
         P.tile_pal = c->d_tile_pal; P.map = t.basemap; P.mode = 0; P.subC4 = nullptr; P.subR4 = nullptr;
         P.labpx = c->d_labpx_t; P.pal_lab = c->d_pal_lab; P.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_prep, grid, dim3(256), 0, c->stream, P);
@@ -109,12 +110,34 @@ int32_t tile_prepare(snesimage_ctx *c, uint32_t need, const uint8_t **base_map) 
     return SNES_OK;
 }
 
-// nc candidates, pairs at t.tiles / t.subs [0, nc): maps into t.lmaps, errors into d_errors[0, nc)
-int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors) {
+// The two ends of a launch group, shared with the character merges: the candidates' colour tables in front of whatever
+// writes their maps into t.lmaps (and their pairs into t.tiles / t.subs), the scorer behind it.
+void tile_score_head(snesimage_ctx *c, uint32_t nc) {
     snesimage_tilework &t = *c->tile;
     hipStream_t st = c->stream;
     hipLaunchKernelGGL(k_candidate_tables, dim3((nc + 63) / 64), dim3(64), 0, st, t.zero_rgb5, (int)nc, c->d_eotf, t.cand_tab);
     hipLaunchKernelGGL(k_candidate_slot, dim3((nc + 63) / 64), dim3(64), 0, st, t.cand_tab, (int)nc, 0xffffffffu); // no colour index is "the candidate's"
+}
+int32_t tile_score_tail(snesimage_ctx *c, uint32_t nc, double *d_errors) {
+    snesimage_tilework &t = *c->tile;
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(k_tile_full, dim3((unsigned)((c->npx / 4 + 255) / 256), nc), dim3(256), 0, st, (const uint8_t *)t.lmaps, (const uint8_t *)c->d_tile_pal, (const uint16_t *)t.tiles,
+                       (const uint8_t *)t.subs, (int)c->W, (int)c->H, (int)c->sub_size, t.maps, t.mapsC4);
+    const bool fast0 = (c->fast_mask & 1) != 0;
+    hipLaunchKernelGGL(k_maps_relayout, dim3((unsigned)(c->H / 4), nc), dim3(256), 0, st, (const uint8_t *)t.maps, (int)c->W, (int)c->H, reinterpret_cast<uint32_t *>(t.mapsR4),
+                       fast0 ? (uint32_t *)nullptr : reinterpret_cast<uint32_t *>(t.mapsT));
+    // the scorer's own stages, on this workspace: full-index maps, a tile table and subpalette planes of zeros
+    DenseView V{t.pack, t.packT, t.packC4, t.packR4, t.sub0C4, t.sub0R4, t.zero_tile, t.work, t.cand_tab, nullptr, t.part, t.maps, t.mapsT, t.mapsC4, t.mapsR4, true, false};
+    CHECK(score_stages(c, V, nc, d_errors, 1, 0, nullptr));
+    HIPCHK(hipGetLastError());
+    return SNES_OK;
+}
+
+// nc candidates, pairs at t.tiles / t.subs [0, nc): maps into t.lmaps, errors into d_errors[0, nc)
+int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors) {
+    snesimage_tilework &t = *c->tile;
+    hipStream_t st = c->stream;
+    tile_score_head(c, nc);
     if (c->dither) {
         hipLaunchKernelGGL(k_tile_tabs, dim3(nc), dim3(256), 0, st, c->d_tile_pal, t.tiles, t.subs, t.tabs);
         DitherParams Dp{};
@@ -136,16 +159,7 @@ int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map,
         R.tiles = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps; R.W = (int)c->W; R.H = (int)c->H; R.sub_size = (int)c->sub_size; R.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_tile_remap, dim3(nc), dim3(256), 0, st, R);
     }
-    hipLaunchKernelGGL(k_tile_full, dim3((unsigned)((c->npx / 4 + 255) / 256), nc), dim3(256), 0, st, (const uint8_t *)t.lmaps, (const uint8_t *)c->d_tile_pal, (const uint16_t *)t.tiles,
-                       (const uint8_t *)t.subs, (int)c->W, (int)c->H, (int)c->sub_size, t.maps, t.mapsC4);
-    const bool fast0 = (c->fast_mask & 1) != 0;
-    hipLaunchKernelGGL(k_maps_relayout, dim3((unsigned)(c->H / 4), nc), dim3(256), 0, st, (const uint8_t *)t.maps, (int)c->W, (int)c->H, reinterpret_cast<uint32_t *>(t.mapsR4),
-                       fast0 ? (uint32_t *)nullptr : reinterpret_cast<uint32_t *>(t.mapsT));
-    // the scorer's own stages, on this workspace: full-index maps, a tile table and subpalette planes of zeros
-    DenseView V{t.pack, t.packT, t.packC4, t.packR4, t.sub0C4, t.sub0R4, t.zero_tile, t.work, t.cand_tab, nullptr, t.part, t.maps, t.mapsT, t.mapsC4, t.mapsR4, true, false};
-    CHECK(score_stages(c, V, nc, d_errors, 1, 0, nullptr));
-    HIPCHK(hipGetLastError());
-    return SNES_OK;
+    return tile_score_tail(c, nc, d_errors);
 }
 
 int32_t tile_check(snesimage_ctx *c) {
