@@ -374,6 +374,60 @@ int32_t snesimage_reduce_characters(snesimage_ctx *ctx, uint32_t max_unique, uin
  * tile, tile_palettes.  Tile t is drawn as flip_f(characters[character[t]]), f = hflip[t] + 2 * vflip[t]. */
 int64_t snesimage_as_tilemap_json(snesimage_ctx *ctx, char *out, int64_t cap);
 
+/* The refit of shared characters — NOT a reference method.  A merge gives tile t the indices of a donor b: indices chosen for
+ * b's pixels and b's subpalette.  A refit asks which 64 indices are best for ALL the tiles that share a character, each read
+ * through its own subpalette and flip — the centroid update of vector quantisation.  Off unless called; no other entry point
+ * changes.  Integers only, except the objective.  The terms are those of the character budget above; everything works on MAP
+ * VALUES (in an unpinned tile a character value is the map value + 1, or 0 for the backdrop value of a backdrop context).
+ * S is the context's internal subpalette size (sub_size + 1 in a backdrop context, whose backdrop B is entry S - 1 of every
+ * subpalette).
+ *   SNAPSHOT: at the start of a sweep, the classes of the stored map as it stands (an optimize() still owed runs first, as in
+ *     snesimage_characters).  An ELIGIBLE CLASS has at least 2 members, none of them pinned.  Its members, its representative
+ *     r = rep and the flips f_m = flip_of(m) are fixed for the whole sweep.  mask(f) = (f & 1 ? 7 : 0) | (f & 2 ? 56 : 0):
+ *     member m's pixel q ^ mask(f_m) shows position q of the representative's orientation.
+ *   FIT of an eligible class: for position q in 0..63 and value v in 0..S-1,
+ *       cost(q, v) = sum over members m of red_mean_key(original pixel q ^ mask(f_m) of tile m,
+ *                                                       8-bit expansion of entry tile_palettes[m] * S + v),
+ *     the integer key of lib.rs:1080-1088 without the square root, summed in a uint64_t (below 2^39).  It reads the ORIGINAL
+ *     image, never the ordered-dither target, and is this integer key whatever SNES_PERCEPTUAL says.  fitted[q] = the LOWEST v
+ *     among the minima of cost(q, .); cur[q] = the representative's map value at q;
+ *     gain = sum over q of cost(q, cur[q]) - cost(q, fitted[q]) >= 0.  The fit depends on the snapshot, the original and the
+ *     palette only, not on the map: the fits of all classes of a sweep are computed once, up front.
+ *   REFIT CALL on eligible class r: if fitted == cur the call is SKIPPED — not scored, changed = 0, the record's error is the
+ *     incumbent.  Otherwise the candidate is the stored map with map(m; p) := fitted[p ^ mask(f_m)] for every member m and
+ *     pixel p, nothing else changed; its error is error() of that stored map (no optimize(), no re-dither); acceptance is
+ *     lib.rs:216-219: taken iff e < incumbent, strict.  Unlike a merge, which a constraint forces, a refit is an improvement:
+ *     it is conditional and can never raise the error.
+ *   REFIT SWEEP: the refit calls on the eligible classes in ascending rep order, each seeing the map and the incumbent the call
+ *     before left (classes are disjoint tile sets: the candidates of later classes stay well defined after an acceptance).
+ *     Afterwards, if anything was accepted, the state is that of snesimage_reduce_characters: a stored map with its error
+ *     known, the epoch advanced.  A sweep that accepts nothing, or has no eligible class, leaves the context untouched bit
+ *     for bit.  U never rises; it may fall if two classes become equal.  Like the reduction, A REFIT IS THE LAST STAGE OF A
+ *     RUN: whatever re-runs optimize() replaces it.
+ *   WINDOWS as snesimage_tile_sweep: a window builds and scores the candidates of the coming K non-skipped calls against the map
+ *     as it stands in one launch group and commits them in order on the device up to the first that accepts; the calls behind
+ *     it are scored again by the next window (one synchronisation per window).  window: 0 = chosen by the library, 1 = call by
+ *     call, K = at most K calls per launch set (bounded by the launch group of the tile moves, at most 512).  For every window
+ *     everything observable afterwards equals call by call, bit for bit.
+ * Refusals: SNES_ERR_ARG for a null context, a rep beyond the image, a rep that is not the representative of an eligible class;
+ * SNES_ERR_STATE between the phases of a split-phase step or window and on a context lent to a batch, a set or a group;
+ * SNES_ERR_HIP after a failed workspace allocation, the context usable and unchanged. */
+typedef struct { double error; uint64_t gain; uint16_t rep, members; uint8_t changed, scored; uint8_t pad[2]; } snesimage_refit_result; /* 24 bytes; error = the incumbent after the call */
+/* The eligible classes of the image as it stands, ascending rep, with their fits: reps, members, gains hold up to ntile entries,
+ * fits 64 map values per class in the representative's orientation; *n = classes.  Every array is optional.  State unchanged. */
+int32_t snesimage_character_fits(snesimage_ctx *ctx, uint16_t *reps /*ntile*/, uint16_t *members /*ntile*/, uint64_t *gains /*ntile*/,
+                                 uint8_t *fits /*ntile*64*/, uint32_t *n);
+/* errors[j] of the refit candidates of n explicit classes (named by their representative, which must be eligible) against the
+ * current state, which is left unchanged.  A class whose fit equals its character returns the incumbent error bit for bit.
+ * maps_out (optional, n*w*h bytes): each candidate's palette_map.  Host pointers; synchronous; n may exceed the chunk. */
+int32_t snesimage_score_refits(snesimage_ctx *ctx, const uint16_t *reps, uint32_t n, double *errors, uint8_t *maps_out /*opt, n*w*h*/);
+/* One refit sweep.  log (optional): the first log_cap records in call order (skipped calls included, scored = 0); *calls = the
+ * eligible classes; *accepted = calls taken; *unique = U afterwards; stats (optional) as snesimage_tile_sweep: calls, accepted,
+ * windows, candidates scored, and `useful` = the scored calls that took effect.  If a window fails (SNES_ERR_HIP) the calls
+ * accepted before it stand and are reported; the map is a stored map whose error is recomputed when next asked for. */
+int32_t snesimage_refit_characters(snesimage_ctx *ctx, uint32_t window, snesimage_refit_result *log, uint32_t log_cap,
+                                   uint32_t *calls, uint32_t *accepted, uint32_t *unique, snesimage_run_stats *stats);
+
 /* State access (the reference mutates these fields directly: lib.rs:1015 and the GUI). */
 int32_t snesimage_get_tile_palettes(snesimage_ctx *ctx, uint8_t *out /*1024*/);
 int32_t snesimage_set_tile_palettes(snesimage_ctx *ctx, const uint8_t *in /*1024*/);

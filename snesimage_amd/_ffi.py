@@ -42,6 +42,12 @@ class MergeResult(C.Structure):
                 ("unique", C.c_uint16)]
 
 
+class RefitResult(C.Structure):
+    """snesimage_refit_result: one call of a refit sweep."""
+    _fields_ = [("error", C.c_double), ("gain", C.c_uint64), ("rep", C.c_uint16), ("members", C.c_uint16), ("changed", C.c_uint8), ("scored", C.c_uint8),
+                ("pad", C.c_uint8 * 2)]
+
+
 # every symbol include/snesimage_hip.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("snesimage_create", C.c_int32, [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
@@ -64,6 +70,9 @@ SIGNATURES = [
     ("snesimage_score_merges", C.c_int32, [C.c_void_p, _u16p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
     ("snesimage_reduce_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(MergeResult), C.c_uint32, _u32p, _u32p]),
     ("snesimage_as_tilemap_json", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
+    ("snesimage_character_fits", C.c_int32, [C.c_void_p, _u16p, _u16p, _u64p, _u8p, _u32p]),
+    ("snesimage_score_refits", C.c_int32, [C.c_void_p, _u16p, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_refit_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(RefitResult), C.c_uint32, _u32p, _u32p, _u32p, C.POINTER(RunStats)]),
     ("snesimage_score_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _f64p]),
     ("snesimage_score_candidates_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]),

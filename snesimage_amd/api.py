@@ -16,6 +16,9 @@ TILE_LOG_DTYPE = np.dtype([("error", np.float64), ("sub", np.int32), ("changed",
 # one record of a character reduction's log (snesimage_merge_result)
 MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("cost", np.uint64), ("tile", np.uint16), ("donor", np.uint16), ("flip", np.uint8), ("rank", np.uint8),
                             ("unique", np.uint16)])
+# one record of a refit sweep's log (snesimage_refit_result)
+REFIT_LOG_DTYPE = np.dtype([("error", np.float64), ("gain", np.uint64), ("rep", np.uint16), ("members", np.uint16), ("changed", np.uint8), ("scored", np.uint8),
+                            ("pad", np.uint8, (2,))])
 
 
 class SnesImageError(RuntimeError):
@@ -238,6 +241,43 @@ class OptimizedImage:
         self._chk(self._L.snesimage_reduce_characters(self._c, int(max_unique), int(shortlist), log, cap, C.byref(merges), C.byref(unique)))
         out = np.array([(r.error, r.cost, r.tile, r.donor, r.flip, r.rank, r.unique) for r in log[:merges.value]], dtype=MERGE_LOG_DTYPE)
         return out, unique.value
+
+    def character_fits(self):
+        """The eligible classes of the image as it stands (at least two tiles sharing a character, none pinned), ascending
+        representative, each with the 64 map values that cost least over all its members (include/snesimage_hip.h: FIT).
+        Returns (reps[n], members[n], gains[n], fits[n, 64]); the state is left unchanged."""
+        ntile = (self.w // 8) * (self.h // 8)
+        reps, members, gains, fits = np.zeros(ntile, np.uint16), np.zeros(ntile, np.uint16), np.zeros(ntile, np.uint64), np.zeros((ntile, 64), np.uint8)
+        n = C.c_uint32(0)
+        self._chk(self._L.snesimage_character_fits(self._c, _p(reps, _ffi._u16p), _p(members, _ffi._u16p), _p(gains, _ffi._u64p), _p(fits, _ffi._u8p), C.byref(n)))
+        return reps[:n.value].copy(), members[:n.value].copy(), gains[:n.value].copy(), fits[:n.value].copy()
+
+    def score_refits(self, reps, want_maps=False):
+        """error() of the image with every tile of class reps[j] redrawn from the class's fit, for every j; the state is left
+        unchanged.  Returns errors (float64), or (errors, maps[n, h, w]) with want_maps."""
+        reps = np.ascontiguousarray(reps, np.uint16).reshape(-1)
+        errs = np.zeros(reps.size, np.float64)
+        maps = np.zeros((reps.size, self.h, self.w), np.uint8) if want_maps else None
+        self._chk(self._L.snesimage_score_refits(self._c, _p(reps, _ffi._u16p), reps.size, _p(errs, _ffi._f64p), _p(maps, _ffi._u8p) if want_maps else None))
+        return (errs, maps) if want_maps else errs
+
+    def refit_characters(self, window=0, want_stats=False):
+        """One refit sweep: every shared character is refitted to all the tiles that use it, and the refit is kept where
+        error() falls (bit-identical for every `window`: 0 = chosen by the library, 1 = call by call, K = at most K calls per
+        launch set).  The last stage of a run, like `reduce_characters`.  Returns (records, accepted, unique): a structured
+        array (REFIT_LOG_DTYPE), one record per eligible class, the calls taken and the character count afterwards; with
+        want_stats a dict of the run statistics as a fourth item."""
+        cap = (self.w // 8) * (self.h // 8)
+        log = (_ffi.RefitResult * cap)()
+        calls, accepted, unique = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_refit_characters(self._c, int(window), log, cap, C.byref(calls), C.byref(accepted), C.byref(unique), C.byref(stats)))
+        out = np.zeros(calls.value, REFIT_LOG_DTYPE)
+        for j, r in enumerate(log[:calls.value]):
+            out[j] = (r.error, r.gain, r.rep, r.members, r.changed, r.scored, (0, 0))
+        if want_stats:
+            return out, accepted.value, unique.value, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+        return out, accepted.value, unique.value
 
     def as_tilemap_json(self):
         """The tilemap the characters imply: characters, and per tile character, hflip, vflip and palette."""

@@ -1,5 +1,6 @@
 // snesimage_amd/csrc/char_host.inc — the character budget: snesimage_characters, snesimage_merge_shortlist,
-// snesimage_score_merges, snesimage_reduce_characters, snesimage_as_tilemap_json (definition: include/snesimage_hip.h;
+// snesimage_score_merges, snesimage_reduce_characters, snesimage_as_tilemap_json, and the refit of shared characters:
+// snesimage_character_fits, snesimage_score_refits, snesimage_refit_characters (definition: include/snesimage_hip.h;
 // kernels: kernels_char.hpp).
 //
 // Characters, classes and the proxy shortlist are recomputed from the stored map whenever they are asked for (five small
@@ -10,6 +11,9 @@
 // first merge the map is no optimize() of anything.
 // A reduction step enqueues scoring, k_merge_commit and the next step's characters and shortlist, then reads the record and
 // the next shortlist's length back: one synchronisation per step.
+// A refit sweep takes the classes and their fits once (k_refit_fit: they depend on the snapshot, the original and the palette,
+// not on the map), then goes through the classes whose fit differs from their character in windows as a tile sweep does:
+// k_refit_maps, the scorer, k_refit_commit, one synchronisation per window.
 // Included by capi.hip behind tile_host.inc (it uses the tile workspace).
 
 struct snesimage_charwork {
@@ -18,14 +22,20 @@ struct snesimage_charwork {
     uint16_t *rep = nullptr, *csize = nullptr;
     unsigned long long *part = nullptr, *keys = nullptr; // part: a list of kCharShort keys per tile; keys: the shortlist, or the pairs of a score_merges launch group (kTileGroup)
     snes::CharInfo *info = nullptr; snes::MergeLog *log = nullptr;
+    // the refit: fits[r * 64 + q] and fit[r] of the class tile r represents; the window's classes; its result (RefitWinRes, 16 bytes, then kTileGroup records)
+    uint8_t *fits = nullptr; snes::RefitFit *fit = nullptr; uint16_t *rcalls = nullptr; unsigned char *rresult = nullptr;
+    WindowPolicy policy; uint32_t adapt = 4;
 };
 
 namespace {
 
 static_assert(sizeof(snes::MergeLog) == sizeof(snesimage_merge_result) && sizeof(snes::MergeLog) == 24, "the log record is copied out as it is");
+static_assert(sizeof(snes::RefitLog) == sizeof(snesimage_refit_result) && sizeof(snes::RefitLog) == 24, "the log record is copied out as it is");
+static_assert(sizeof(snes::RefitFit) == 16 && sizeof(snes::RefitWinRes) <= 16, "the layout of the refit workspace");
 
 void char_release(snesimage_charwork *w) {
     dfree(w->chars); dfree(w->pinned); dfree(w->flip); dfree(w->rep); dfree(w->csize); dfree(w->part); dfree(w->keys); dfree(w->info); dfree(w->log);
+    dfree(w->fits); dfree(w->fit); dfree(w->rcalls); dfree(w->rresult);
     w->ready = false;
 }
 void char_free(snesimage_ctx *c) { if (c->chr) { char_release(c->chr); delete c->chr; c->chr = nullptr; } }
@@ -40,10 +50,14 @@ int32_t char_alloc(snesimage_ctx *c) {
         HIPCHK(dmalloc(&w.rep, sizeof(uint16_t) * 1024)); HIPCHK(dmalloc(&w.csize, sizeof(uint16_t) * 1024));
         HIPCHK(dmalloc(&w.part, sizeof(unsigned long long) * 1024 * kCharShort)); HIPCHK(dmalloc(&w.keys, sizeof(unsigned long long) * kTileGroup));
         HIPCHK(dmalloc(&w.info, sizeof(snes::CharInfo))); HIPCHK(dmalloc(&w.log, sizeof(snes::MergeLog)));
+        HIPCHK(dmalloc(&w.fits, 1024 * 64)); HIPCHK(dmalloc(&w.fit, sizeof(snes::RefitFit) * 1024)); HIPCHK(dmalloc(&w.rcalls, sizeof(uint16_t) * kTileGroup));
+        HIPCHK(dmalloc(&w.rresult, 16 + sizeof(snes::RefitLog) * kTileGroup));
         if (g_poison_alloc.load()) { // whatever is read must have been written by the call's own kernels
             HIPCHK(hipMemsetAsync(w.chars, 0xff, 1024 * 64, c->stream)); HIPCHK(hipMemsetAsync(w.pinned, 0xff, 1024, c->stream)); HIPCHK(hipMemsetAsync(w.flip, 0xff, 1024, c->stream));
             HIPCHK(hipMemsetAsync(w.rep, 0xff, sizeof(uint16_t) * 1024, c->stream)); HIPCHK(hipMemsetAsync(w.csize, 0xff, sizeof(uint16_t) * 1024, c->stream));
             HIPCHK(hipMemsetAsync(w.part, 0x5a, sizeof(unsigned long long) * 1024 * kCharShort, c->stream)); HIPCHK(hipMemsetAsync(w.keys, 0x5a, sizeof(unsigned long long) * kTileGroup, c->stream));
+            HIPCHK(hipMemsetAsync(w.fits, 0xff, 1024 * 64, c->stream)); HIPCHK(hipMemsetAsync(w.fit, 0xff, sizeof(snes::RefitFit) * 1024, c->stream));
+            HIPCHK(hipMemsetAsync(w.rcalls, 0xff, sizeof(uint16_t) * kTileGroup, c->stream)); HIPCHK(hipMemsetAsync(w.rresult, 0xff, 16 + sizeof(snes::RefitLog) * kTileGroup, c->stream));
         }
         return SNES_OK;
     };
@@ -105,6 +119,38 @@ int32_t char_shortlist_len(uint32_t *k) {
     if (*k > (uint32_t)kCharShort) return fail(SNES_ERR_ARG, "a shortlist holds at most 64 candidates");
     if (*k == 0) *k = 16;
     return SNES_OK;
+}
+
+// the snapshot and the fits of a sweep: classes of the stored map, then every eligible class's fit (w.fits, w.fit)
+int32_t char_fits(snesimage_ctx *c) {
+    CHECK(char_classes(c));
+    snesimage_charwork &w = *c->chr;
+    const uint32_t ntile = char_ntile(c);
+    hipLaunchKernelGGL(k_refit_fit, dim3(ntile), dim3(256), 0, c->stream, (const uint8_t *)c->d_orig, (const uint8_t *)c->d_map, (int)c->W, (const uint8_t *)w.pinned, (const uint16_t *)w.rep,
+                       (const uint8_t *)w.flip, (const uint16_t *)w.csize, (const uint8_t *)c->d_tile_pal, (const uint32_t *)c->d_pal_rgb8, (int)c->sub_size, c->ncol, (int)ntile, w.fits, w.fit);
+    HIPCHK(hipGetLastError());
+    return SNES_OK;
+}
+// ... read back: fit[ntile], and U of the snapshot
+int32_t char_fits_read(snesimage_ctx *c, std::vector<snes::RefitFit> &fit, uint32_t *unique) {
+    snesimage_charwork &w = *c->chr;
+    snes::CharInfo info{};
+    fit.resize(char_ntile(c));
+    HIPCHK(hipMemcpyAsync(fit.data(), w.fit, sizeof(snes::RefitFit) * fit.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&info, w.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *unique = info.unique;
+    return SNES_OK;
+}
+
+// nc refit candidates, classes at w.rcalls[0, nc): maps into the tile workspace's lmaps, errors into d_errors[0, nc)
+int32_t refit_score_group(snesimage_ctx *c, uint32_t nc, double *d_errors) {
+    snesimage_tilework &t = *c->tile;
+    snesimage_charwork &w = *c->chr;
+    tile_score_head(c, nc);
+    hipLaunchKernelGGL(k_refit_maps, dim3(nc), dim3(256), 0, c->stream, (const uint16_t *)w.rcalls, (const uint8_t *)c->d_map, (const uint16_t *)w.rep, (const uint8_t *)w.flip, (const uint8_t *)w.fits,
+                       (const uint8_t *)c->d_tile_pal, (int)c->W, (int)c->npx, t.lmaps, t.tiles, t.subs);
+    return tile_score_tail(c, nc, d_errors);
 }
 
 } // namespace
@@ -243,6 +289,159 @@ int32_t snesimage_reduce_characters(snesimage_ctx *c, uint32_t max_unique, uint3
     if (merges) *merges = done;
     if (unique) *unique = info.unique;
     return SNES_OK;
+}
+
+int32_t snesimage_character_fits(snesimage_ctx *c, uint16_t *reps, uint16_t *members, uint64_t *gains, uint8_t *fits, uint32_t *n) {
+    CHECK(char_check(c));
+    CHECK(set_device(c));
+    CHECK(ensure_map(c));
+    CHECK(ensure_tables(c));
+    CHECK(char_alloc(c));
+    CHECK(char_fits(c));
+    const uint32_t ntile = char_ntile(c);
+    std::vector<snes::RefitFit> fit;
+    std::vector<uint8_t> all(fits ? 64 * (size_t)ntile : 0);
+    if (fits) HIPCHK(hipMemcpyAsync(all.data(), c->chr->fits, all.size(), hipMemcpyDeviceToHost, c->stream));
+    uint32_t unique = 0;
+    CHECK(char_fits_read(c, fit, &unique));
+    uint32_t k = 0;
+    for (uint32_t r = 0; r < ntile; r++) {
+        if (!fit[r].eligible) continue;
+        if (reps) reps[k] = (uint16_t)r;
+        if (members) members[k] = fit[r].members;
+        if (gains) gains[k] = fit[r].gain;
+        if (fits) memcpy(fits + 64 * (size_t)k, all.data() + 64 * (size_t)r, 64);
+        k++;
+    }
+    if (n) *n = k;
+    return SNES_OK;
+}
+
+int32_t snesimage_score_refits(snesimage_ctx *c, const uint16_t *reps, uint32_t n, double *errors, uint8_t *maps_out) {
+    CHECK(char_check(c));
+    if (!reps || !errors) return fail(SNES_ERR_ARG, "null pointer");
+    if (n == 0) return SNES_OK;
+    const uint32_t ntile = char_ntile(c);
+    for (uint32_t j = 0; j < n; j++) if (reps[j] >= ntile) return fail(SNES_ERR_ARG, "tile beyond the image");
+    CHECK(set_device(c));
+    CHECK(ensure_map(c));
+    CHECK(ensure_tables(c));
+    CHECK(char_alloc(c));
+    CHECK(char_fits(c));
+    std::vector<snes::RefitFit> fit;
+    uint32_t unique = 0;
+    CHECK(char_fits_read(c, fit, &unique));
+    for (uint32_t j = 0; j < n; j++)
+        if (!fit[reps[j]].eligible) return fail(SNES_ERR_ARG, "not the representative of an eligible class (at least two tiles sharing a character, none of them pinned)");
+    uint32_t group = tile_group(c) < kTileGroup ? tile_group(c) : kTileGroup;
+    if (n < group) group = n;
+    const uint8_t *base_map = nullptr;
+    CHECK(tile_prepare(c, group, &base_map, true));
+    snesimage_tilework &t = *c->tile;
+    double inc = 0.0;
+    HIPCHK(hipMemcpyAsync(&inc, c->d_inc_err, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    for (uint32_t c0 = 0; c0 < n; c0 += group) {
+        const uint32_t nc = n - c0 < group ? n - c0 : group;
+        HIPCHK(hipMemcpyAsync(c->chr->rcalls, reps + c0, sizeof(uint16_t) * nc, hipMemcpyHostToDevice, c->stream));
+        CHECK(refit_score_group(c, nc, t.errs));
+        HIPCHK(hipMemcpyAsync(errors + c0, t.errs, sizeof(double) * nc, hipMemcpyDeviceToHost, c->stream));
+        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out + (size_t)c0 * c->npx, t.lmaps, c->npx * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint32_t j = 0; j < n; j++) if (!fit[reps[j]].differs) errors[j] = inc; // the candidate is the stored map: a refit call would not score it
+    return SNES_OK;
+}
+
+int32_t snesimage_refit_characters(snesimage_ctx *c, uint32_t window, snesimage_refit_result *log, uint32_t log_cap, uint32_t *calls, uint32_t *accepted, uint32_t *unique,
+                                   snesimage_run_stats *stats) {
+    CHECK(char_check(c));
+    CHECK(set_device(c));
+    CHECK(ensure_map(c));
+    CHECK(ensure_tables(c));
+    CHECK(char_alloc(c));
+    CHECK(char_fits(c)); // the snapshot: w.rep, w.flip, w.fits and w.fit hold for the whole sweep
+    snesimage_charwork &w = *c->chr;
+    std::vector<snes::RefitFit> fit;
+    uint32_t U = 0;
+    CHECK(char_fits_read(c, fit, &U));
+    const uint32_t ntile = char_ntile(c);
+    std::vector<uint16_t> elig, todo; // the calls in order; those that are scored
+    for (uint32_t r = 0; r < ntile; r++) if (fit[r].eligible) { elig.push_back((uint16_t)r); if (fit[r].differs) todo.push_back((uint16_t)r); }
+    snesimage_run_stats S{};
+    uint32_t n_acc = 0, done = 0; // done: calls logged so far
+    auto report = [&]() { if (calls) *calls = (uint32_t)elig.size(); if (accepted) *accepted = n_acc; if (unique) *unique = U; if (stats) *stats = S; };
+    if (elig.empty()) { report(); return SNES_OK; }
+    uint32_t kmax = tile_group(c) < kTileGroup ? tile_group(c) : kTileGroup;
+    if (kmax > todo.size()) kmax = (uint32_t)todo.size();
+    if (window == 1) kmax = kmax ? 1 : 0; else if (window > 1 && window < kmax) kmax = window;
+    if (kmax) { const uint8_t *base_map = nullptr; CHECK(tile_prepare(c, kmax, &base_map, true)); } // (every allocation comes before the first commit)
+    else { CHECK(ensure_source(c)); CHECK(ensure_incumbent(c)); }                                   // nothing to score: the records still carry the incumbent
+    double inc = 0.0;
+    HIPCHK(hipMemcpyAsync(&inc, c->d_inc_err, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    auto put = [&](const snes::RefitLog &r) { if (log && done < log_cap) memcpy(log + done, &r, sizeof(r)); done++; S.calls++; };
+    auto skip_until = [&](uint32_t rep_end) { // the skipped calls in front of class rep_end: not scored, the record's error is the incumbent
+        while (done < elig.size() && elig[done] < rep_end) {
+            const snes::RefitFit &f = fit[elig[done]];
+            snes::RefitLog r{}; r.error = inc; r.gain = f.gain; r.rep = elig[done]; r.members = f.members;
+            put(r);
+        }
+    };
+    uint32_t K = window == 0 ? (w.adapt < kmax ? w.adapt : kmax) : kmax;
+    if (K < 1) K = 1;
+    std::vector<unsigned char> h_res;
+    auto run = [&]() -> int32_t {
+        snesimage_tilework &t = *c->tile;
+        uint32_t pos = 0;
+        while (pos < todo.size()) {
+            const uint32_t k = K < todo.size() - pos ? K : (uint32_t)(todo.size() - pos);
+            HIPCHK(hipMemcpyAsync(w.rcalls, todo.data() + pos, sizeof(uint16_t) * k, hipMemcpyHostToDevice, c->stream));
+            CHECK(refit_score_group(c, k, t.errs));
+            hipLaunchKernelGGL(k_refit_commit, dim3(1), dim3(1024), 0, c->stream, (const double *)t.errs, (const uint16_t *)w.rcalls, (int)k, (const snes::RefitFit *)w.fit, (const uint8_t *)t.lmaps,
+                               (int)c->npx, c->d_map, c->d_inc_err, reinterpret_cast<snes::RefitLog *>(w.rresult + 16), reinterpret_cast<snes::RefitWinRes *>(w.rresult));
+            HIPCHK(hipGetLastError());
+            h_res.resize(16 + sizeof(snes::RefitLog) * (size_t)k);
+            HIPCHK(hipMemcpyAsync(h_res.data(), w.rresult, h_res.size(), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream)); // the one synchronisation of the window
+            snes::RefitWinRes res; memcpy(&res, h_res.data(), sizeof(res));
+            const uint32_t used = (uint32_t)res.consumed;
+            if (used < 1 || used > k || res.accepted >= (int32_t)used) return fail(SNES_ERR_HIP, "refit window: bad commit record");
+            for (uint32_t i = 0; i < used; i++) {
+                snes::RefitLog r; memcpy(&r, h_res.data() + 16 + sizeof(r) * i, sizeof(r));
+                skip_until(todo[pos + i]);
+                put(r);
+            }
+            S.windows += 1; S.scored += k; S.useful += used;
+            if (res.accepted >= 0) { // as snesimage_reduce_characters leaves it: a stored map whose error is known
+                snes::RefitLog r; memcpy(&r, h_res.data() + 16 + sizeof(r) * (size_t)res.accepted, sizeof(r));
+                inc = r.error;
+                n_acc++; S.accepted += 1;
+                c->pack_valid = false; c->sp.plist_valid = false; c->epoch++; c->epoch_by_commit = false;
+                c->map_synced = false; c->map_pending = false; c->inc_valid = true; c->best_valid = false;
+            }
+            pos += used;
+            if (window == 0) { K = w.policy.next(used, res.accepted >= 0 ? 1u : 0u, kmax < 2 ? kmax : 2u, kmax, 1, k, 0.2); if (K > kmax) K = kmax; if (K < 1) K = 1; w.adapt = K; }
+        }
+        return SNES_OK;
+    };
+    int32_t rc = kmax ? run() : SNES_OK;
+    if (rc != SNES_OK) { // a window failed: what it left in the map is unknown, the calls accepted before it stand
+        c->pack_valid = false; c->sp.plist_valid = false; c->epoch++; c->epoch_by_commit = false;
+        c->map_synced = false; c->map_pending = false; c->inc_valid = false; c->best_valid = false;
+        report();
+        return rc;
+    }
+    skip_until(ntile);
+    if (n_acc) { // two classes may have become equal: U of the map as it is now
+        snes::CharInfo info{};
+        rc = char_classes(c);
+        if (rc == SNES_OK) {
+            if (hipMemcpyAsync(&info, w.info, sizeof(info), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(SNES_ERR_HIP, "refit sweep: the character count could not be read");
+            else U = info.unique;
+        }
+    }
+    report();
+    return rc;
 }
 
 // keys sorted, no spaces, as snesimage_as_json: character, characters, hflip, palette, vflip

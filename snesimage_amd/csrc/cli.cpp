@@ -20,6 +20,8 @@
 // --max-tiles N merges tiles after the last optimizer call until at most N distinct characters are left (the VRAM budget;
 // include/snesimage_hip.h: snesimage_reduce_characters), --merge-shortlist K sets how many merges each step scores, and
 // --tilemap FILE writes the characters and the tilemap (snesimage_as_tilemap_json), with or without --max-tiles.
+// --refit-tiles N runs up to N refit sweeps behind that (snesimage_refit_characters): every shared character is refitted to all
+// the tiles that use it, and the refit is kept where the error falls.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -88,6 +90,9 @@ void usage() {
             "                           under the tilemap's flips count once); each merge is the one with the lowest error among the\n"
             "                           --merge-shortlist cheapest by colour distance; not with --share or --devices\n"
             "      --merge-shortlist <K>  merges scored per step, 1..64 [default: 16: a choice, not a measurement]; needs --max-tiles\n"
+            "      --refit-tiles <N>    behind --max-tiles (or the last optimizer call), up to N sweeps (1..16) that refit every shared character\n"
+            "                           to all the tiles using it and keep a refit where the error falls; stops after a sweep that accepts\n"
+            "                           nothing; not with --share or --devices\n"
             "      --tilemap <F>        write the distinct characters and the tilemap (character, hflip, vflip, palette per tile) as JSON;\n"
             "                           not with --share or --devices\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
@@ -175,8 +180,8 @@ int main(int argc, char **argv) {
     uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, tile_every = 0, window = 0; // src/config.rs:13-18 defaults
     uint64_t seed = 1;
     int device = 0;
-    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg;
-    bool max_tiles_given = false, merge_short_given = false; uint32_t max_tiles = 0, merge_short = 0;
+    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg, refit_arg;
+    bool max_tiles_given = false, merge_short_given = false, refit_given = false; uint32_t max_tiles = 0, merge_short = 0, refit_sweeps = 0;
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
@@ -207,6 +212,7 @@ int main(int argc, char **argv) {
         else if (a == "--resume") resume_file = need("--resume");
         else if (a == "--max-tiles") { max_tiles_given = true; max_tiles_arg = need("--max-tiles"); }
         else if (a == "--merge-shortlist") { merge_short_given = true; merge_short_arg = need("--merge-shortlist"); }
+        else if (a == "--refit-tiles") { refit_given = true; refit_arg = need("--refit-tiles"); }
         else if (a == "--tilemap") tilemap_file = need("--tilemap");
         else if (a == "--share") {
             const std::string v = need("--share");
@@ -224,10 +230,10 @@ int main(int argc, char **argv) {
         const char *bad = !devices.empty() ? "'--devices'" : (reassign_every ? "'--reassign-tiles'" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--tile-moves <K>' cannot be used with %s\n", bad); return 2; }
     }
-    if (max_tiles_given || merge_short_given || !tilemap_file.empty()) { // said before any file or device is touched
+    if (max_tiles_given || merge_short_given || refit_given || !tilemap_file.empty()) { // said before any file or device is touched
         char *end = nullptr;
         if (merge_short_given && !max_tiles_given) { fprintf(stderr, "error: '--merge-shortlist <K>' needs '--max-tiles <N>'\n"); return 2; }
-        const char *opt = max_tiles_given ? "--max-tiles <N>" : "--tilemap <F>";
+        const char *opt = max_tiles_given ? "--max-tiles <N>" : (refit_given ? "--refit-tiles <N>" : "--tilemap <F>");
         const char *bad = !shares.empty() ? "'--share'" : (!devices.empty() ? "'--devices'" : nullptr); // characters are counted in one image on one device
         if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
         if (max_tiles_given) {
@@ -239,6 +245,11 @@ int main(int argc, char **argv) {
             const unsigned long k = strtoul(merge_short_arg.c_str(), &end, 10);
             if (merge_short_arg.empty() || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--merge-shortlist <K>': expected 1..64\n", merge_short_arg.c_str()); return 2; }
             merge_short = (uint32_t)k;
+        }
+        if (refit_given) {
+            const unsigned long n = strtoul(refit_arg.c_str(), &end, 10);
+            if (refit_arg.empty() || *end || n < 1 || n > 16) { fprintf(stderr, "error: invalid value '%s' for '--refit-tiles <N>': expected 1..16\n", refit_arg.c_str()); return 2; }
+            refit_sweeps = (uint32_t)n;
         }
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
@@ -477,6 +488,17 @@ int main(int argc, char **argv) {
         log_info("Characters: " + std::to_string(u0) + " -> " + std::to_string(u1) + " in " + std::to_string(merges) + " merges (budget " + std::to_string(max_tiles) + ")");
         log_info("Error: " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (u1 > max_tiles) log_info("No tile is left that may be merged: the budget is not met");
+    }
+    for (uint32_t sweep = 0; sweep < refit_sweeps; sweep++) { // behind the merges, in front of everything that is written: a refit is the last stage too
+        uint32_t n_calls = 0, n_acc = 0, u1 = 0;
+        double e0 = 0.0, e1 = 0.0;
+        snesimage_run_stats rs{};
+        if (snesimage_error(ctx, &e0) != 0 || snesimage_refit_characters(ctx, 0, nullptr, 0, &n_calls, &n_acc, &u1, &rs) != 0 || snesimage_error(ctx, &e1) != 0)
+            die(std::string("Unable to refit characters: ") + snesimage_last_error());
+        const uint32_t skipped = n_calls - (uint32_t)rs.useful;
+        log_info("Refit sweep " + std::to_string(sweep + 1) + ": " + std::to_string(n_calls) + " calls, " + std::to_string(n_acc) + " accepted, " + std::to_string(skipped) + " skipped; error " +
+                 fmt_f64(e0) + " -> " + fmt_f64(e1) + "; " + std::to_string(u1) + " characters");
+        if (n_acc == 0) break;
     }
     log_info("Writing output to " + target); // src/lib.rs:1000-1002
     write_json(ctx, target);

@@ -228,4 +228,135 @@ __global__ __launch_bounds__(64) void k_merge_commit(const double *__restrict__ 
     }
 }
 
+// ---- the refit: each shared character fitted to all the tiles that use it -----------------------------------------------------
+//
+// A class of the snapshot (rep[], flip[] as k_char_classes left them) is ELIGIBLE if it has at least two members and none is
+// pinned.  Its FIT gives every position q of the representative's orientation the map value v that costs least over all
+// members, each read through its own subpalette and flip: cost(q, v) = sum over members m of red_mean_key(original pixel
+// q ^ mask(flip[m]) of tile m, entry tile_pal[m] * S + v), ties to the lowest v.  The candidate map (k_refit_maps) goes through
+// the map-reading scorer as a merge does, and k_refit_commit applies the window's first call that beats the incumbent.
+
+struct RefitFit { unsigned long long gain; uint16_t members; uint8_t eligible, differs; uint32_t pad; };      // per tile; all zero unless the tile represents an eligible class
+struct RefitLog { double error; unsigned long long gain; uint16_t rep, members; uint8_t changed, scored, pad[2]; }; // = snesimage_refit_result
+struct RefitWinRes { int32_t consumed, accepted; };  // calls that took effect; the one that accepted (-1: none)
+
+__device__ inline int flip_mask(int f) { return ((f & 1) ? 7 : 0) | ((f & 2) ? 56 : 0); }
+__device__ inline int tile_px(int t, int p, int W) { return ((t >> 5) * 8 + (p >> 3)) * W + (t & 31) * 8 + (p & 7); }
+
+// The fit of the class tile t represents.  grid = tiles, block 256: thread (q = tid & 63, lane group = tid >> 6) takes the
+// values v = lane group, + 4, ... of position q, sums each over the members in 64 bits (a key stays below 2^29, a class has at
+// most 1,024 members: below 2^39) and keeps the lowest (cost << 8 | v); the four lane groups meet through LDS.
+// The members' tile, flip and subpalette are listed in LDS (4 KB); their original pixels come from L2.
+__global__ __launch_bounds__(256) void k_refit_fit(const uint8_t *__restrict__ orig, const uint8_t *__restrict__ map, int W, const uint8_t *__restrict__ pinned, const uint16_t *__restrict__ rep,
+                                                  const uint8_t *__restrict__ flip, const uint16_t *__restrict__ csize, const uint8_t *__restrict__ tile_pal, const uint32_t *__restrict__ pal_rgb8,
+                                                  int S, int ncol, int ntile, uint8_t *__restrict__ fits, RefitFit *__restrict__ fit) {
+    __shared__ uint16_t s_tile[1024];
+    __shared__ uint8_t s_mask[1024], s_sub[1024];
+    __shared__ uint32_t s_pal[256];
+    __shared__ unsigned long long s_best[4][64], s_cur[64];
+    __shared__ int s_n, s_pin;
+    const int t = blockIdx.x, tid = threadIdx.x;
+    if ((int)rep[t] != t || csize[t] < 2) { // (the same for the whole block)
+        if (tid == 0) { RefitFit z{}; fit[t] = z; }
+        if (tid < 64) fits[t * 64 + tid] = 0;
+        return;
+    }
+    if (tid == 0) { s_n = 0; s_pin = 0; }
+    for (int e = tid; e < ncol && e < 256; e += 256) s_pal[e] = pal_rgb8[e];
+    __syncthreads();
+    for (int u = tid; u < ntile; u += 256) {
+        if ((int)rep[u] != t) continue;
+        const int i = atomicAdd(&s_n, 1); // (the order of the list does not matter: the sums are integers)
+        if (i < 1024) { s_tile[i] = (uint16_t)u; s_mask[i] = (uint8_t)flip_mask(flip[u]); s_sub[i] = tile_pal[u]; }
+        if (pinned[u]) s_pin = 1;
+    }
+    __syncthreads();
+    const int n = s_n < 1024 ? s_n : 1024;
+    if (s_pin) { // a pinned member: the class is never changed
+        if (tid == 0) { RefitFit z{}; fit[t] = z; }
+        if (tid < 64) fits[t * 64 + tid] = 0;
+        return;
+    }
+    const int q = tid & 63, lg = tid >> 6;
+    const int cur = map[tile_px(t, q, W)];
+    const int cur_v = cur < S ? cur : S - 1; // (a stored map holds values below S)
+    unsigned long long best = kCharNone;
+    for (int v = lg; v < S; v += 4) {
+        unsigned long long cost = 0;
+        for (int i = 0; i < n; i++) {
+            const int e = (int)s_sub[i] * S + v;
+            const uint32_t px = reinterpret_cast<const uint32_t *>(orig)[tile_px((int)s_tile[i], q ^ (int)s_mask[i], W)] & 0x00ffffffu;
+            cost += red_mean_key(s_pal[e < 256 ? e : 255], px);
+        }
+        const unsigned long long k = (cost << 8) | (unsigned)v;
+        best = k < best ? k : best; // v ascends: the lowest v of equal costs stays
+        if (v == cur_v) s_cur[q] = cost;
+    }
+    s_best[lg][q] = best;
+    __syncthreads();
+    if (tid < 64) { // one wave
+        unsigned long long m = s_best[0][q];
+#pragma unroll
+        for (int i = 1; i < 4; i++) m = s_best[i][q] < m ? s_best[i][q] : m;
+        const int fitted = (int)(m & 0xffu);
+        unsigned long long g = s_cur[q] - (m >> 8);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) g += __shfl_xor(g, o, 64);
+        const unsigned long long diff = __ballot(fitted != cur);
+        fits[t * 64 + q] = (uint8_t)fitted;
+        if (q == 0) { RefitFit r{}; r.gain = g; r.members = (uint16_t)n; r.eligible = 1; r.differs = diff != 0ull ? 1 : 0; fit[t] = r; }
+    }
+}
+
+// A refit candidate's palette_map: the stored map with every member m of class reps[cand] rewritten to
+// fitted[p ^ mask(flip[m])]; and the pair (rep, its own subpalette) for k_tile_full, which so substitutes nothing.
+// grid = candidates, block 256: a wave per member tile, a lane per pixel.
+__global__ __launch_bounds__(256) void k_refit_maps(const uint16_t *__restrict__ reps, const uint8_t *__restrict__ base_map, const uint16_t *__restrict__ rep, const uint8_t *__restrict__ flip,
+                                                   const uint8_t *__restrict__ fits, const uint8_t *__restrict__ tile_pal, int W, int npx, uint8_t *__restrict__ lmaps,
+                                                   uint16_t *__restrict__ tiles, uint8_t *__restrict__ subs) {
+    const int cand = blockIdx.x, tid = threadIdx.x, ntile = npx >> 6;
+    int r = reps[cand];
+    r = r < ntile ? r : 0; // (the host hands over representatives of the image only)
+    const uint4 *src = reinterpret_cast<const uint4 *>(base_map);
+    uint4 *dst = reinterpret_cast<uint4 *>(lmaps + (size_t)cand * npx);
+    for (int i = tid; i < npx / 16; i += 256) dst[i] = src[i];
+    __syncthreads(); // the copy is in place before the members' bytes are replaced
+    const int p = tid & 63;
+    for (int u = tid >> 6; u < ntile; u += 4) {
+        if ((int)rep[u] != r) continue; // (the same for the whole wave)
+        lmaps[(size_t)cand * npx + tile_px(u, p, W)] = fits[r * 64 + (p ^ flip_mask(flip[u]))];
+    }
+    if (tid == 0) { tiles[cand] = (uint16_t)r; subs[cand] = tile_pal[r]; }
+}
+
+// The window's refit calls in order (lib.rs:216-219 per call: taken iff its error is below the incumbent, strict): every call up
+// to and including the first that accepts is logged; that one's map and error become the image's.  One block.
+__global__ __launch_bounds__(1024) void k_refit_commit(const double *__restrict__ errs, const uint16_t *__restrict__ reps, int ncalls, const RefitFit *__restrict__ fit,
+                                                      const uint8_t *__restrict__ lmaps, int npx, uint8_t *__restrict__ map, double *__restrict__ inc_err, RefitLog *__restrict__ log,
+                                                      RefitWinRes *__restrict__ res) {
+    __shared__ int s_win;
+    if (threadIdx.x == 0) {
+        const double inc = *inc_err;
+        int win = -1, used = ncalls;
+        for (int i = 0; i < ncalls && win < 0; i++) {
+            const double e = errs[i];
+            const RefitFit f = fit[reps[i]];
+            const bool take = e < inc;
+            RefitLog r{};
+            r.error = take ? e : inc; r.gain = f.gain; r.rep = reps[i]; r.members = f.members; r.changed = take ? 1 : 0; r.scored = 1;
+            log[i] = r;
+            if (take) { win = i; used = i + 1; }
+        }
+        res->consumed = used; res->accepted = win;
+        s_win = win;
+    }
+    __syncthreads(); // the records are written before the state changes hands
+    const int win = s_win;
+    if (win < 0) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(lmaps + (size_t)win * npx); // (outside the members' tiles it is the stored map itself)
+    uint4 *dst = reinterpret_cast<uint4 *>(map);
+    for (int i = threadIdx.x; i < npx / 16; i += 1024) dst[i] = src[i];
+    if (threadIdx.x == 0) *inc_err = errs[win];
+}
+
 } // namespace snes
