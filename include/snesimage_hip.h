@@ -428,6 +428,67 @@ int32_t snesimage_score_refits(snesimage_ctx *ctx, const uint16_t *reps, uint32_
 int32_t snesimage_refit_characters(snesimage_ctx *ctx, uint32_t window, snesimage_refit_result *log, uint32_t log_cap,
                                    uint32_t *calls, uint32_t *accepted, uint32_t *unique, snesimage_run_stats *stats);
 
+/* The character budget of a shared-palette set — NOT a reference method.  On the console everything drawn on one background
+ * reads one CGRAM, which the set models, and one VRAM character area: the two screens of a 512-wide level or the frames of an
+ * animated background share one tileset.  These calls count and reduce the characters of ALL members together.  Everything is
+ * an integer except the objective; the terms are those of the character budget above, extended as follows.
+ *   GLOBAL TILE: a set of F members, each with ntile = 32 * h/8 tiles, has G = F * ntile global tiles, numbered
+ *     g = member * ntile + tile (member-major).  The budget takes sets with G <= 8192 (eight frames of 256 x 256, nine of
+ *     256 x 224); beyond that every call below answers SNES_ERR_UNSUPPORTED before touching anything.  The cap exists so that
+ *     (cost, recipient, donor, flip) orders as one 64-bit key: a tile's cost is at most 64 * 299,505,150 < 2^35, which leaves
+ *     13 bits each for recipient and donor.  The packing is internal; the order of the tuple is the contract.
+ *   CHARACTER, FLIP, PINNED: unchanged, per tile, from its member's stored map and source alpha (sets refuse backdrop members:
+ *     there is no backdrop value).
+ *   SAME CHARACTER, rep(g), flip_of(g), U: as above but over all G tiles: rep(g) is the LOWEST GLOBAL INDEX of g's class, U the
+ *     number of classes of the whole set.  A character that occurs in two members counts once.
+ *   MERGE CANDIDATE (gt, gb, f), gt != gb, both unpinned: the recipient's member takes, in tile gt, the map values of tile gb
+ *     — which may belong to ANOTHER member — under flip f.  The recipient keeps its own subpalette; nothing else changes, and
+ *     no other member's map changes.  Its MEMBER ERROR e is error() of the recipient member's stored map with that tile
+ *     rewritten (no optimize(), no re-dither).  Its INCREASE is d = e - inc_m, inc_m that member's incumbent error: one binary64
+ *     subtraction; d may be negative.  Its PROXY COST is that of the single-image budget: the integer red-mean key summed over
+ *     the recipient's 64 ORIGINAL pixels against the entries of the recipient's own subpalette that the donor's values name.
+ *   ONE REDUCTION STEP with shortlist length K: recipients are the unpinned tiles ALONE in their set-wide class; a recipient's
+ *     donors are the unpinned class representatives other than itself.  The shortlist is the K candidates lowest in
+ *     (cost, gt, gb, f), fewer if fewer exist.  All are scored, each in its recipient's member.  The winner is the lowest
+ *     (d, rank in the shortlist) — members' errors differ in size, their increases compare — a NaN never wins; it is applied
+ *     UNCONDITIONALLY.  Afterwards the recipient member's map is the candidate's and its incumbent the candidate's scored bits;
+ *     E is the members' incumbents summed in member order, as snesimage_shared_error sums; U has fallen by exactly one.
+ *   REDUCTION to max_unique: steps while U > max_unique and a pair exists.  Running out of pairs is no error.
+ *   STATE AFTERWARDS: every member that received a merge is as after snesimage_reduce_characters — a stored map, its error
+ *     known, its epoch advanced — and the set records the new epochs: it stays intact.  snesimage_shared_error returns the last
+ *     record's `error` bit for bit; the members' as_json, get_palette_map and as_rgba read the merged maps.  REDUCTION IS THE
+ *     LAST STAGE OF A RUN: every set call that optimizes — snesimage_shared_step*, _run_slots, _slots_reserve, _tile_sweep,
+ *     _reassign_tiles, the initialisers and the palette setter — first re-runs optimize() on every member that holds a merged
+ *     map and then behaves exactly as on a set that never reduced.  snesimage_shared_error, _score_candidates and the calls
+ *     below leave the merged maps.  A budget already met takes no step and leaves set and members untouched bit for bit.
+ * Refusals mirror the single-image calls: SNES_ERR_ARG for null pointers, a member or tile out of range, a pinned tile named,
+ * gt == gb, f > 3, max_unique == 0, shortlist > 64; SNES_ERR_STATE as every set call (a member changed outside the set, or a
+ * member destroyed: that is answered before any member is read); SNES_ERR_HIP after a failed workspace allocation, set and
+ * members usable and unchanged.  If a step fails the steps before it stand and are reported; the members that had a
+ * candidate in it hold "a stored map of unknown error". */
+typedef struct { double error, member_error; uint64_t cost; uint16_t member, tile, donor_member, donor, unique;
+                 uint8_t flip, rank; uint8_t pad[4]; } snesimage_shared_merge_result; /* 40 bytes; error = E after the step, member_error = e, unique = U after it */
+/* U, and optionally rep (G, global indices), flip_of (G) and the characters (G * 64) of the set as it stands. */
+int32_t snesimage_shared_characters(snesimage_shared *set, uint32_t *unique, uint16_t *rep /*G, global, opt*/, uint8_t *flip /*G, opt*/,
+                                    uint8_t *chars /*G*64, opt*/);
+/* The shortlist a reduction step with length k (1..64, 0 = 16) would score, in rank order; *n = min(k, candidates that exist).
+ * Output arrays (each optional) hold k entries: recipient (member, tile), donor (member, tile), flip, proxy cost.  State unchanged. */
+int32_t snesimage_shared_merge_shortlist(snesimage_shared *set, uint32_t k, uint16_t *members, uint16_t *tiles, uint16_t *donor_members,
+                                         uint16_t *donors, uint8_t *flips, uint64_t *costs, uint32_t *n);
+/* errors[j] = the member error e of n explicit candidates — any unpinned pair — against the current state, which is left
+ * unchanged.  A candidate that changes nothing returns its member's incumbent bit for bit.  maps_out (optional, n*w*h bytes):
+ * each candidate's palette_map of the recipient's member.  Host pointers; synchronous. */
+int32_t snesimage_shared_score_merges(snesimage_shared *set, const uint16_t *members, const uint16_t *tiles, const uint16_t *donor_members,
+                                      const uint16_t *donors, const uint8_t *flips, uint32_t n, double *errors /*e: the recipient member's*/,
+                                      uint8_t *maps_out /*opt, n*w*h*/);
+/* The reduction.  log (optional): the first log_cap steps' records; *merges: steps taken; *unique: U afterwards. */
+int32_t snesimage_shared_reduce_characters(snesimage_shared *set, uint32_t max_unique, uint32_t shortlist /*1..64, 0 = 16*/,
+                                           snesimage_shared_merge_result *log, uint32_t log_cap, uint32_t *merges, uint32_t *unique);
+/* The tilemap of the set as it stands, conventions of snesimage_as_tilemap_json: "characters" is ONE list for the whole set,
+ * classes ordered by representative, each in the representative's orientation; "character", "hflip", "palette" and "vflip" are
+ * lists of F lists, in member order. */
+int64_t snesimage_shared_as_tilemap_json(snesimage_shared *set, char *out, int64_t cap);
+
 /* State access (the reference mutates these fields directly: lib.rs:1015 and the GUI). */
 int32_t snesimage_get_tile_palettes(snesimage_ctx *ctx, uint8_t *out /*1024*/);
 int32_t snesimage_set_tile_palettes(snesimage_ctx *ctx, const uint8_t *in /*1024*/);

@@ -42,6 +42,12 @@ class MergeResult(C.Structure):
                 ("unique", C.c_uint16)]
 
 
+class SharedMergeResult(C.Structure):
+    """snesimage_shared_merge_result: one step of a set's character reduction."""
+    _fields_ = [("error", C.c_double), ("member_error", C.c_double), ("cost", C.c_uint64), ("member", C.c_uint16), ("tile", C.c_uint16),
+                ("donor_member", C.c_uint16), ("donor", C.c_uint16), ("unique", C.c_uint16), ("flip", C.c_uint8), ("rank", C.c_uint8), ("pad", C.c_uint8 * 4)]
+
+
 class RefitResult(C.Structure):
     """snesimage_refit_result: one call of a refit sweep."""
     _fields_ = [("error", C.c_double), ("gain", C.c_uint64), ("rep", C.c_uint16), ("members", C.c_uint16), ("changed", C.c_uint8), ("scored", C.c_uint8),
@@ -73,6 +79,11 @@ SIGNATURES = [
     ("snesimage_character_fits", C.c_int32, [C.c_void_p, _u16p, _u16p, _u64p, _u8p, _u32p]),
     ("snesimage_score_refits", C.c_int32, [C.c_void_p, _u16p, C.c_uint32, _f64p, _u8p]),
     ("snesimage_refit_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(RefitResult), C.c_uint32, _u32p, _u32p, _u32p, C.POINTER(RunStats)]),
+    ("snesimage_shared_characters", C.c_int32, [C.c_void_p, _u32p, _u16p, _u8p, _u8p]),
+    ("snesimage_shared_merge_shortlist", C.c_int32, [C.c_void_p, C.c_uint32, _u16p, _u16p, _u16p, _u16p, _u8p, _u64p, _u32p]),
+    ("snesimage_shared_score_merges", C.c_int32, [C.c_void_p, _u16p, _u16p, _u16p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_shared_reduce_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SharedMergeResult), C.c_uint32, _u32p, _u32p]),
+    ("snesimage_shared_as_tilemap_json", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
     ("snesimage_score_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _f64p]),
     ("snesimage_score_candidates_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]),

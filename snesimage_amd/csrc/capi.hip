@@ -10,6 +10,7 @@
 #include "kernels_shared.hpp"
 #include "kernels_tile.hpp"
 #include "kernels_char.hpp"
+#include "kernels_char_set.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1733,4 +1734,5 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "group_host.inc"
 #include "tile_host.inc"
 #include "char_host.inc"
+#include "shared_char_host.inc"
 #include "ordered_host.inc"

@@ -22,6 +22,9 @@
 // --tilemap FILE writes the characters and the tilemap (snesimage_as_tilemap_json), with or without --max-tiles.
 // --refit-tiles N runs up to N refit sweeps behind that (snesimage_refit_characters): every shared character is refitted to all
 // the tiles that use it, and the refit is kept where the error falls.
+// --max-set-tiles N (with --share) is the budget of the whole set: the frames share one VRAM character area, so their characters
+// are counted together and a tile may take its indices from a tile of another frame (snesimage_shared_reduce_characters);
+// --set-tilemap FILE writes the set's characters and one tilemap per frame (snesimage_shared_as_tilemap_json).
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -90,11 +93,16 @@ void usage() {
             "                           under the tilemap's flips count once); each merge is the one with the lowest error among the\n"
             "                           --merge-shortlist cheapest by colour distance; not with --share or --devices\n"
             "      --merge-shortlist <K>  merges scored per step, 1..64 [default: 16: a choice, not a measurement]; needs --max-tiles\n"
+            "                           or --max-set-tiles\n"
             "      --refit-tiles <N>    behind --max-tiles (or the last optimizer call), up to N sweeps (1..16) that refit every shared character\n"
             "                           to all the tiles using it and keep a refit where the error falls; stops after a sweep that accepts\n"
             "                           nothing; not with --share or --devices\n"
             "      --tilemap <F>        write the distinct characters and the tilemap (character, hflip, vflip, palette per tile) as JSON;\n"
             "                           not with --share or --devices\n"
+            "      --max-set-tiles <N>  with --share: after the last optimizer call, merge tiles until the frames of the set hold at most N\n"
+            "                           distinct characters together (1..8192; one VRAM character area for all frames): a tile may take\n"
+            "                           its indices from a tile of another frame; at most 8192 tiles in all; not with --devices\n"
+            "      --set-tilemap <F>    with --share: write the set's distinct characters and one tilemap per frame as JSON\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
             "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only\n"
@@ -180,8 +188,8 @@ int main(int argc, char **argv) {
     uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, tile_every = 0, window = 0; // src/config.rs:13-18 defaults
     uint64_t seed = 1;
     int device = 0;
-    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg, refit_arg;
-    bool max_tiles_given = false, merge_short_given = false, refit_given = false; uint32_t max_tiles = 0, merge_short = 0, refit_sweeps = 0;
+    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg, refit_arg, set_tilemap_file, max_set_arg;
+    bool max_tiles_given = false, merge_short_given = false, refit_given = false, max_set_given = false; uint32_t max_tiles = 0, merge_short = 0, refit_sweeps = 0, max_set_tiles = 0;
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
@@ -214,6 +222,8 @@ int main(int argc, char **argv) {
         else if (a == "--merge-shortlist") { merge_short_given = true; merge_short_arg = need("--merge-shortlist"); }
         else if (a == "--refit-tiles") { refit_given = true; refit_arg = need("--refit-tiles"); }
         else if (a == "--tilemap") tilemap_file = need("--tilemap");
+        else if (a == "--max-set-tiles") { max_set_given = true; max_set_arg = need("--max-set-tiles"); }
+        else if (a == "--set-tilemap") set_tilemap_file = need("--set-tilemap");
         else if (a == "--share") {
             const std::string v = need("--share");
             const size_t eq = v.find('=');
@@ -232,10 +242,10 @@ int main(int argc, char **argv) {
     }
     if (max_tiles_given || merge_short_given || refit_given || !tilemap_file.empty()) { // said before any file or device is touched
         char *end = nullptr;
-        if (merge_short_given && !max_tiles_given) { fprintf(stderr, "error: '--merge-shortlist <K>' needs '--max-tiles <N>'\n"); return 2; }
+        if (merge_short_given && !max_tiles_given && !max_set_given) { fprintf(stderr, "error: '--merge-shortlist <K>' needs '--max-tiles <N>' or '--max-set-tiles <N>'\n"); return 2; }
         const char *opt = max_tiles_given ? "--max-tiles <N>" : (refit_given ? "--refit-tiles <N>" : "--tilemap <F>");
         const char *bad = !shares.empty() ? "'--share'" : (!devices.empty() ? "'--devices'" : nullptr); // characters are counted in one image on one device
-        if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
+        if (bad && (max_tiles_given || refit_given || !tilemap_file.empty())) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
         if (max_tiles_given) {
             const unsigned long n = strtoul(max_tiles_arg.c_str(), &end, 10);
             if (max_tiles_arg.empty() || *end || n < 1 || n > 1024) { fprintf(stderr, "error: invalid value '%s' for '--max-tiles <N>': expected 1..1024\n", max_tiles_arg.c_str()); return 2; }
@@ -250,6 +260,17 @@ int main(int argc, char **argv) {
             const unsigned long n = strtoul(refit_arg.c_str(), &end, 10);
             if (refit_arg.empty() || *end || n < 1 || n > 16) { fprintf(stderr, "error: invalid value '%s' for '--refit-tiles <N>': expected 1..16\n", refit_arg.c_str()); return 2; }
             refit_sweeps = (uint32_t)n;
+        }
+    }
+    if (max_set_given || !set_tilemap_file.empty()) { // the budget of a set: said before any file or device is touched
+        const char *opt = max_set_given ? "--max-set-tiles <N>" : "--set-tilemap <F>";
+        if (shares.empty()) { fprintf(stderr, "error: '%s' needs '--share <SOURCE=TARGET>': it counts the characters of a set (one image: --max-tiles, --tilemap)\n", opt); return 2; }
+        if (!devices.empty()) { fprintf(stderr, "error: the argument '%s' cannot be used with '--devices'\n", opt); return 2; }
+        if (max_set_given) {
+            char *end = nullptr;
+            const unsigned long n = strtoul(max_set_arg.c_str(), &end, 10);
+            if (max_set_arg.empty() || *end || n < 1 || n > 8192) { fprintf(stderr, "error: invalid value '%s' for '--max-set-tiles <N>': expected 1..8192\n", max_set_arg.c_str()); return 2; }
+            max_set_tiles = (uint32_t)n;
         }
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
@@ -318,6 +339,9 @@ int main(int argc, char **argv) {
         load_source(shares[i].first, ow, oh, shared_rgba[i]);
         if (ow != w || oh != h) die("shared image " + shares[i].first + " is " + std::to_string(ow) + "x" + std::to_string(oh) + ", the source " + std::to_string(w) + "x" + std::to_string(h));
     }
+    if ((max_set_given || !set_tilemap_file.empty()) && (uint64_t)(shares.size() + 1) * (w / 8) * (h / 8) > 8192) // known once the images are decoded: said before the run, not after it
+        die(std::string(max_set_given ? "--max-set-tiles" : "--set-tilemap") + ": the set has " + std::to_string((uint64_t)(shares.size() + 1) * (w / 8) * (h / 8)) +
+            " tiles in all; the character budget of a set takes at most 8192 (eight frames of 256 x 256, nine of 256 x 224)");
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
@@ -500,6 +524,16 @@ int main(int argc, char **argv) {
                  fmt_f64(e0) + " -> " + fmt_f64(e1) + "; " + std::to_string(u1) + " characters");
         if (n_acc == 0) break;
     }
+    if (max_set_given) { // the set's budget, behind the last optimizer call and in front of everything that is written
+        uint32_t u0 = 0, u1 = 0, merges = 0;
+        double e0 = 0.0, e1 = 0.0;
+        if (snesimage_shared_characters(set, &u0, nullptr, nullptr, nullptr) != 0 || snesimage_shared_error(set, &e0) != 0) die(std::string("Unable to count characters: ") + snesimage_last_error());
+        if (snesimage_shared_reduce_characters(set, max_set_tiles, merge_short, nullptr, 0, &merges, &u1) != 0 || snesimage_shared_error(set, &e1) != 0)
+            die(std::string("Unable to merge tiles: ") + snesimage_last_error());
+        log_info("Characters of the set: " + std::to_string(u0) + " -> " + std::to_string(u1) + " in " + std::to_string(merges) + " merges (budget " + std::to_string(max_set_tiles) + ")");
+        log_info("Error: " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        if (u1 > max_set_tiles) log_info("No tile is left that may be merged: the budget is not met");
+    }
     log_info("Writing output to " + target); // src/lib.rs:1000-1002
     write_json(ctx, target);
     for (size_t i = 0; i < shares.size(); i++) {
@@ -516,6 +550,17 @@ int main(int argc, char **argv) {
         fwrite(json.data(), 1, (size_t)need - 1, f);
         fclose(f);
         log_info("Wrote tilemap to " + tilemap_file);
+    }
+    if (!set_tilemap_file.empty()) {
+        const int64_t need = snesimage_shared_as_tilemap_json(set, nullptr, 0);
+        if (need < 0) die(snesimage_last_error());
+        std::vector<char> json((size_t)need);
+        snesimage_shared_as_tilemap_json(set, json.data(), need);
+        FILE *f = fopen(set_tilemap_file.c_str(), "wb");
+        if (!f) die("cannot create " + set_tilemap_file);
+        fwrite(json.data(), 1, (size_t)need - 1, f);
+        fclose(f);
+        log_info("Wrote the set's tilemap to " + set_tilemap_file);
     }
     if (!preview_file.empty()) { // left: source, right: as_rgba() of the result (src/lib.rs:940-957)
         std::vector<uint8_t> result((size_t)w * h * 4), both((size_t)2 * w * h * 4), png;

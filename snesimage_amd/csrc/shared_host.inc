@@ -5,7 +5,8 @@
 // member order, W x F*H — with the point order of the reference's own initialisers over that picture.
 
 struct snesimage_shared_window; // slot windows of the set (shared_window_host.inc)
-namespace { void shared_window_free(snesimage_shared_window *w); }
+struct snesimage_sharedchar;    // workspace of the set's character budget (shared_char_host.inc)
+namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); }
 
 struct snesimage_shared {
     snesimage_batch *b = nullptr;
@@ -14,6 +15,8 @@ struct snesimage_shared {
     double *d_sum = nullptr; uint32_t sum_cap = 0; // snesimage_shared_score_candidates: E_k
     const double **d_tab = nullptr;           // the members' error vectors, for ks_sum
     std::vector<unsigned long long> epoch;    // each member's palette / tile-map generation when the set last touched it
+    snesimage_sharedchar *chr = nullptr;      // the character budget of the set, made on first use
+    bool reduced = false;                     // snesimage_shared_reduce_characters left merged maps: stored maps that are no optimize() of the palette
 };
 
 namespace {
@@ -22,7 +25,10 @@ std::vector<snesimage_ctx *> &members(snesimage_shared *s) { return s->b->ctx; }
 
 // Every set call starts here: the set is intact, and no member was changed behind its back since the set last touched it.
 // wait: the call works on the members outside the batched launches, so the set's stream must be idle first.
-int32_t shared_enter(snesimage_shared *s, bool wait = true) {
+// A character reduction is the last stage of a run: every call that optimizes first gives each member that received a merge
+// its optimize() and its incumbent back (what shared_settle leaves), so the batched launches never meet an unsynced member.
+// keep_merged: the call only reads the members as they stand (the error, the character calls) and leaves the merged maps.
+int32_t shared_enter(snesimage_shared *s, bool wait = true, bool keep_merged = false) {
     if (!s) return fail(SNES_ERR_ARG, "null set");
     if (s->b->dead) return fail(SNES_ERR_STATE, "a member context of this set was destroyed");
     auto &M = members(s);
@@ -30,6 +36,17 @@ int32_t shared_enter(snesimage_shared *s, bool wait = true) {
         if (M[i]->epoch != s->epoch[i] || M[i]->pend || M[i]->win_pend)
             return fail(SNES_ERR_STATE, "member " + std::to_string(i) + " of the set was changed outside it (its palette, tile palettes or map): the members no longer share one state");
     HIPCHK(hipSetDevice(s->b->device));
+    if (s->reduced && !keep_merged) {
+        CHECK(batch_quiesce(s->b));
+        for (auto *c : M) {
+            CHECK(ensure_tables(c));
+            CHECK(ensure_source(c));
+            if (!c->map_synced) CHECK(do_optimize(c));
+            CHECK(ensure_incumbent(c));
+        }
+        for (auto *c : M) HIPCHK(hipStreamSynchronize(c->stream));
+        s->reduced = false;
+    }
     return wait ? batch_quiesce(s->b) : SNES_OK;
 }
 
@@ -215,6 +232,7 @@ void snesimage_shared_destroy(snesimage_shared *s) {
     (void)hipSetDevice(s->b->device);
     if (s->b->stream) (void)hipStreamSynchronize(s->b->stream);
     if (s->win) { shared_window_free(s->win); s->win = nullptr; } // (its slot contexts borrow the members' planes: before the members go)
+    if (s->chr) { shared_char_free(s->chr); s->chr = nullptr; }
     snesimage_batch_destroy(s->b); // (waits for its stream)
     if (s->d_joint) (void)hipFree(s->d_joint);
     if (s->d_sum) (void)hipFree(s->d_sum);
@@ -245,7 +263,7 @@ int32_t snesimage_shared_set_palette_rgb5(snesimage_shared *s, const uint8_t *in
 
 int32_t snesimage_shared_error(snesimage_shared *s, double *out) {
     if (!out) return fail(SNES_ERR_ARG, "null pointer");
-    CHECK(shared_enter(s));
+    CHECK(shared_enter(s, true, true));
     double E = 0.0;
     auto &M = members(s);
     for (size_t i = 0; i < M.size(); i++) {
@@ -263,7 +281,7 @@ int32_t snesimage_shared_error(snesimage_shared *s, double *out) {
 // adds the error vectors in member order on the set's stream.  The members are left unchanged.
 int32_t snesimage_shared_score_candidates(snesimage_shared *s, uint32_t palette, uint32_t index, const uint8_t *rgb5, uint32_t n, double *errors) {
     if (!rgb5 || !errors) return fail(SNES_ERR_ARG, "null pointer");
-    CHECK(shared_enter(s));
+    CHECK(shared_enter(s, true, true)); // (the candidates are remapped from the palette: the stored maps are not read)
     auto &M = members(s);
     CHECK(check_slot(M[0], palette, index));
     if (n == 0) return SNES_OK;

@@ -14,6 +14,10 @@ from . import _ffi
 from .api import METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
 
 
+SHARED_MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("member_error", np.float64), ("cost", np.uint64), ("member", np.uint16), ("tile", np.uint16),
+                                   ("donor_member", np.uint16), ("donor", np.uint16), ("unique", np.uint16), ("flip", np.uint8), ("rank", np.uint8)])
+
+
 class SharedPalette:
     """A set over `images` (OptimizedImage, in member order).  Destroy the set (close) before its members."""
 
@@ -139,6 +143,65 @@ class SharedPalette:
         self._chk(self._L.snesimage_shared_tile_sweep(self._s, int(first_tile), int(n_tiles), int(window), log, C.byref(stats)))
         out = np.array([(r.error, r.sub, r.changed) for r in log[:F * n_tiles]], dtype=TILE_LOG_DTYPE).reshape(F, n_tiles)
         return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    # -- the character budget of the set (not in the reference; include/snesimage_hip.h) ---------------------------
+    def _ntile(self):
+        return (self.images[0].w // 8) * (self.images[0].h // 8)
+
+    def characters(self):
+        """The distinct characters of all members together (global tile g = member * ntile + tile), equal under the tilemap's
+        flips counted once.  Returns (unique, rep[G] as global indices, flip[G], chars[G, 64])."""
+        G = len(self.images) * self._ntile()
+        unique = C.c_uint32(0)
+        rep, flip, chars = np.zeros(G, np.uint16), np.zeros(G, np.uint8), np.zeros((G, 64), np.uint8)
+        self._chk(self._L.snesimage_shared_characters(self._s, C.byref(unique), _p(rep, _ffi._u16p), _p(flip, _ffi._u8p), _p(chars, _ffi._u8p)))
+        return unique.value, rep, flip, chars
+
+    def merge_shortlist(self, k=0):
+        """The k (1..64, 0 = 16) merge candidates lowest in (proxy cost, recipient, donor, flip) over the whole set; the state
+        is left unchanged.  Returns (members, tiles, donor_members, donors, flips, costs), each as long as the shortlist."""
+        cap = 64
+        mem, tiles, dmem, donors = (np.zeros(cap, np.uint16) for _ in range(4))
+        flips, costs = np.zeros(cap, np.uint8), np.zeros(cap, np.uint64)
+        n = C.c_uint32(0)
+        self._chk(self._L.snesimage_shared_merge_shortlist(self._s, int(k), _p(mem, _ffi._u16p), _p(tiles, _ffi._u16p), _p(dmem, _ffi._u16p), _p(donors, _ffi._u16p),
+                                                           _p(flips, _ffi._u8p), _p(costs, _ffi._u64p), C.byref(n)))
+        return tuple(a[:n.value].copy() for a in (mem, tiles, dmem, donors, flips, costs))
+
+    def score_merges(self, members, tiles, donor_members, donors, flips, want_maps=False):
+        """error() of member members[j] with its tile tiles[j] taking the indices of tile donors[j] of member donor_members[j]
+        under flip flips[j], for every j; the state is left unchanged.  Returns errors (float64), or (errors, maps[n, h, w])."""
+        mem, tiles, dmem, donors = (np.ascontiguousarray(a, np.uint16).reshape(-1) for a in (members, tiles, donor_members, donors))
+        flips = np.ascontiguousarray(flips, np.uint8).reshape(-1)
+        if not mem.size == tiles.size == dmem.size == donors.size == flips.size:
+            raise ValueError("members, tiles, donor_members, donors and flips differ in length")
+        errs = np.zeros(mem.size, np.float64)
+        maps = np.zeros((mem.size, self.images[0].h, self.images[0].w), np.uint8) if want_maps else None
+        self._chk(self._L.snesimage_shared_score_merges(self._s, _p(mem, _ffi._u16p), _p(tiles, _ffi._u16p), _p(dmem, _ffi._u16p), _p(donors, _ffi._u16p),
+                                                        _p(flips, _ffi._u8p), mem.size, _p(errs, _ffi._f64p), _p(maps, _ffi._u8p) if want_maps else None))
+        return (errs, maps) if want_maps else errs
+
+    def reduce_characters(self, max_unique, shortlist=0):
+        """Merge tiles until the whole set holds at most max_unique distinct characters (or no eligible pair is left); a donor
+        may sit in another member.  Every merge is the one of the proxy's `shortlist` (1..64, 0 = 16) best that raises its
+        member's error() least.  The last stage of a run: any set call that optimizes replaces the merged maps.  Returns
+        (records, unique): a structured array (SHARED_MERGE_LOG_DTYPE), one record per merge, and the count reached."""
+        cap = len(self.images) * self._ntile()
+        log = (_ffi.SharedMergeResult * cap)()
+        merges, unique = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.snesimage_shared_reduce_characters(self._s, int(max_unique), int(shortlist), log, cap, C.byref(merges), C.byref(unique)))
+        out = np.array([(r.error, r.member_error, r.cost, r.member, r.tile, r.donor_member, r.donor, r.unique, r.flip, r.rank) for r in log[:merges.value]],
+                       dtype=SHARED_MERGE_LOG_DTYPE)
+        return out, unique.value
+
+    def as_tilemap_json(self):
+        """The tilemap of the set: one list of characters, and per member and tile character, hflip, vflip and palette."""
+        need = self._L.snesimage_shared_as_tilemap_json(self._s, None, 0)
+        if need < 0:
+            raise SnesImageError(int(need), self._L.snesimage_last_error().decode())
+        buf = C.create_string_buffer(int(need))
+        self._L.snesimage_shared_as_tilemap_json(self._s, buf, need)
+        return buf.value.decode()
 
     # -- state ------------------------------------------------------------------------------------
     @property
