@@ -489,6 +489,69 @@ int32_t snesimage_shared_reduce_characters(snesimage_shared *set, uint32_t max_u
  * lists of F lists, in member order. */
 int64_t snesimage_shared_as_tilemap_json(snesimage_shared *set, char *out, int64_t cap);
 
+/* The refit of shared characters across the members of a shared-palette set — NOT a reference method.  After a set merge a
+ * character that serves tiles of several frames still carries the indices chosen for one donor tile of one frame.  This is the
+ * refit above over the whole set: each shared character fitted to ALL the tiles of ALL members that use it, decided on the joint
+ * error.  Off unless called; no other entry point changes.  The terms are those of "the refit of shared characters" and of "the
+ * character budget of a shared-palette set" (global tile g = member * ntile + tile; sets hold no backdrop member, so a map value
+ * is a character value - 1 in every unpinned tile; S is the subpalette size).
+ *   SNAPSHOT: at the start of a sweep, the SET-WIDE classes of the members' stored maps as they stand: rep(g) is the lowest
+ *     GLOBAL tile of g's class, flip_of(g) as defined.  An optimize() still owed runs first, as in snesimage_shared_characters;
+ *     merged maps stay.  An ELIGIBLE CLASS has at least 2 global tiles, none of them pinned (in whichever member).  Its tiles, its
+ *     representative r and the flips f_g are fixed for the whole sweep.  Its TOUCHED MEMBERS are the members that hold at least
+ *     one of its tiles.
+ *   FIT of an eligible class: for position q in 0..63 and value v in 0..S-1,
+ *       cost(q, v) = sum over the class's global tiles g = (m, t) of red_mean_key(original pixel q ^ mask(f_g) of tile t of
+ *                                member m, 8-bit expansion of entry tile_palettes_m[t] * S + v of the shared palette),
+ *     summed in a uint64_t: at most 8,192 terms of at most 299,505,150 each, so below 2^42, and cost << 8 | v still fits.
+ *     fitted[q] = the LOWEST v among the minima of cost(q, .); cur[q] = the representative's map value at q;
+ *     gain = sum over q of cost(q, cur[q]) - cost(q, fitted[q]) >= 0.  The fit reads the members' ORIGINALS, never an
+ *     ordered-dither target, and is this integer key whatever SNES_PERCEPTUAL says.  It depends on the snapshot, the originals
+ *     and the palette only: the fits of all classes of a sweep are computed once, up front.
+ *   REFIT CALL on eligible class r: if fitted == cur the call is SKIPPED — not scored, changed = 0, the record's error is E.
+ *     Otherwise the candidate gives every tile g of the class map(g; p) := fitted[p ^ mask(f_g)] in its own member's stored map;
+ *     nothing else changes.  For each touched member i, e_i is error() of that member's candidate map (no optimize(), no
+ *     re-dither).  With inc_i the members' incumbent errors, E' = sum over i of (e_i if i is touched, else inc_i) and
+ *     E = sum over i of inc_i, both summed in member order, left to right, with plain + (as snesimage_shared_error sums).  The
+ *     candidate is taken iff E' < E, strict (lib.rs:216-219 applied to the joint error, as every set call decides); a NaN in
+ *     any e_i never wins.  On acceptance every touched member takes its candidate map and e_i as its incumbent.  A SINGLE
+ *     MEMBER'S ERROR MAY RISE as long as E falls: the set is one picture budget, and the decision is the set's.
+ *   REFIT SWEEP: the calls on the eligible classes in ascending global rep, each seeing the maps and the incumbents the call
+ *     before left (classes are disjoint sets of tiles).  U never rises; it may fall if two classes become equal.
+ *   WINDOWS as snesimage_refit_characters: a window builds and scores the candidates of the coming K non-skipped calls against
+ *     the maps as they stand — each touched member scores its share in its own tile workspace — and one commit walks the calls
+ *     in order up to the first that accepts; the calls behind it are scored again by the next window.  One synchronisation per
+ *     window.  window: 0 = chosen by the library, 1 = call by call, K = at most K calls per launch set (bounded by the launch
+ *     group of the tile moves and by 64, a member's share of a set's launch set).  For every window the records, maps,
+ *     incumbents and epochs afterwards are the same, bit for bit.
+ *   STATE AFTERWARDS: if a call was accepted, that of snesimage_shared_reduce_characters: every member touched by an accepted
+ *     call holds a stored map with its error known and its epoch advanced, the set records the new epochs and stays intact,
+ *     snesimage_shared_error returns the last accepted E bit for bit, and the set remembers that it holds merged maps: every set
+ *     call that optimizes re-runs optimize() first.  A REFIT IS THE LAST STAGE OF A RUN.  A sweep that accepts nothing — no
+ *     eligible class, only skipped calls, or every scored call rejected — leaves the set and every member untouched bit for
+ *     bit.  Between enqueuing a window's commit and reading its records every member touched by a call of that window is flagged
+ *     "a stored map of unknown error"; the members that no accepted call touched get their flags and epoch back, as in the set's
+ *     merge step.  If a window fails (SNES_ERR_HIP) the calls accepted before it stand and are reported.
+ * Refusals mirror the two blocks this extends: SNES_ERR_ARG for null pointers, a rep beyond G, a rep that does not represent an
+ * eligible class; SNES_ERR_UNSUPPORTED for G > 8,192, before anything is touched; SNES_ERR_STATE as every set call;
+ * SNES_ERR_HIP after a failed workspace allocation, set and members usable and unchanged. */
+typedef struct { double error; uint64_t gain; uint16_t rep, members, touched; uint8_t changed, scored; } snesimage_shared_refit_result; /* 24 bytes; error = E after the call; rep global; members = the class's tiles; touched = its members */
+/* The eligible classes of the set as it stands, ascending global rep, with their fits: reps, members (tiles in the class), gains
+ * hold up to G entries, fits 64 map values per class in the representative's orientation; *n = classes.  Every array is
+ * optional.  State unchanged. */
+int32_t snesimage_shared_character_fits(snesimage_shared *set, uint16_t *reps /*G, global*/, uint16_t *members /*G*/, uint64_t *gains /*G*/,
+                                        uint8_t *fits /*G*64*/, uint32_t *n);
+/* errors[j] = E' of the refit candidate of class reps[j] (global representatives, each eligible) against the current state,
+ * which is left unchanged.  member_errors (optional, n*F): e_i, or inc_i bit for bit for an untouched member.  maps_out
+ * (optional, n*F*w*h bytes): every member's candidate map, the stored map for an untouched member.  A class whose fit equals its
+ * character returns E bit for bit.  Host pointers; synchronous; n may exceed a launch group. */
+int32_t snesimage_shared_score_refits(snesimage_shared *set, const uint16_t *reps, uint32_t n, double *errors /*E' per class*/,
+                                      double *member_errors /*opt, n*F*/, uint8_t *maps_out /*opt, n*F*w*h*/);
+/* One refit sweep.  log (optional): the first log_cap records in call order (skipped calls included, scored = 0); *calls = the
+ * eligible classes; *accepted = calls taken; *unique = U afterwards; stats (optional) as snesimage_refit_characters. */
+int32_t snesimage_shared_refit_characters(snesimage_shared *set, uint32_t window, snesimage_shared_refit_result *log, uint32_t log_cap,
+                                          uint32_t *calls, uint32_t *accepted, uint32_t *unique, snesimage_run_stats *stats);
+
 /* State access (the reference mutates these fields directly: lib.rs:1015 and the GUI). */
 int32_t snesimage_get_tile_palettes(snesimage_ctx *ctx, uint8_t *out /*1024*/);
 int32_t snesimage_set_tile_palettes(snesimage_ctx *ctx, const uint8_t *in /*1024*/);

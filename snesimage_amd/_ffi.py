@@ -54,6 +54,12 @@ class RefitResult(C.Structure):
                 ("pad", C.c_uint8 * 2)]
 
 
+class SharedRefitResult(C.Structure):
+    """snesimage_shared_refit_result: one call of a set's refit sweep."""
+    _fields_ = [("error", C.c_double), ("gain", C.c_uint64), ("rep", C.c_uint16), ("members", C.c_uint16), ("touched", C.c_uint16), ("changed", C.c_uint8),
+                ("scored", C.c_uint8)]
+
+
 # every symbol include/snesimage_hip.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("snesimage_create", C.c_int32, [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
@@ -84,6 +90,9 @@ SIGNATURES = [
     ("snesimage_shared_score_merges", C.c_int32, [C.c_void_p, _u16p, _u16p, _u16p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
     ("snesimage_shared_reduce_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SharedMergeResult), C.c_uint32, _u32p, _u32p]),
     ("snesimage_shared_as_tilemap_json", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
+    ("snesimage_shared_character_fits", C.c_int32, [C.c_void_p, _u16p, _u16p, _u64p, _u8p, _u32p]),
+    ("snesimage_shared_score_refits", C.c_int32, [C.c_void_p, _u16p, C.c_uint32, _f64p, _f64p, _u8p]),
+    ("snesimage_shared_refit_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(SharedRefitResult), C.c_uint32, _u32p, _u32p, _u32p, C.POINTER(RunStats)]),
     ("snesimage_score_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _f64p]),
     ("snesimage_score_candidates_device", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                                       C.c_void_p, C.c_void_p]),

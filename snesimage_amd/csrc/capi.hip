@@ -1735,4 +1735,5 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "tile_host.inc"
 #include "char_host.inc"
 #include "shared_char_host.inc"
+#include "shared_refit_host.inc"
 #include "ordered_host.inc"

@@ -25,6 +25,8 @@
 // --max-set-tiles N (with --share) is the budget of the whole set: the frames share one VRAM character area, so their characters
 // are counted together and a tile may take its indices from a tile of another frame (snesimage_shared_reduce_characters);
 // --set-tilemap FILE writes the set's characters and one tilemap per frame (snesimage_shared_as_tilemap_json).
+// --refit-set-tiles N (with --share) runs up to N refit sweeps over the whole set behind that (snesimage_shared_refit_characters):
+// every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -103,6 +105,10 @@ void usage() {
             "                           distinct characters together (1..8192; one VRAM character area for all frames): a tile may take\n"
             "                           its indices from a tile of another frame; at most 8192 tiles in all; not with --devices\n"
             "      --set-tilemap <F>    with --share: write the set's distinct characters and one tilemap per frame as JSON\n"
+            "      --refit-set-tiles <N>  with --share: behind --max-set-tiles (or the last optimizer call), up to N sweeps (1..16) that refit\n"
+            "                           every character shared across the frames to all the tiles using it and keep a refit where the\n"
+            "                           set's error falls (one frame's error may rise); stops after a sweep that accepts nothing; not\n"
+            "                           with --devices\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
             "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only\n"
@@ -188,8 +194,8 @@ int main(int argc, char **argv) {
     uint32_t count = 1, size = 7, flags = 0, calls = 0, ncand = 64, reassign_every = 0, tile_every = 0, window = 0; // src/config.rs:13-18 defaults
     uint64_t seed = 1;
     int device = 0;
-    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg, refit_arg, set_tilemap_file, max_set_arg;
-    bool max_tiles_given = false, merge_short_given = false, refit_given = false, max_set_given = false; uint32_t max_tiles = 0, merge_short = 0, refit_sweeps = 0, max_set_tiles = 0;
+    std::string tile_file, preview_file, resume_file, tilemap_file, max_tiles_arg, merge_short_arg, refit_arg, set_tilemap_file, max_set_arg, refit_set_arg;
+    bool max_tiles_given = false, merge_short_given = false, refit_given = false, max_set_given = false, refit_set_given = false; uint32_t max_tiles = 0, merge_short = 0, refit_sweeps = 0, max_set_tiles = 0, refit_set_sweeps = 0;
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
@@ -224,6 +230,7 @@ int main(int argc, char **argv) {
         else if (a == "--tilemap") tilemap_file = need("--tilemap");
         else if (a == "--max-set-tiles") { max_set_given = true; max_set_arg = need("--max-set-tiles"); }
         else if (a == "--set-tilemap") set_tilemap_file = need("--set-tilemap");
+        else if (a == "--refit-set-tiles") { refit_set_given = true; refit_set_arg = need("--refit-set-tiles"); }
         else if (a == "--share") {
             const std::string v = need("--share");
             const size_t eq = v.find('=');
@@ -272,6 +279,14 @@ int main(int argc, char **argv) {
             if (max_set_arg.empty() || *end || n < 1 || n > 8192) { fprintf(stderr, "error: invalid value '%s' for '--max-set-tiles <N>': expected 1..8192\n", max_set_arg.c_str()); return 2; }
             max_set_tiles = (uint32_t)n;
         }
+    }
+    if (refit_set_given) { // the refit of a set: said before any file or device is touched
+        if (shares.empty()) { fprintf(stderr, "error: '--refit-set-tiles <N>' needs '--share <SOURCE=TARGET>': it refits the characters of a set (one image: --refit-tiles)\n"); return 2; }
+        if (!devices.empty()) { fprintf(stderr, "error: the argument '--refit-set-tiles <N>' cannot be used with '--devices'\n"); return 2; }
+        char *end = nullptr;
+        const unsigned long n = strtoul(refit_set_arg.c_str(), &end, 10);
+        if (refit_set_arg.empty() || refit_set_arg[0] == '-' || *end || n < 1 || n > 16) { fprintf(stderr, "error: invalid value '%s' for '--refit-set-tiles <N>': expected 1..16\n", refit_set_arg.c_str()); return 2; }
+        refit_set_sweeps = (uint32_t)n;
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
@@ -533,6 +548,17 @@ int main(int argc, char **argv) {
         log_info("Characters of the set: " + std::to_string(u0) + " -> " + std::to_string(u1) + " in " + std::to_string(merges) + " merges (budget " + std::to_string(max_set_tiles) + ")");
         log_info("Error: " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (u1 > max_set_tiles) log_info("No tile is left that may be merged: the budget is not met");
+    }
+    for (uint32_t sweep = 0; sweep < refit_set_sweeps; sweep++) { // behind the set's merges, in front of everything that is written: a refit is the last stage too
+        uint32_t n_calls = 0, n_acc = 0, u1 = 0;
+        double e0 = 0.0, e1 = 0.0;
+        snesimage_run_stats rs{};
+        if (snesimage_shared_error(set, &e0) != 0 || snesimage_shared_refit_characters(set, 0, nullptr, 0, &n_calls, &n_acc, &u1, &rs) != 0 || snesimage_shared_error(set, &e1) != 0)
+            die(std::string("Unable to refit the characters of the set: ") + snesimage_last_error());
+        const uint32_t skipped = n_calls - (uint32_t)rs.useful;
+        log_info("Refit sweep of the set " + std::to_string(sweep + 1) + ": " + std::to_string(n_calls) + " calls, " + std::to_string(n_acc) + " accepted, " + std::to_string(skipped) +
+                 " skipped; error " + fmt_f64(e0) + " -> " + fmt_f64(e1) + "; " + std::to_string(u1) + " characters");
+        if (n_acc == 0) break;
     }
     log_info("Writing output to " + target); // src/lib.rs:1000-1002
     write_json(ctx, target);

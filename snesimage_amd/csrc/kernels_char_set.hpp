@@ -250,4 +250,160 @@ __global__ __launch_bounds__(64) void ks_merge_commit(const unsigned long long *
     }
 }
 
+// ---- the refit across the members of a set: each shared character fitted to all the tiles of all members that use it ---------
+//
+// The snapshot is the set-wide classes as k_char_classes left them (rep[], flip[] over the G global tiles).  ks_refit_fit fits
+// every eligible class at once; the host, which reads the fits anyway to log the skipped calls, builds the small tables of a
+// window (which call is scored as which candidate of which member) and uploads them; ks_refit_maps writes one member's
+// candidates into that member's tile workspace; ks_refit_commit decides on E = the members' errors summed in member order.
+
+constexpr int kSetRefitMembers = 256; // most members of a set with G <= kSetTiles (an image has at least 32 tiles)
+struct SetRefitFit { unsigned long long gain; uint16_t members, touched; uint8_t eligible, differs; uint16_t pad; }; // per global tile; all zero unless it represents an eligible class
+struct SetRefitLog { double error; unsigned long long gain; uint16_t rep, members, touched; uint8_t changed, scored; }; // = snesimage_shared_refit_result
+struct SetRefitCall { uint16_t rep, first, count, pad; };  // a window's call: class rep, scored as slots[first .. first + count), ascending member
+struct SetRefitSlot { uint16_t member, slot; };              // touched member, and the candidate's number in that member's workspace
+
+// The fit of the class global tile g represents.  grid = global tiles, block 256; thread (q = tid & 63, lane group = tid >> 6)
+// as in k_refit_fit.  A class may hold every tile of the set, so a tile of the class is ONE word of the LDS list (32 KB):
+// tile | member << 10 | mask << 18 | subpalette << 24 (tile < 1024, member < 256, mask < 64).  The sums are 64-bit integers
+// (8,192 keys below 2^29: below 2^42), so the order of the list does not matter.  Static LDS: 38,440 bytes; no scratch.
+__global__ __launch_bounds__(256) void ks_refit_fit(const SetMember *__restrict__ tab, int ntile, int W, const uint8_t *__restrict__ pinned, const uint16_t *__restrict__ rep,
+                                                   const uint8_t *__restrict__ flip, const uint16_t *__restrict__ csize, const uint32_t *__restrict__ pal_rgb8, int S, int ncol, int G, int F,
+                                                   uint8_t *__restrict__ fits, SetRefitFit *__restrict__ fit) {
+    __shared__ uint32_t s_list[kSetTiles];
+    __shared__ const uint8_t *s_orig[kSetRefitMembers];
+    __shared__ uint32_t s_pal[256], s_touch[kSetRefitMembers / 32];
+    __shared__ unsigned long long s_best[4][64], s_cur[64];
+    __shared__ int s_n, s_pin;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    if ((int)rep[g] != g || csize[g] < 2) { // (the same for the whole block)
+        if (tid == 0) { SetRefitFit z{}; fit[g] = z; }
+        if (tid < 64) fits[(size_t)g * 64 + tid] = 0;
+        return;
+    }
+    if (tid == 0) { s_n = 0; s_pin = 0; }
+    if (tid < kSetRefitMembers / 32) s_touch[tid] = 0;
+    for (int e = tid; e < ncol && e < 256; e += 256) s_pal[e] = pal_rgb8[e];
+    for (int m = tid; m < F && m < kSetRefitMembers; m += 256) s_orig[m] = tab[m].orig;
+    __syncthreads();
+    for (int u = tid; u < G; u += 256) {
+        if ((int)rep[u] != g) continue;
+        const int m = u / ntile, t = u - m * ntile;
+        const int i = atomicAdd(&s_n, 1); // (the order of the list does not matter: the sums are integers)
+        if (i < kSetTiles && m < kSetRefitMembers)
+            s_list[i] = (uint32_t)t | ((uint32_t)m << 10) | ((uint32_t)flip_mask(flip[u]) << 18) | ((uint32_t)tab[m].tile_pal[t] << 24);
+        if (m < kSetRefitMembers) atomicOr(&s_touch[m >> 5], 1u << (m & 31));
+        if (pinned[u]) s_pin = 1;
+    }
+    __syncthreads();
+    const int n = s_n < kSetTiles ? s_n : kSetTiles;
+    if (s_pin) { // a pinned tile, in whichever member: the class is never changed
+        if (tid == 0) { SetRefitFit z{}; fit[g] = z; }
+        if (tid < 64) fits[(size_t)g * 64 + tid] = 0;
+        return;
+    }
+    const int q = tid & 63, lg = tid >> 6;
+    const int mg = g / ntile;
+    const int cur = tab[mg].map[tile_px(g - mg * ntile, q, W)];
+    const int cur_v = cur < S ? cur : S - 1; // (a stored map holds values below S)
+    unsigned long long best = kCharNone;
+    for (int v = lg; v < S; v += 4) {
+        unsigned long long cost = 0;
+        for (int i = 0; i < n; i++) {
+            const uint32_t w = s_list[i];
+            const int e = (int)(w >> 24) * S + v;
+            const uint32_t px = reinterpret_cast<const uint32_t *>(s_orig[(w >> 10) & 255u])[tile_px((int)(w & 1023u), q ^ (int)((w >> 18) & 63u), W)] & 0x00ffffffu;
+            cost += red_mean_key(s_pal[e < 256 ? e : 255], px);
+        }
+        const unsigned long long k = (cost << 8) | (unsigned)v;
+        best = k < best ? k : best; // v ascends: the lowest v of equal costs stays
+        if (v == cur_v) s_cur[q] = cost;
+    }
+    s_best[lg][q] = best;
+    __syncthreads();
+    if (tid < 64) { // one wave
+        unsigned long long m = s_best[0][q];
+#pragma unroll
+        for (int i = 1; i < 4; i++) m = s_best[i][q] < m ? s_best[i][q] : m;
+        const int fitted = (int)(m & 0xffu);
+        unsigned long long gn = s_cur[q] - (m >> 8);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) gn += __shfl_xor(gn, o, 64);
+        const unsigned long long diff = __ballot(fitted != cur);
+        fits[(size_t)g * 64 + q] = (uint8_t)fitted;
+        if (q == 0) {
+            int touched = 0;
+#pragma unroll
+            for (int i = 0; i < kSetRefitMembers / 32; i++) touched += __popc(s_touch[i]);
+            SetRefitFit r{}; r.gain = gn; r.members = (uint16_t)n; r.touched = (uint16_t)touched; r.eligible = 1; r.differs = diff != 0ull ? 1 : 0;
+            fit[g] = r;
+        }
+    }
+}
+
+// One member's refit candidates, into that member's tile workspace: the member's stored map with every tile of class
+// reps[cand] THAT LIES IN THIS MEMBER rewritten to fitted[p ^ mask(flip)]; and the pair (tile 0, its own subpalette) for
+// k_tile_full, which so substitutes nothing.  grid = the member's candidates, block 256: a wave per tile, a lane per pixel.
+__global__ __launch_bounds__(256) void ks_refit_maps(const uint16_t *__restrict__ reps, const SetMember *__restrict__ tab, int member, int ntile, int G, int W, int npx,
+                                                    const uint16_t *__restrict__ rep, const uint8_t *__restrict__ flip, const uint8_t *__restrict__ fits, uint8_t *__restrict__ lmaps,
+                                                    uint16_t *__restrict__ tiles, uint8_t *__restrict__ subs) {
+    const int cand = blockIdx.x, tid = threadIdx.x;
+    int r = reps[cand];
+    r = r < G ? r : 0; // (the host hands over representatives of the set only)
+    const uint4 *src = reinterpret_cast<const uint4 *>(tab[member].map);
+    uint4 *dst = reinterpret_cast<uint4 *>(lmaps + (size_t)cand * npx);
+    for (int i = tid; i < npx / 16; i += 256) dst[i] = src[i];
+    __syncthreads(); // the copy is in place before the class's bytes are replaced
+    const int p = tid & 63, g0 = member * ntile;
+    for (int u = tid >> 6; u < ntile; u += 4) {
+        if ((int)rep[g0 + u] != r) continue; // (the same for the whole wave)
+        lmaps[(size_t)cand * npx + tile_px(u, p, W)] = fits[(size_t)r * 64 + (p ^ flip_mask(flip[g0 + u]))];
+    }
+    if (tid == 0) { tiles[cand] = 0; subs[cand] = tab[member].tile_pal[0]; }
+}
+
+// The window's refit calls in order.  E = the members' incumbents, E' = the same with a touched member's incumbent replaced by
+// the error of its candidate, both summed in member order with plain + (as ks_commit and snesimage_shared_error sum); a call
+// is taken iff E' < E, strict (lib.rs:216-219 on the joint error; a NaN never wins).  Every call up to and including the first
+// that accepts is logged; then that one's maps and errors become the touched members'.  One block.
+__global__ __launch_bounds__(1024) void ks_refit_commit(const SetRefitCall *__restrict__ calls, const SetRefitSlot *__restrict__ slots, int ncalls, const SetRefitFit *__restrict__ fit,
+                                                       const SetMember *__restrict__ tab, int F, int npx, SetRefitLog *__restrict__ log, RefitWinRes *__restrict__ res) {
+    __shared__ int s_win;
+    if (threadIdx.x == 0) {
+        double E = 0.0;
+        for (int i = 0; i < F; i++) { const double v = *tab[i].inc_err; E = i == 0 ? v : E + v; }
+        int win = -1, used = ncalls;
+        for (int c = 0; c < ncalls && win < 0; c++) {
+            const SetRefitCall call = calls[c];
+            double E1 = 0.0;
+            int k = 0;
+            for (int i = 0; i < F; i++) {
+                double v;
+                if (k < (int)call.count && (int)slots[call.first + k].member == i) { v = tab[i].errs[slots[call.first + k].slot]; k++; }
+                else v = *tab[i].inc_err;
+                E1 = i == 0 ? v : E1 + v;
+            }
+            const SetRefitFit f = fit[call.rep];
+            const bool take = E1 < E;
+            SetRefitLog r{};
+            r.error = take ? E1 : E; r.gain = f.gain; r.rep = call.rep; r.members = f.members; r.touched = f.touched; r.changed = take ? 1 : 0; r.scored = 1;
+            log[c] = r;
+            if (take) { win = c; used = c + 1; }
+        }
+        res->consumed = used; res->accepted = win;
+        s_win = win;
+    }
+    __syncthreads(); // the records are written before the state changes hands
+    const int win = s_win;
+    if (win < 0) return;
+    const SetRefitCall call = calls[win];
+    for (int k = 0; k < (int)call.count; k++) {
+        const SetRefitSlot sl = slots[call.first + k];
+        const uint4 *src = reinterpret_cast<const uint4 *>(tab[sl.member].lmaps + (size_t)sl.slot * npx); // (outside the class's tiles it is the stored map itself)
+        uint4 *dst = reinterpret_cast<uint4 *>(tab[sl.member].map);
+        for (int i = threadIdx.x; i < npx / 16; i += 1024) dst[i] = src[i];
+        if (threadIdx.x == 0) *tab[sl.member].inc_err = tab[sl.member].errs[sl.slot];
+    }
+}
+
 } // namespace snes

@@ -20,13 +20,23 @@ struct snesimage_sharedchar {
     uint32_t *mcount = nullptr;
     snes::CharInfo *info = nullptr; snes::SetMergeLog *log = nullptr; snes::SetMember *tab = nullptr;
     std::vector<snes::SetMember> h_tab; // (kept here: the copy to the device may still read it when the filling function returns)
+    // the refit across members (shared_refit_host.inc), made on first use: fits[g * 64 + q] and fit[g] of the class global tile g
+    // represents; a window's calls, slots and the members' candidate lists (kCharShort each); its result (RefitWinRes, 16 bytes, then kCharShort records)
+    bool refit_ready = false;
+    uint8_t *rfits = nullptr; snes::SetRefitFit *rfit = nullptr; snes::SetRefitCall *rcalls = nullptr; snes::SetRefitSlot *rslots = nullptr; uint16_t *rmreps = nullptr; unsigned char *rresult = nullptr;
+    WindowPolicy rpolicy; uint32_t radapt = 4;
 };
 
 namespace {
 
 static_assert(sizeof(snes::SetMergeLog) == sizeof(snesimage_shared_merge_result) && sizeof(snes::SetMergeLog) == 40, "the log record is copied out as it is");
 
+void shared_refit_release(snesimage_sharedchar *w) {
+    dfree(w->rfits); dfree(w->rfit); dfree(w->rcalls); dfree(w->rslots); dfree(w->rmreps); dfree(w->rresult);
+    w->refit_ready = false;
+}
 void shared_char_release(snesimage_sharedchar *w) {
+    shared_refit_release(w);
     dfree(w->chars); dfree(w->pinned); dfree(w->flip); dfree(w->spos); dfree(w->rep); dfree(w->csize); dfree(w->part); dfree(w->skeys); dfree(w->mkeys); dfree(w->mcount);
     dfree(w->info); dfree(w->log); dfree(w->tab);
     w->ready = false;

@@ -16,6 +16,9 @@ from .api import METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
 
 SHARED_MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("member_error", np.float64), ("cost", np.uint64), ("member", np.uint16), ("tile", np.uint16),
                                    ("donor_member", np.uint16), ("donor", np.uint16), ("unique", np.uint16), ("flip", np.uint8), ("rank", np.uint8)])
+# one record of a set's refit sweep (snesimage_shared_refit_result)
+SHARED_REFIT_LOG_DTYPE = np.dtype([("error", np.float64), ("gain", np.uint64), ("rep", np.uint16), ("members", np.uint16), ("touched", np.uint16),
+                                   ("changed", np.uint8), ("scored", np.uint8)])
 
 
 class SharedPalette:
@@ -193,6 +196,44 @@ class SharedPalette:
         out = np.array([(r.error, r.member_error, r.cost, r.member, r.tile, r.donor_member, r.donor, r.unique, r.flip, r.rank) for r in log[:merges.value]],
                        dtype=SHARED_MERGE_LOG_DTYPE)
         return out, unique.value
+
+    def character_fits(self):
+        """The eligible classes of the set as it stands (at least two tiles, of whichever members, sharing a character, none
+        pinned), ascending global representative, each with the 64 map values that cost least over all its tiles
+        (include/snesimage_hip.h: FIT).  Returns (reps[n], members[n], gains[n], fits[n, 64]); the state is left unchanged."""
+        G = len(self.images) * self._ntile()
+        reps, members, gains, fits = np.zeros(G, np.uint16), np.zeros(G, np.uint16), np.zeros(G, np.uint64), np.zeros((G, 64), np.uint8)
+        n = C.c_uint32(0)
+        self._chk(self._L.snesimage_shared_character_fits(self._s, _p(reps, _ffi._u16p), _p(members, _ffi._u16p), _p(gains, _ffi._u64p), _p(fits, _ffi._u8p), C.byref(n)))
+        return reps[:n.value].copy(), members[:n.value].copy(), gains[:n.value].copy(), fits[:n.value].copy()
+
+    def score_refits(self, reps, maps=False):
+        """E' of the set with every tile of class reps[j] (a global representative) redrawn from the class's fit, for every j;
+        the state is left unchanged.  Returns (errors[n], member_errors[n, F]) — a member the class does not touch keeps its
+        incumbent — and with maps=True also maps[n, F, h, w]."""
+        reps = np.ascontiguousarray(reps, np.uint16).reshape(-1)
+        F = len(self.images)
+        errs, mem = np.zeros(reps.size, np.float64), np.zeros((reps.size, F), np.float64)
+        out = np.zeros((reps.size, F, self.images[0].h, self.images[0].w), np.uint8) if maps else None
+        self._chk(self._L.snesimage_shared_score_refits(self._s, _p(reps, _ffi._u16p), reps.size, _p(errs, _ffi._f64p), _p(mem, _ffi._f64p), _p(out, _ffi._u8p) if maps else None))
+        return (errs, mem, out) if maps else (errs, mem)
+
+    def refit_characters(self, window=0, log_cap=None):
+        """One refit sweep over the set: every character shared by tiles of whichever members is refitted to all of them, and
+        the refit is kept where E falls (a single member's error may rise).  Bit-identical for every `window` (0 = chosen by the
+        library, 1 = call by call, K = at most K calls per launch set).  The last stage of a run, like `reduce_characters`.
+        Returns (records, accepted, unique, stats): a structured array (SHARED_REFIT_LOG_DTYPE) of the first log_cap records
+        (default: all), one per eligible class, the calls taken, the character count afterwards and the run statistics."""
+        cap = len(self.images) * self._ntile() if log_cap is None else int(log_cap)
+        log = (_ffi.SharedRefitResult * max(1, cap))()
+        calls, accepted, unique = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_shared_refit_characters(self._s, int(window), log, cap, C.byref(calls), C.byref(accepted), C.byref(unique), C.byref(stats)))
+        n = min(calls.value, cap)
+        out = np.zeros(n, SHARED_REFIT_LOG_DTYPE)
+        for j, r in enumerate(log[:n]):
+            out[j] = (r.error, r.gain, r.rep, r.members, r.touched, r.changed, r.scored)
+        return out, accepted.value, unique.value, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
     def as_tilemap_json(self):
         """The tilemap of the set: one list of characters, and per member and tile character, hflip, vflip and palette."""
