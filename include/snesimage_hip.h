@@ -597,6 +597,44 @@ int32_t snesimage_set_ordered_dither(snesimage_ctx *ctx, const int8_t *offsets /
 int32_t snesimage_get_ordered_dither(snesimage_ctx *ctx, int8_t *out /* 256 */, uint32_t *n);
 int32_t snesimage_get_target_rgba(snesimage_ctx *ctx, uint8_t *out /* w*h*4: T */);
 void    snesimage_bayer_offsets(uint32_t n, uint32_t amplitude, int8_t *out /* n*n */);
+/* NOT a reference method: per-tile ordered-dither LEVELS, chosen by the objective (DESIGN 5d').  Gradients want the full
+ * amplitude; flat areas, outlines and text look worse with any.  A BANK is L tables (1 <= L <= 8) of one side n (2, 4, 8 or 16;
+ * int8_t, row-major, any values; an all-zero table means "no dithering"), and every tile t = ty*32 + tx is on one of them:
+ * level[t] in [0, L).  The target image becomes T.c(x, y) = clamp(orig.c + bank[level[tile(x, y)]][y % n][x % n], 0, 255),
+ * T.a = orig.a.  The pattern's phase stays in image coordinates: neighbouring tiles on one level join seamlessly, and a 16 x 16
+ * table spans two tiles.  With L = 1 this is the T of snesimage_set_ordered_dither, and everything said there about who reads T
+ * holds for any L: no existing entry point changes.
+ *   A LEVEL CALL on tile t with cur = level[t]: for l = 0 .. L-1 ascending, l != cur, e_l = error() of the state with
+ * level[t] := l and optimize() run (palette and tile_palettes untouched: the map differs from the current one in the tile's
+ * 64 pixels at most); acceptance as lib.rs:216-219 — best := incumbent, a strict e_l < best is taken.  If one was taken the
+ * state becomes that candidate's (level[t], T on that tile, palette_map, the incumbent error), otherwise it is untouched bit
+ * for bit.  A level whose 64 choices equal the current ones gives e_l == incumbent exactly and is never taken.
+ *   A LEVEL SWEEP is the level calls on first_tile .. first_tile + n_tiles - 1 in order, each seeing the state the one before
+ * left, run in windows exactly as snesimage_tile_sweep runs them (window 0: chosen by the library; 1: call by call; K: at most
+ * K calls per launch set; one synchronisation per window); every window size gives everything observable bit for bit equal to
+ * call by call.  The record's `sub` field carries the tile's level after the call.  After an accepted call the context is as
+ * snesimage_set_tile_levels + snesimage_optimize would leave it, with the incumbent error known.  A window that fails leaves
+ * the accepted calls standing and reported.
+ * snesimage_set_ordered_dither_bank: sets the bank, every tile on start_level.  It invalidates what
+ * snesimage_set_ordered_dither invalidates and has its refusals (SNES_ERR_UNSUPPORTED on a SNES_DITHER context, SNES_ERR_STATE
+ * between the phases of a split-phase step or on a lent context; SNES_ERR_ARG for n outside {0, 2, 4, 8, 16}, L > 8, a null
+ * bank or start_level >= L).  L = 0 or n = 0 switches ordered dithering off.
+ * snesimage_get_ordered_dither_bank: 8 * 256 bytes, table l at 256 * l (zeros behind the n*n offsets), *n and *L (0: none).
+ * snesimage_get_tile_levels / snesimage_set_tile_levels: 1024 bytes as snesimage_get_tile_palettes (0 for the rows of tiles
+ * below the image, whatever is set there); a value >= L on a tile of the image is SNES_ERR_ARG, no bank SNES_ERR_STATE; invalidation and refusals as for the bank setter.
+ * snesimage_score_tile_levels: e_j of explicit (tile, level) pairs, the state left unchanged; a pair naming the tile's current
+ * level returns the incumbent bit for bit; n may exceed the chunk (launch groups as in snesimage_score_tile_moves); maps_out
+ * (optional): n palette_maps of w*h bytes.
+ * On a context with L > 1: snesimage_set_ordered_dither replaces the bank by a bank of one; snesimage_get_ordered_dither
+ * answers SNES_ERR_STATE (use the bank getter); snesimage_batch_create, snesimage_shared_create and snesimage_group_create
+ * refuse the member with SNES_ERR_ARG — sets and groups share launches and one table. */
+int32_t snesimage_set_ordered_dither_bank(snesimage_ctx *ctx, const int8_t *tables /* L*n*n */, uint32_t n, uint32_t L, uint32_t start_level);
+int32_t snesimage_get_ordered_dither_bank(snesimage_ctx *ctx, int8_t *tables /* 8*256 */, uint32_t *n, uint32_t *L);
+int32_t snesimage_get_tile_levels(snesimage_ctx *ctx, uint8_t *out /* 1024 */);
+int32_t snesimage_set_tile_levels(snesimage_ctx *ctx, const uint8_t *in /* 1024 */);
+int32_t snesimage_score_tile_levels(snesimage_ctx *ctx, const uint16_t *tiles, const uint8_t *levels, uint32_t n, double *errors, uint8_t *maps_out /* optional */);
+int32_t snesimage_level_step(snesimage_ctx *ctx, uint32_t tile, snesimage_tile_result *out);
+int32_t snesimage_level_sweep(snesimage_ctx *ctx, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);

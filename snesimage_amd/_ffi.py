@@ -149,6 +149,13 @@ SIGNATURES = [
     ("snesimage_get_ordered_dither", C.c_int32, [C.c_void_p, _i8p, _u32p]),
     ("snesimage_get_target_rgba", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_bayer_offsets", None, [C.c_uint32, C.c_uint32, _i8p]),
+    ("snesimage_set_ordered_dither_bank", C.c_int32, [C.c_void_p, _i8p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("snesimage_get_ordered_dither_bank", C.c_int32, [C.c_void_p, _i8p, _u32p, _u32p]),
+    ("snesimage_get_tile_levels", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_set_tile_levels", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_score_tile_levels", C.c_int32, [C.c_void_p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_level_step", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(TileResult)]),
+    ("snesimage_level_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
     ("snesimage_get_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_as_rgba", C.c_int32, [C.c_void_p, _u8p]),

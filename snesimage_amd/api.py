@@ -431,6 +431,75 @@ class OptimizedImage:
         self._chk(self._L.snesimage_get_ordered_dither(self._c, _p(out, _ffi._i8p), C.byref(n)))
         return out[:n.value * n.value].reshape(n.value, n.value).copy() if n.value else None
 
+    def set_ordered_dither_bank(self, tables, start_level=0):
+        """Per-tile ordered-dither levels (not in the reference): `tables` is (L, n, n) int8, 1 <= L <= 8 tables of one side
+        n = 2, 4, 8 or 16; every tile starts on `start_level`.  None switches ordered dithering off.  Invalidates
+        palette_map as `set_ordered_dither` does."""
+        if tables is None:
+            self._chk(self._L.snesimage_set_ordered_dither_bank(self._c, None, 0, 0, 0))
+            return
+        t = np.asarray(tables)
+        if t.ndim != 3 or t.shape[1] != t.shape[2] or t.shape[1] not in (2, 4, 8, 16):
+            raise ValueError("an ordered-dither bank is (L, n, n) with n = 2, 4, 8 or 16")
+        if t.min() < -128 or t.max() > 127:
+            raise ValueError("ordered-dither offsets are int8")
+        t = np.ascontiguousarray(t, np.int8)
+        self._chk(self._L.snesimage_set_ordered_dither_bank(self._c, _p(t, _ffi._i8p), t.shape[1], t.shape[0], int(start_level)))
+
+    @property
+    def ordered_dither_bank(self):
+        """The bank in force, (L, n, n) int8, or None."""
+        out = np.zeros((8, 256), np.int8)
+        n, L = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.snesimage_get_ordered_dither_bank(self._c, _p(out, _ffi._i8p), C.byref(n), C.byref(L)))
+        if not n.value or not L.value:
+            return None
+        return out[:L.value, :n.value * n.value].reshape(L.value, n.value, n.value).copy()
+
+    @property
+    def tile_levels(self):
+        """The table of the bank every tile is on, 1024 uint8 as `tile_palettes`; setting it invalidates palette_map."""
+        out = np.zeros(1024, np.uint8)
+        self._chk(self._L.snesimage_get_tile_levels(self._c, _p(out, _ffi._u8p)))
+        return out
+
+    @tile_levels.setter
+    def tile_levels(self, v):
+        v = np.ascontiguousarray(v, np.uint8).reshape(1024)
+        self._chk(self._L.snesimage_set_tile_levels(self._c, _p(v, _ffi._u8p)))
+
+    def score_tile_levels(self, tiles, levels, want_maps=False):
+        """error() of the image with tile tiles[j] on level levels[j], for every j; the state is left unchanged.
+        Returns errors (float64), or (errors, maps[n, h, w]) with want_maps."""
+        tiles = np.ascontiguousarray(tiles, np.uint16).reshape(-1)
+        levels = np.ascontiguousarray(levels, np.uint8).reshape(-1)
+        if tiles.size != levels.size:
+            raise ValueError("tiles and levels differ in length")
+        errs = np.zeros(tiles.size, np.float64)
+        maps = np.zeros((tiles.size, self.h, self.w), np.uint8) if want_maps else None
+        self._chk(self._L.snesimage_score_tile_levels(self._c, _p(tiles, _ffi._u16p), _p(levels, _ffi._u8p), tiles.size, _p(errs, _ffi._f64p),
+                                                      _p(maps, _ffi._u8p) if want_maps else None))
+        return (errs, maps) if want_maps else errs
+
+    def level_step(self, tile):
+        """One level call: the tile moves to the level with the strictly lowest error(), if one beats the incumbent.
+        Returns (error, level, changed)."""
+        r = _ffi.TileResult()
+        self._chk(self._L.snesimage_level_step(self._c, int(tile), C.byref(r)))
+        return r.error, r.sub, int(r.changed)
+
+    def level_sweep(self, first_tile=0, n_tiles=None, window=0):
+        """Level calls on first_tile .. first_tile + n_tiles - 1 in order, several per launch set (bit-identical to
+        `level_step` per tile for every `window`, as `tile_sweep`).  Returns (log, stats): log is a structured array
+        (error, sub, changed), `sub` holding the tile's level after the call."""
+        if n_tiles is None:
+            n_tiles = (self.w // 8) * (self.h // 8) - int(first_tile)
+        log = (_ffi.TileResult * max(1, n_tiles))()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_level_sweep(self._c, int(first_tile), int(n_tiles), int(window), log, C.byref(stats)))
+        out = np.array([(r.error, r.sub, r.changed) for r in log[:n_tiles]], dtype=TILE_LOG_DTYPE)
+        return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
     def target_rgba(self):
         """The image the nearest-colour choice is made against: the original plus the table's offsets, clamped; alpha kept."""
         out = np.zeros((self.h, self.w, 4), np.uint8)

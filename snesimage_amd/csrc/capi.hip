@@ -9,6 +9,7 @@
 #include "kernels_batch.hpp"
 #include "kernels_shared.hpp"
 #include "kernels_tile.hpp"
+#include "kernels_level.hpp"
 #include "kernels_char.hpp"
 #include "kernels_char_set.hpp"
 
@@ -146,6 +147,10 @@ struct snesimage_ctx {
     // initialisers, as_rgba and the JSON keep reading d_orig.  The *_own buffers exist only while a table is set.
     uint8_t *d_target = nullptr, *d_target_own = nullptr; float *d_labpx_t = nullptr, *d_labpxT_t = nullptr, *d_labpx_t_own = nullptr, *d_labpxT_t_own = nullptr;
     uint32_t od_n = 0; int8_t od_tab[256] = {}; // the table: od_n * od_n offsets, row-major; od_n == 0: none
+    // Per-tile levels (DESIGN 5d'): a bank of od_L tables of side od_n, table l at od_bank[256 * l], and the table every tile is on.
+    // od_L <= 1: the one table above.  d_level exists once a bank entry point was called; od_level mirrors it.
+    uint32_t od_L = 0; int8_t od_bank[8 * 256] = {}; uint8_t od_level[1024] = {}; uint8_t *d_level = nullptr;
+    struct snesimage_levelwork *lvl = nullptr; // the level calls' own arrays (level_host.inc), created on first use
     // per-chunk workspace
     float *d_work = nullptr, *d_cand_tab = nullptr, *d_cand_lab = nullptr;
     double *d_part = nullptr;
@@ -1012,6 +1017,7 @@ struct SlotScope {
 };
 // the members of a batch, a set or a group are scored by shared launches and summed or compared: one ordered-dither table for all
 bool ordered_tables_equal(const snesimage_ctx *a, const snesimage_ctx *b) { return a->od_n == b->od_n && (a->od_n == 0 || memcmp(a->od_tab, b->od_tab, (size_t)a->od_n * a->od_n) == 0); }
+const char *kLevelsRefused = "the context holds an ordered-dither bank of several tables: batches, groups and shared-palette sets share launches and one table (per-tile levels for them are not built yet)";
 const char *kBackdropRefused = "SNES_BACKDROP contexts are not supported here: the backdrop schedule is not carried through batches, groups, shared-palette sets and split-phase slot windows";
 
 int32_t batch_quiesce(struct snesimage_batch *b);
@@ -1256,12 +1262,13 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
 
 void batch_forget(struct snesimage_batch *b, snesimage_ctx *c);
 void group_forget(struct snesimage_group *g, snesimage_ctx *c);
-namespace { void window_free(struct snesimage_window *w); void tile_free(snesimage_ctx *c); void char_free(snesimage_ctx *c); }
+namespace { void window_free(struct snesimage_window *w); void tile_free(snesimage_ctx *c); void char_free(snesimage_ctx *c); void level_free(snesimage_ctx *c); }
 void snesimage_destroy(snesimage_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->tile) { if (c->stream) (void)hipStreamSynchronize(c->stream); tile_free(c); }
     if (c->chr) { if (c->stream) (void)hipStreamSynchronize(c->stream); char_free(c); }
+    if (c->lvl) { if (c->stream) (void)hipStreamSynchronize(c->stream); level_free(c); }
     if (c->win) { if (c->stream) (void)hipStreamSynchronize(c->stream); window_free(c->win); c->win = nullptr; } // its slot contexts borrow this context's planes
     if (c->owner) batch_forget(c->owner, c); // waits for the batch's stream and retires the batch
     if (c->group) group_forget(c->group, c); // retires the group: its other members are their own again
@@ -1272,7 +1279,7 @@ void snesimage_destroy(snesimage_ctx *c) {
     dfree(c->d_orig); dfree(c->d_tile_pal); dfree(c->d_colors); dfree(c->d_map); dfree(c->d_pack); dfree(c->d_packT); dfree(c->d_eotf); dfree(c->d_lab_eotf);
     dfree(c->d_pal_rgb8); dfree(c->d_pal_lin); dfree(c->d_pal_xyb); dfree(c->d_pal_lab); dfree(c->d_lin0); dfree(c->d_img1); dfree(c->d_img1T); dfree(c->d_mu1); dfree(c->d_sd1);
     dfree(c->d_bestmaps_all); dfree(c->d_bestrecs_all); dfree(c->d_skip); dfree(c->d_rplist); dfree(c->d_rcount); dfree(c->d_rtab); dfree(c->d_rlab); dfree(c->d_tile_cost); dfree(c->d_tile_any); dfree(c->d_tile_moved);
-    dfree(c->d_target_own); dfree(c->d_labpx_t_own); dfree(c->d_labpxT_t_own);
+    dfree(c->d_target_own); dfree(c->d_labpx_t_own); dfree(c->d_labpxT_t_own); dfree(c->d_level);
     dfree(c->d_labpx); dfree(c->d_labpxT); dfree(c->d_work); dfree(c->d_cand_tab); dfree(c->d_cand_lab); dfree(c->d_part); dfree(c->d_maps); dfree(c->d_mapsT);
     dfree(c->d_cand); dfree(c->d_cand_sel); dfree(c->d_errs); dfree(c->d_errs_sel); dfree(c->d_inc_err); dfree(c->d_last); dfree(c->d_scratch_err); dfree(c->d_dummy_cand);
     for (auto &L : c->extra) { if (L.stream) (void)hipStreamSynchronize(L.stream); dfree(L.d_mapsC4); dfree(L.d_mapsR4); dfree(L.d_work); dfree(L.d_cand_tab); dfree(L.d_cand_lab); dfree(L.d_part); dfree(L.d_maps); dfree(L.d_mapsT); if (L.done) (void)hipEventDestroy(L.done); if (L.stream) (void)hipStreamDestroy(L.stream); }
@@ -1737,3 +1744,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "shared_char_host.inc"
 #include "shared_refit_host.inc"
 #include "ordered_host.inc"
+#include "level_host.inc"

@@ -17,6 +17,10 @@
 // --ordered-dither N [--dither-amplitude A] adds the N x N Bayer pattern of amplitude A to the picture before the nearest-colour
 // choice (include/snesimage_hip.h: snesimage_set_ordered_dither): the alternative to -d that keeps animation frames steady.
 // The JSON does not record it: a --resume run names the option again.
+// --tile-dither K [--dither-levels L] lets every tile choose its own strength of that pattern (include/snesimage_hip.h:
+// snesimage_level_sweep): a ladder of L amplitudes from none to A, every tile starting on A; every K sweeps of the palette and
+// once behind the last call each tile is tried on every other level and kept where the error itself falls.
+// --tile-levels-out FILE / --tile-levels-in FILE carry the ladder and the tiles' levels from run to run (for --resume).
 // --max-tiles N merges tiles after the last optimizer call until at most N distinct characters are left (the VRAM budget;
 // include/snesimage_hip.h: snesimage_reduce_characters), --merge-shortlist K sets how many merges each step scores, and
 // --tilemap FILE writes the characters and the tilemap (snesimage_as_tilemap_json), with or without --max-tiles.
@@ -36,6 +40,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -80,6 +85,15 @@ void usage() {
             "                           but -d; the output does not record it: name it again with --resume\n"
             "      --dither-amplitude <A>  peak-to-peak strength of that pattern in 8-bit steps, 1..255 [default: 32, four BGR555 steps:\n"
             "                           a choice, not a measurement]\n"
+            "      --tile-dither <K>    with --ordered-dither: every K sweeps of the palette and once behind the last call, try every tile on\n"
+            "                           every other strength of the pattern (--dither-levels) and keep a change where the error itself\n"
+            "                           falls; behind --tile-moves if both are given; not with -d, --share or --devices\n"
+            "      --dither-levels <L>  strengths a tile chooses from, 2..8: level 0 is no dithering, level j the pattern at amplitude\n"
+            "                           A*j/(L-1); needs A >= L-1; tiles start on the full amplitude [default: 4: a choice, not a\n"
+            "                           measurement]\n"
+            "      --tile-levels-out <F>  write the ladder and every tile's level as JSON ({\"n\", \"amplitudes\", \"levels\"})\n"
+            "      --tile-levels-in <F>   start from the ladder and levels of such a file (with --resume: the main JSON does not record them);\n"
+            "                           the ladder is the file's: a --dither-levels or --dither-amplitude that differs from it is refused\n"
             "      --calls <N>          optimizer calls to run [default: 0]\n      --candidates <N>     random candidates per call [default: 64]\n"
             "      --window <N>         optimizer calls scored per launch set (0 = adaptive, 1 = call by call; same result) [default: 0]\n"
             "      --seed <N>           candidate RNG seed [default: 1]\n      --device <N>         HIP device [default: 0]\n"
@@ -135,6 +149,22 @@ bool json_int_array(const std::string &path, const char *key, std::vector<long> 
         else return false; // nested arrays or anything else: not a flat integer array
     }
     return false;
+}
+// the integer stored under `"key":N`
+bool json_int_scalar(const std::string &path, const char *key, long &out) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    std::string text; char buf[65536]; size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+    fclose(f);
+    const std::string pat = std::string("\"") + key + "\"";
+    size_t at = text.find(pat);
+    if (at == std::string::npos) return false;
+    at = text.find(':', at + pat.size());
+    if (at == std::string::npos) return false;
+    char *end = nullptr;
+    out = strtol(text.c_str() + at + 1, &end, 10);
+    return end != text.c_str() + at + 1;
 }
 
 void synth(uint64_t seed, uint32_t w, uint32_t h, std::vector<uint8_t> &out) {
@@ -201,6 +231,7 @@ int main(int argc, char **argv) {
     bool decode_only = false;
     uint32_t ordered_n = 0, ordered_amp = 32; bool ordered_given = false, amp_given = false; std::string ordered_arg, amp_arg;
     bool backdrop = false, backdrop_fixed = false; uint8_t backdrop_rgb[3] = {0, 0, 0}; std::string backdrop_arg;
+    uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -213,6 +244,10 @@ int main(int argc, char **argv) {
         else if (a == "--backdrop-fixed") { backdrop_fixed = true; backdrop_arg = need("--backdrop-fixed"); }
         else if (a == "--ordered-dither") { ordered_given = true; ordered_arg = need("--ordered-dither"); }
         else if (a == "--dither-amplitude") { amp_given = true; amp_arg = need("--dither-amplitude"); }
+        else if (a == "--tile-dither") { level_given = true; level_arg = need("--tile-dither"); }
+        else if (a == "--dither-levels") { dither_levels_given = true; dither_levels_arg = need("--dither-levels"); }
+        else if (a == "--tile-levels-out") levels_out_file = need("--tile-levels-out");
+        else if (a == "--tile-levels-in") levels_in_file = need("--tile-levels-in");
         else if (a == "--calls") calls = (uint32_t)strtoul(need("--calls"), nullptr, 10);
         else if (a == "--candidates") ncand = (uint32_t)strtoul(need("--candidates"), nullptr, 10);
         else if (a == "--seed") seed = strtoull(need("--seed"), nullptr, 0);
@@ -309,10 +344,49 @@ int main(int argc, char **argv) {
     }
     int8_t ordered_tab[256] = {};
     if (ordered_n) snesimage_bayer_offsets(ordered_n, ordered_amp, ordered_tab);
+    // per-tile levels: the ladder of amplitudes (level 0 = none, level j = A*j/(L-1)) or the one of --tile-levels-in
+    std::vector<long> level_amps, levels_in;
+    if (level_given || dither_levels_given || !levels_out_file.empty() || !levels_in_file.empty()) { // said before any file or device is touched
+        const char *opt = level_given ? "--tile-dither <K>" : dither_levels_given ? "--dither-levels <L>" : !levels_out_file.empty() ? "--tile-levels-out <F>" : "--tile-levels-in <F>";
+        const char *bad = (flags & SNES_DITHER) ? "'--dither'" : !shares.empty() ? "'--share'" : (!devices.empty() ? "'--devices'" : nullptr); // error diffusion has no levels; sets and groups share one table
+        if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
+        if (!ordered_given) { fprintf(stderr, "error: '%s' needs '--ordered-dither <N>'\n", opt); return 2; }
+        char *end = nullptr;
+        if (level_given) {
+            const unsigned long k = strtoul(level_arg.c_str(), &end, 10);
+            if (level_arg.empty() || level_arg[0] == '-' || *end || k < 1 || k > 1000000) { fprintf(stderr, "error: invalid value '%s' for '--tile-dither <K>': expected a number of sweeps, 1 or more\n", level_arg.c_str()); return 2; }
+            level_every = (uint32_t)k;
+        }
+        if (dither_levels_given) {
+            const unsigned long l = strtoul(dither_levels_arg.c_str(), &end, 10);
+            if (dither_levels_arg.empty() || *end || l < 2 || l > 8) { fprintf(stderr, "error: invalid value '%s' for '--dither-levels <L>': expected 2..8\n", dither_levels_arg.c_str()); return 2; }
+            dither_levels = (uint32_t)l;
+        }
+        if (!level_given && levels_in_file.empty()) { fprintf(stderr, "error: '%s' needs '--tile-dither <K>' or '--tile-levels-in <F>'\n", opt); return 2; }
+        if (levels_in_file.empty() && ordered_amp < dither_levels - 1) {
+            fprintf(stderr, "error: '--dither-levels %u' needs '--dither-amplitude' of at least %u: every level is a different amplitude\n", dither_levels, dither_levels - 1); return 2; }
+        if (!levels_in_file.empty()) {
+            long n_in = 0;
+            if (!json_int_scalar(levels_in_file, "n", n_in) || !json_int_array(levels_in_file, "amplitudes", level_amps) || !json_int_array(levels_in_file, "levels", levels_in))
+                die("cannot read n, amplitudes and levels from " + levels_in_file);
+            if (n_in != (long)ordered_n) die(levels_in_file + " was written for --ordered-dither " + std::to_string(n_in));
+            if (level_amps.empty() || level_amps.size() > 8) die(levels_in_file + ": 1 to 8 amplitudes expected");
+            for (long a : level_amps) if (a < 0 || a > 255) die(levels_in_file + ": amplitude out of range");
+            for (long l : levels_in) if (l < 0 || l >= (long)level_amps.size()) die(levels_in_file + ": level out of range");
+            // the ladder is the file's: a --dither-levels or --dither-amplitude that says otherwise is a mistake, not a preference
+            if (dither_levels_given && dither_levels != level_amps.size()) die(levels_in_file + " holds " + std::to_string(level_amps.size()) + " levels, --dither-levels says " + std::to_string(dither_levels));
+            const long top = *std::max_element(level_amps.begin(), level_amps.end());
+            if (amp_given && (long)ordered_amp != top) die(levels_in_file + " was written for --dither-amplitude " + std::to_string(top) + ", the command line says " + std::to_string(ordered_amp));
+            ordered_amp = (uint32_t)top; // (what the log reports)
+        } else for (uint32_t j = 0; j < dither_levels; j++) level_amps.push_back((long)(ordered_amp * j / (dither_levels - 1)));
+    }
+    std::vector<int8_t> level_bank(256 * level_amps.size(), 0); // table j at n*n*j: zeros for amplitude 0
+    for (size_t j = 0; j < level_amps.size(); j++) if (level_amps[j]) snesimage_bayer_offsets(ordered_n, (uint32_t)level_amps[j], &level_bank[(size_t)ordered_n * ordered_n * j]);
     // every context of the run gets the table before anything is computed on it (the initialisers end with optimize(), which sees it)
     auto create = [&](const uint8_t *px, uint32_t cw, uint32_t chh, int dev, snesimage_ctx **out) -> int32_t {
         int32_t rc = snesimage_create(px, cw, chh, count, size, flags, dev, out);
-        if (rc == 0 && ordered_n) rc = snesimage_set_ordered_dither(*out, ordered_tab, ordered_n);
+        if (rc == 0 && !level_amps.empty()) rc = snesimage_set_ordered_dither_bank(*out, level_bank.data(), ordered_n, (uint32_t)level_amps.size(), (uint32_t)level_amps.size() - 1); // (tiles start on the full amplitude)
+        else if (rc == 0 && ordered_n) rc = snesimage_set_ordered_dither(*out, ordered_tab, ordered_n);
         return rc;
     };
     if (backdrop || backdrop_fixed) { // said before any device is touched
@@ -361,6 +435,18 @@ int main(int argc, char **argv) {
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
     if (ordered_n) log_info("Ordered dithering: " + std::to_string(ordered_n) + " x " + std::to_string(ordered_n) + " Bayer pattern, amplitude " + std::to_string(ordered_amp));
+    if (!level_amps.empty()) {
+        std::string m = "Per-tile dither levels: " + std::to_string(level_amps.size()) + " levels, amplitudes";
+        for (size_t j = 0; j < level_amps.size(); j++) m += (j ? ", " : " ") + std::to_string(level_amps[j]);
+        log_info(m);
+        if (!levels_in_file.empty()) {
+            if (levels_in.size() != 32 * (size_t)(h / 8)) die(levels_in_file + " does not match the image: one level per 8 x 8 tile expected (" + std::to_string(32 * (size_t)(h / 8)) + ")");
+            std::vector<uint8_t> lv(1024, 0);
+            for (size_t i = 0; i < levels_in.size(); i++) lv[i] = (uint8_t)levels_in[i];
+            if (snesimage_set_tile_levels(ctx, lv.data()) != 0) die(snesimage_last_error());
+            log_info("Tile levels from " + levels_in_file);
+        }
+    }
     if (backdrop_fixed && snesimage_set_backdrop_rgb5(ctx, backdrop_rgb) != 0) die(snesimage_last_error()); // (the initialisers end with optimize(), which sees it)
     // --share: one context per image, every member's storage sized for one call's candidates (about 4.45 MB each), one set
     std::vector<snesimage_ctx *> frames{ctx};
@@ -448,6 +534,13 @@ int main(int argc, char **argv) {
         }
         if (std::abs(error - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(error)); last_error = error; } // src/lib.rs:912-915
     };
+    auto level_sweep = [&]() { // one level sweep over the whole image, each call decided by error()
+        snesimage_run_stats ts{};
+        double e0 = 0.0, e1 = 0.0;
+        if (snesimage_error(ctx, &e0) != 0 || snesimage_level_sweep(ctx, 0, 32 * (h / 8), 0, nullptr, &ts) != 0 || snesimage_error(ctx, &e1) != 0) die(std::string("Unable to choose dither levels: ") + snesimage_last_error());
+        log_info("Tile dither: " + std::to_string(ts.calls) + " calls, " + std::to_string(ts.accepted) + " accepted in " + std::to_string(ts.windows) + " launch sets; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
+    };
     auto end_of_sweep = [&]() {
         if (reassign_every && step != sweep && step % reassign_every == 0) { // a sweep over every slot has just ended (src/lib.rs:925-931)
             uint32_t moved = 0;
@@ -464,6 +557,7 @@ int main(int argc, char **argv) {
             log_info("Moved " + std::to_string(ts.accepted) + " tiles in " + std::to_string(ts.windows) + " launch sets");
             if (std::abs(e - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e)); last_error = e; }
         }
+        if (level_every && step != sweep && step % level_every == 0) level_sweep(); // behind the tile moves: the levels are chosen for the subpalettes the tiles ended on
         sweep = step;
     };
     if (ncand <= 64 && window != 1) {
@@ -477,7 +571,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every || backdrop_fixed) { // calls left in the current sweep
+            if (reassign_every || tile_every || level_every || backdrop_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;
@@ -519,6 +613,7 @@ int main(int argc, char **argv) {
         report(p, ix, &before[3 * ((size_t)p * size + ix)], best, error);
         end_of_sweep();
     }
+    if (level_every) level_sweep(); // once behind the last call; the character budget and the refit run behind it
     if (max_tiles_given) { // the last stage: anything that re-runs optimize() would replace the merged map
         uint32_t u0 = 0, u1 = 0, merges = 0;
         double e0 = 0.0, e1 = 0.0;
@@ -565,6 +660,20 @@ int main(int argc, char **argv) {
     for (size_t i = 0; i < shares.size(); i++) {
         log_info("Writing output to " + shares[i].second);
         write_json(frames[i + 1], shares[i].second);
+    }
+    if (!levels_out_file.empty()) { // what the main JSON does not record: the ladder and every tile's level
+        std::vector<uint8_t> lv(1024);
+        if (snesimage_get_tile_levels(ctx, lv.data()) != 0) die(snesimage_last_error());
+        std::string js = "{\"n\":" + std::to_string(ordered_n) + ",\"amplitudes\":[";
+        for (size_t j = 0; j < level_amps.size(); j++) js += (j ? "," : "") + std::to_string(level_amps[j]);
+        js += "],\"levels\":[";
+        for (size_t i = 0; i < 32 * (size_t)(h / 8); i++) js += (i ? "," : "") + std::to_string((unsigned)lv[i]);
+        js += "]}";
+        FILE *f = fopen(levels_out_file.c_str(), "wb");
+        if (!f) die("cannot create " + levels_out_file);
+        fwrite(js.data(), 1, js.size(), f);
+        fclose(f);
+        log_info("Wrote tile levels to " + levels_out_file);
     }
     if (!tilemap_file.empty()) {
         const int64_t need = snesimage_as_tilemap_json(ctx, nullptr, 0);

@@ -17,6 +17,20 @@ int32_t ordered_quiesce(snesimage_ctx *c) {
     return SNES_OK;
 }
 
+// what snesimage_set_palette_rgb5 invalidates (the palette's tables stay), and everything built from the target: the pack, the
+// contested list, the tile workspace's planes, what the slot contexts borrowed.  The source pyramid and Lab(orig) stay valid.
+void ordered_invalidate(snesimage_ctx *c) {
+    c->pack_valid = false; c->inc_valid = false; c->map_synced = false; c->epoch++; c->epoch_by_commit = false;
+    c->sp.plist_valid = false; c->sp.counters_cleared = false;
+    if (c->tile) c->tile->planes_ready = false;
+    if (c->win)
+        for (auto &set : c->win->child)
+            for (snesimage_ctx *k : set) {
+                k->d_target = c->d_target; k->d_labpx_t = c->d_labpx_t; k->d_labpxT_t = c->d_labpxT_t; k->od_n = c->od_n; memcpy(k->od_tab, c->od_tab, sizeof k->od_tab);
+                k->pack_valid = false; k->sp.plist_valid = false; k->sp.counters_cleared = false;
+            }
+}
+
 } // namespace
 
 extern "C" {
@@ -68,22 +82,16 @@ int32_t snesimage_set_ordered_dither(snesimage_ctx *c, const int8_t *offsets, ui
         c->d_target = c->d_orig; c->d_labpx_t = c->d_labpx; c->d_labpxT_t = c->d_labpxT;
     }
     c->od_n = n;
-    // what snesimage_set_palette_rgb5 invalidates (the palette's tables stay), and everything built from the target: the pack, the
-    // contested list, the tile workspace's planes, what the slot contexts borrowed.  The source pyramid and Lab(orig) stay valid.
-    c->pack_valid = false; c->inc_valid = false; c->map_synced = false; c->epoch++; c->epoch_by_commit = false;
-    c->sp.plist_valid = false; c->sp.counters_cleared = false;
-    if (c->tile) c->tile->planes_ready = false;
-    if (c->win)
-        for (auto &set : c->win->child)
-            for (snesimage_ctx *k : set) {
-                k->d_target = c->d_target; k->d_labpx_t = c->d_labpx_t; k->d_labpxT_t = c->d_labpxT_t; k->od_n = c->od_n; memcpy(k->od_tab, c->od_tab, sizeof k->od_tab);
-                k->pack_valid = false; k->sp.plist_valid = false; k->sp.counters_cleared = false;
-            }
+    // a plain table is a bank of one with every tile on it (level_host.inc)
+    c->od_L = n ? 1 : 0; memset(c->od_bank, 0, sizeof c->od_bank); memcpy(c->od_bank, c->od_tab, sizeof c->od_tab); memset(c->od_level, 0, sizeof c->od_level);
+    if (c->d_level) HIPCHK(hipMemsetAsync(c->d_level, 0, 1024, c->stream));
+    ordered_invalidate(c);
     return SNES_OK;
 }
 
 int32_t snesimage_get_ordered_dither(snesimage_ctx *c, int8_t *out, uint32_t *n) {
     if (!c || !out || !n) return fail(SNES_ERR_ARG, "null pointer");
+    if (c->od_L > 1) return fail(SNES_ERR_STATE, "the context holds a bank of several tables: read it with snesimage_get_ordered_dither_bank");
     memcpy(out, c->od_tab, 256); // (zeros behind the n * n offsets)
     *n = c->od_n;
     return SNES_OK;

@@ -203,6 +203,7 @@ int32_t snesimage_shared_create(snesimage_ctx **ctxs, uint32_t n, snesimage_shar
         if (!ctxs[i]) return fail(SNES_ERR_ARG, "null context in set");
         if (ctxs[i]->group) return fail(SNES_ERR_STATE, "context belongs to a group");
         if (ctxs[i]->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
+        if (ctxs[i]->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
         for (uint32_t j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(SNES_ERR_ARG, "a context appears twice in the set");
     }
     // the batch checks the rest (device, size, geometry, chunk, flags, the group-sparse path) and readies every member

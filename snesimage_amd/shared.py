@@ -31,7 +31,10 @@ class SharedPalette:
         self._L = _ffi.load()
         if ordered_dither is not None:
             for img in self.images:
-                img.set_ordered_dither(ordered_dither)
+                if np.ndim(ordered_dither) == 3:  # a bank, (L, n, n): with L > 1 the library refuses the member below, with its message
+                    img.set_ordered_dither_bank(ordered_dither)
+                else:
+                    img.set_ordered_dither(ordered_dither)
         arr = (C.c_void_p * len(self.images))(*[img._c for img in self.images])
         h = C.c_void_p()
         self._chk(self._L.snesimage_shared_create(arr if self.images else None, len(self.images), C.byref(h)))

@@ -11,6 +11,8 @@ no collective in this mode.
 import ctypes as C
 import threading
 
+import numpy as np
+
 from . import _ffi, api
 from .synth import synth_image
 
@@ -28,7 +30,9 @@ def shard_images(n_images, rank, world):
 
 class ImageBatch:
     """`images`: iterable of (global_index, rgba) pairs, all optimised with the same palette geometry, flags and
-    ordered-dither table (`ordered_dither`: api.bayer_offsets(n, A) or any (n, n) int8 tile; None = none)."""
+    ordered-dither table (`ordered_dither`: api.bayer_offsets(n, A) or any (n, n) int8 tile; None = none).  A bank of
+    several tables, (L, n, n), is refused with the library's message where a batch forms (`batched=True`: in `initialize`):
+    the members of a batch share launches and one table."""
 
     def __init__(self, images, sub_count, sub_size, device=0, candidates=64, host_threads=8, dither=False,
                  perceptual=False, nes=False, batched=False, groups=4, ordered_dither=None):
@@ -41,7 +45,10 @@ class ImageBatch:
             img = api.OptimizedImage(rgba, sub_count, sub_size, dither=dither, perceptual=perceptual, nes=nes, device=device)
             img.set_chunk(max(self.candidates, 64))  # workspace for one call's candidates, not the library's 1,024-candidate default
             if ordered_dither is not None:  # every image gets the table before the initialisers (their closing optimize() sees it) and before a batch forms
-                img.set_ordered_dither(ordered_dither)
+                if np.ndim(ordered_dither) == 3:  # a bank, (L, n, n): with L > 1 the library refuses the member where a batch forms (initialize)
+                    img.set_ordered_dither_bank(ordered_dither)
+                else:
+                    img.set_ordered_dither(ordered_dither)
             self.images.append(img)
         self.host_threads = max(1, min(int(host_threads), len(self.images)))
         self.calls_done = 0
