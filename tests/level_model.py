@@ -189,9 +189,13 @@ CASES = {
 
 
 def case_setup(O, name):
-    """-> (img, bank, start_level, model at the k-means start, backdrop B or None).  For a backdrop case the model runs at
-    the expanded geometry with column `size` = B (the mean of the opaque pixels)."""
-    h, hole, count, size, flags, backdrop, n, amp, L, seed = CASES[name]
+    return setup(O, CASES[name])
+
+
+def setup(O, spec):
+    """-> (img, bank, start_level, model at the k-means start, backdrop B or None) of a tuple laid out as CASES' values.  For
+    a backdrop case the model runs at the expanded geometry with column `size` = B (the mean of the opaque pixels)."""
+    h, hole, count, size, flags, backdrop, n, amp, L, seed = spec
     img = image(h, seed)
     if hole:
         img = with_hole(img)
