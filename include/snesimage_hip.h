@@ -635,6 +635,48 @@ int32_t snesimage_set_tile_levels(snesimage_ctx *ctx, const uint8_t *in /* 1024 
 int32_t snesimage_score_tile_levels(snesimage_ctx *ctx, const uint16_t *tiles, const uint8_t *levels, uint32_t n, double *errors, uint8_t *maps_out /* optional */);
 int32_t snesimage_level_step(snesimage_ctx *ctx, uint32_t tile, snesimage_tile_result *out);
 int32_t snesimage_level_sweep(snesimage_ctx *ctx, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats);
+/* NOT a reference method: per-tile ordered-dither levels on a SHARED-PALETTE SET, tied or per frame (DESIGN 5d'').  The
+ * refusals above stand — snesimage_shared_create takes no member with L > 1, and a lent member's own setters answer
+ * SNES_ERR_STATE — so a set gets its bank through the set: the SET owns the bank, every member holds it and a level per tile of
+ * its own, and reads its own T.  F = the number of members; E = the members' error() summed in member order, first then plain +,
+ * as snesimage_shared_error sums.  A level chosen frame by frame makes a static tile's pattern switch on and off between
+ * frames, the shimmer ordered dithering is there to remove; hence the TIED level: one level per tile position for all frames.
+ *   A TIED LEVEL CALL on tile position t, every member's level[t] being the common cur: for l = 0 .. L-1 ascending, l != cur,
+ * E_l = the sum in member order of e_{m,l}, e_{m,l} = error() of member m with level_m[t] := l and optimize() run (a member whose
+ * 64 choices do not change gives its incumbent exactly); acceptance as lib.rs:216-219 on E — best := E, a strict E_l < best is
+ * taken.  An accepted call changes level[t], tile t of T (and of Lab(T)), the palette_map and the incumbent error in EVERY member,
+ * members whose map does not change and members whose own error rises included; otherwise every member is untouched bit for bit.
+ *   A TIED LEVEL SWEEP is the tied calls on first_tile .. first_tile + n_tiles - 1 in order, each seeing the state the one
+ * before left, run in windows (window 0: chosen by the library; 1: call by call; K: at most K calls per launch set; one
+ * synchronisation per window; a member's share of a window is at most its launch group, see snesimage_score_tile_moves); every
+ * window size gives everything observable bit for bit equal to call by call.  A window that accepts nothing leaves every member
+ * untouched bit for bit; a window that fails leaves the accepted calls standing and reported.
+ * snesimage_shared_set_ordered_dither_bank: arguments and their validation as snesimage_set_ordered_dither_bank (SNES_ERR_ARG
+ * for a null set, n outside {0, 2, 4, 8, 16}, L > 8, a null bank, start_level >= L); the bank goes to every member with every
+ * tile of every member on start_level; L = 0 or n = 0 switches the tables of all members off.  SNES_ERR_UNSUPPORTED for a set of
+ * SNES_DITHER members, SNES_ERR_STATE while a split-phase step or window of a member is pending.  A failed allocation
+ * (SNES_ERR_HIP) leaves every member as it was: T, bank and levels.  Afterwards the set is settled as after
+ * snesimage_shared_set_palette_rgb5: optimize() has run on every member and the incumbents are known.  After
+ * snesimage_shared_destroy the members keep bank and levels, as lone contexts with a bank do.
+ * snesimage_shared_set_tile_levels: snesimage_set_tile_levels on member `member` (1024 bytes; a value >= L on a tile of the
+ * image or member >= F is SNES_ERR_ARG, no bank SNES_ERR_STATE), the set settled afterwards; snesimage_get_tile_levels on the
+ * member reads the levels back.
+ * snesimage_shared_score_tile_levels: pair j is "every member's tile tiles[j] on levels[j]"; member_errors[j*F + m] (optional)
+ * is member m's error — its incumbent, bit for bit, where its tile is on that level already or its 64 choices do not change —
+ * and errors[j] their sum in member order.  The state is left unchanged; n may exceed the chunk.  SNES_ERR_ARG for a tile beyond
+ * the image or a level beyond the bank; SNES_ERR_STATE without a bank, and on a set whose stored maps are a character
+ * reduction's (no optimize() of the palette: the call does not replace them).
+ * snesimage_shared_level_sweep: tied != 0: the tied level sweep; log holds n_tiles records (error = E after the call, sub = the
+ * common level after it, changed); SNES_ERR_STATE, before any work, when the members differ in level on a tile of the range.
+ * tied == 0: snesimage_level_sweep on every member, member after member, each call decided on the member's own error as
+ * snesimage_shared_tile_sweep decides; log holds F * n_tiles records, member-major.  Both: window and stats as for
+ * snesimage_level_sweep (stats summed over the members; a tied window scores each of its candidates F times); SNES_ERR_ARG for
+ * a tile range beyond the image, SNES_ERR_STATE without a bank; like every set call that optimizes, the sweep first replaces the
+ * merged maps of an earlier character reduction by optimize().  With a bank of one table nothing is scored or accepted. */
+int32_t snesimage_shared_set_ordered_dither_bank(snesimage_shared *set, const int8_t *tables /* L*n*n */, uint32_t n, uint32_t L, uint32_t start_level);
+int32_t snesimage_shared_set_tile_levels(snesimage_shared *set, uint32_t member, const uint8_t *levels /* 1024 */);
+int32_t snesimage_shared_score_tile_levels(snesimage_shared *set, const uint16_t *tiles, const uint8_t *levels, uint32_t n, double *errors, double *member_errors /* n*F, optional */);
+int32_t snesimage_shared_level_sweep(snesimage_shared *set, uint32_t first_tile, uint32_t n_tiles, uint32_t window, uint32_t tied, snesimage_tile_result *log, snesimage_run_stats *stats);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);

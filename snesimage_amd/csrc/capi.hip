@@ -1745,3 +1745,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "shared_refit_host.inc"
 #include "ordered_host.inc"
 #include "level_host.inc"
+#include "shared_level_host.inc"

@@ -21,6 +21,10 @@
 // snesimage_level_sweep): a ladder of L amplitudes from none to A, every tile starting on A; every K sweeps of the palette and
 // once behind the last call each tile is tried on every other level and kept where the error itself falls.
 // --tile-levels-out FILE / --tile-levels-in FILE carry the ladder and the tiles' levels from run to run (for --resume).
+// --set-tile-dither K (with --share and --ordered-dither) does the same for a set (include/snesimage_hip.h:
+// snesimage_shared_level_sweep): --set-levels tied (the default) keeps one level per tile position for all frames, decided on the
+// set's error, so a static tile's pattern does not switch on and off from frame to frame; --set-levels frame lets every frame
+// choose for itself.  --set-tile-levels-out FILE / --set-tile-levels-in FILE carry the ladder and every frame's levels.
 // --max-tiles N merges tiles after the last optimizer call until at most N distinct characters are left (the VRAM budget;
 // include/snesimage_hip.h: snesimage_reduce_characters), --merge-shortlist K sets how many merges each step scores, and
 // --tilemap FILE writes the characters and the tilemap (snesimage_as_tilemap_json), with or without --max-tiles.
@@ -94,6 +98,18 @@ void usage() {
             "      --tile-levels-out <F>  write the ladder and every tile's level as JSON ({\"n\", \"amplitudes\", \"levels\"})\n"
             "      --tile-levels-in <F>   start from the ladder and levels of such a file (with --resume: the main JSON does not record them);\n"
             "                           the ladder is the file's: a --dither-levels or --dither-amplitude that differs from it is refused\n"
+            "      --set-tile-dither <K>  with --share and --ordered-dither: every K sweeps of the palette and once behind the last call, a\n"
+            "                           level sweep of the set over all tiles (--dither-levels, --dither-amplitude: the same ladder; tiles\n"
+            "                           start on the full amplitude); behind --tile-moves if both are given, in front of --max-set-tiles\n"
+            "                           and --refit-set-tiles; not with -d or --devices\n"
+            "      --set-levels <tied|frame>  tied: one level per tile position for all frames, decided on the set's error; frame: every\n"
+            "                           frame chooses for itself [default: tied: a choice, made for steadiness from frame to frame, not a\n"
+            "                           measurement]\n"
+            "      --set-tile-levels-out <F>  write the ladder and every frame's levels as JSON ({\"n\", \"amplitudes\", \"tied\", \"frames\"}),\n"
+            "                           frames in command-line order\n"
+            "      --set-tile-levels-in <F>   start the set from the ladder and levels of such a file; the ladder is the file's: a\n"
+            "                           --dither-levels or --dither-amplitude that differs from it is refused, as is a file with another\n"
+            "                           frame or tile count, or one that says tied while its frames differ\n"
             "      --calls <N>          optimizer calls to run [default: 0]\n      --candidates <N>     random candidates per call [default: 64]\n"
             "      --window <N>         optimizer calls scored per launch set (0 = adaptive, 1 = call by call; same result) [default: 0]\n"
             "      --seed <N>           candidate RNG seed [default: 1]\n      --device <N>         HIP device [default: 0]\n"
@@ -167,6 +183,50 @@ bool json_int_scalar(const std::string &path, const char *key, long &out) {
     return end != text.c_str() + at + 1;
 }
 
+// the arrays of integers stored under `"key":[[...],[...]]`
+bool json_int_arrays(const std::string &path, const char *key, std::vector<std::vector<long>> &out) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    std::string text; char buf[65536]; size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+    fclose(f);
+    const std::string pat = std::string("\"") + key + "\"";
+    size_t at = text.find(pat);
+    if (at == std::string::npos) return false;
+    at = text.find('[', at + pat.size());
+    if (at == std::string::npos) return false;
+    out.clear();
+    bool inner = false;
+    for (size_t i = at + 1; i < text.size(); ) {
+        const char ch = text[i];
+        if (ch == '[' && !inner) { inner = true; out.emplace_back(); i++; }
+        else if (ch == ']' && inner) { inner = false; i++; }
+        else if (ch == ']') return true;
+        else if (inner && (ch == '-' || (ch >= '0' && ch <= '9'))) { char *end = nullptr; out.back().push_back(strtol(text.c_str() + i, &end, 10)); i = (size_t)(end - text.c_str()); }
+        else if (ch == ',' || ch == ' ' || ch == '\n' || ch == '\r' || ch == '\t') i++;
+        else return false;
+    }
+    return false;
+}
+// the boolean stored under `"key":true|false`
+bool json_bool(const std::string &path, const char *key, bool &out) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    std::string text; char buf[65536]; size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, n);
+    fclose(f);
+    const std::string pat = std::string("\"") + key + "\"";
+    size_t at = text.find(pat);
+    if (at == std::string::npos) return false;
+    at = text.find(':', at + pat.size());
+    if (at == std::string::npos) return false;
+    at++;
+    while (at < text.size() && (text[at] == ' ' || text[at] == '\n' || text[at] == '\r' || text[at] == '\t')) at++;
+    if (text.compare(at, 4, "true") == 0) { out = true; return true; }
+    if (text.compare(at, 5, "false") == 0) { out = false; return true; }
+    return false;
+}
+
 void synth(uint64_t seed, uint32_t w, uint32_t h, std::vector<uint8_t> &out) {
     out.resize((size_t)w * h * 4);
     uint64_t s = seed;
@@ -232,6 +292,7 @@ int main(int argc, char **argv) {
     uint32_t ordered_n = 0, ordered_amp = 32; bool ordered_given = false, amp_given = false; std::string ordered_arg, amp_arg;
     bool backdrop = false, backdrop_fixed = false; uint8_t backdrop_rgb[3] = {0, 0, 0}; std::string backdrop_arg;
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
+    uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -248,6 +309,10 @@ int main(int argc, char **argv) {
         else if (a == "--dither-levels") { dither_levels_given = true; dither_levels_arg = need("--dither-levels"); }
         else if (a == "--tile-levels-out") levels_out_file = need("--tile-levels-out");
         else if (a == "--tile-levels-in") levels_in_file = need("--tile-levels-in");
+        else if (a == "--set-tile-dither") { set_level_given = true; set_level_arg = need("--set-tile-dither"); }
+        else if (a == "--set-levels") { set_mode_given = true; set_mode_arg = need("--set-levels"); }
+        else if (a == "--set-tile-levels-out") set_levels_out_file = need("--set-tile-levels-out");
+        else if (a == "--set-tile-levels-in") set_levels_in_file = need("--set-tile-levels-in");
         else if (a == "--calls") calls = (uint32_t)strtoul(need("--calls"), nullptr, 10);
         else if (a == "--candidates") ncand = (uint32_t)strtoul(need("--candidates"), nullptr, 10);
         else if (a == "--seed") seed = strtoull(need("--seed"), nullptr, 0);
@@ -346,7 +411,8 @@ int main(int argc, char **argv) {
     if (ordered_n) snesimage_bayer_offsets(ordered_n, ordered_amp, ordered_tab);
     // per-tile levels: the ladder of amplitudes (level 0 = none, level j = A*j/(L-1)) or the one of --tile-levels-in
     std::vector<long> level_amps, levels_in;
-    if (level_given || dither_levels_given || !levels_out_file.empty() || !levels_in_file.empty()) { // said before any file or device is touched
+    const bool set_level_opts = set_level_given || set_mode_given || !set_levels_out_file.empty() || !set_levels_in_file.empty(); // the levels of a set: their own options
+    if (level_given || (dither_levels_given && !set_level_opts) || !levels_out_file.empty() || !levels_in_file.empty()) { // said before any file or device is touched
         const char *opt = level_given ? "--tile-dither <K>" : dither_levels_given ? "--dither-levels <L>" : !levels_out_file.empty() ? "--tile-levels-out <F>" : "--tile-levels-in <F>";
         const char *bad = (flags & SNES_DITHER) ? "'--dither'" : !shares.empty() ? "'--share'" : (!devices.empty() ? "'--devices'" : nullptr); // error diffusion has no levels; sets and groups share one table
         if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
@@ -380,12 +446,60 @@ int main(int argc, char **argv) {
             ordered_amp = (uint32_t)top; // (what the log reports)
         } else for (uint32_t j = 0; j < dither_levels; j++) level_amps.push_back((long)(ordered_amp * j / (dither_levels - 1)));
     }
+    std::vector<std::vector<long>> set_levels_in; // --set-tile-levels-in: one list of levels per frame
+    if (set_level_opts) { // said before any file or device is touched
+        const char *opt = set_level_given ? "--set-tile-dither <K>" : set_mode_given ? "--set-levels <tied|frame>" : !set_levels_out_file.empty() ? "--set-tile-levels-out <F>" : "--set-tile-levels-in <F>";
+        const char *bad = (flags & SNES_DITHER) ? "'--dither'" : (!devices.empty() ? "'--devices'" : (level_given || !levels_out_file.empty() || !levels_in_file.empty()) ? "the levels of one image ('--tile-dither', '--tile-levels-out', '--tile-levels-in')" : nullptr);
+        if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", opt, bad); return 2; }
+        if (shares.empty()) { fprintf(stderr, "error: '%s' needs '--share <SOURCE=TARGET>': it chooses the dither levels of a set (one image: --tile-dither)\n", opt); return 2; }
+        if (!ordered_given) { fprintf(stderr, "error: '%s' needs '--ordered-dither <N>'\n", opt); return 2; }
+        char *end = nullptr;
+        if (set_level_given) {
+            const unsigned long k = strtoul(set_level_arg.c_str(), &end, 10);
+            if (set_level_arg.empty() || set_level_arg[0] == '-' || *end || k < 1 || k > 1000000) { fprintf(stderr, "error: invalid value '%s' for '--set-tile-dither <K>': expected a number of sweeps, 1 or more\n", set_level_arg.c_str()); return 2; }
+            set_level_every = (uint32_t)k;
+        }
+        if (set_mode_given) {
+            if (set_mode_arg != "tied" && set_mode_arg != "frame") { fprintf(stderr, "error: invalid value '%s' for '--set-levels <tied|frame>': expected tied or frame\n", set_mode_arg.c_str()); return 2; }
+            set_tied = set_mode_arg == "tied";
+        }
+        if (dither_levels_given) {
+            const unsigned long l = strtoul(dither_levels_arg.c_str(), &end, 10);
+            if (dither_levels_arg.empty() || *end || l < 2 || l > 8) { fprintf(stderr, "error: invalid value '%s' for '--dither-levels <L>': expected 2..8\n", dither_levels_arg.c_str()); return 2; }
+            dither_levels = (uint32_t)l;
+        }
+        if (!set_level_given && set_levels_in_file.empty()) { fprintf(stderr, "error: '%s' needs '--set-tile-dither <K>' or '--set-tile-levels-in <F>'\n", opt); return 2; }
+        if (set_levels_in_file.empty() && ordered_amp < dither_levels - 1) {
+            fprintf(stderr, "error: '--dither-levels %u' needs '--dither-amplitude' of at least %u: every level is a different amplitude\n", dither_levels, dither_levels - 1); return 2; }
+        if (!set_levels_in_file.empty()) {
+            const std::string &file = set_levels_in_file;
+            long n_in = 0; bool tied_in = false;
+            if (!json_int_scalar(file, "n", n_in) || !json_int_array(file, "amplitudes", level_amps) || !json_bool(file, "tied", tied_in) || !json_int_arrays(file, "frames", set_levels_in))
+                die("cannot read n, amplitudes, tied and frames from " + file);
+            if (n_in != (long)ordered_n) die(file + " was written for --ordered-dither " + std::to_string(n_in));
+            if (level_amps.empty() || level_amps.size() > 8) die(file + ": 1 to 8 amplitudes expected");
+            for (long a : level_amps) if (a < 0 || a > 255) die(file + ": amplitude out of range");
+            if (set_levels_in.size() != shares.size() + 1) die(file + " holds the levels of " + std::to_string(set_levels_in.size()) + " frames, the set has " + std::to_string(shares.size() + 1));
+            bool differ = false;
+            for (const auto &fr : set_levels_in) {
+                for (long l : fr) if (l < 0 || l >= (long)level_amps.size()) die(file + ": level out of range");
+                differ = differ || fr != set_levels_in[0];
+            }
+            if (tied_in && differ) die(file + " says tied, but its frames differ in level");
+            if (set_tied && differ) die(file + ": the frames differ in level, which --set-levels tied does not take (name --set-levels frame)");
+            // the ladder is the file's: a --dither-levels or --dither-amplitude that says otherwise is a mistake, not a preference
+            if (dither_levels_given && dither_levels != level_amps.size()) die(file + " holds " + std::to_string(level_amps.size()) + " levels, --dither-levels says " + std::to_string(dither_levels));
+            const long top = *std::max_element(level_amps.begin(), level_amps.end());
+            if (amp_given && (long)ordered_amp != top) die(file + " was written for --dither-amplitude " + std::to_string(top) + ", the command line says " + std::to_string(ordered_amp));
+            ordered_amp = (uint32_t)top; // (what the log reports)
+        } else for (uint32_t j = 0; j < dither_levels; j++) level_amps.push_back((long)(ordered_amp * j / (dither_levels - 1)));
+    }
     std::vector<int8_t> level_bank(256 * level_amps.size(), 0); // table j at n*n*j: zeros for amplitude 0
     for (size_t j = 0; j < level_amps.size(); j++) if (level_amps[j]) snesimage_bayer_offsets(ordered_n, (uint32_t)level_amps[j], &level_bank[(size_t)ordered_n * ordered_n * j]);
     // every context of the run gets the table before anything is computed on it (the initialisers end with optimize(), which sees it)
     auto create = [&](const uint8_t *px, uint32_t cw, uint32_t chh, int dev, snesimage_ctx **out) -> int32_t {
         int32_t rc = snesimage_create(px, cw, chh, count, size, flags, dev, out);
-        if (rc == 0 && !level_amps.empty()) rc = snesimage_set_ordered_dither_bank(*out, level_bank.data(), ordered_n, (uint32_t)level_amps.size(), (uint32_t)level_amps.size() - 1); // (tiles start on the full amplitude)
+        if (rc == 0 && !level_amps.empty() && !set_level_opts) rc = snesimage_set_ordered_dither_bank(*out, level_bank.data(), ordered_n, (uint32_t)level_amps.size(), (uint32_t)level_amps.size() - 1); // (tiles start on the full amplitude)
         else if (rc == 0 && ordered_n) rc = snesimage_set_ordered_dither(*out, ordered_tab, ordered_n);
         return rc;
     };
@@ -435,7 +549,7 @@ int main(int argc, char **argv) {
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
     if (ordered_n) log_info("Ordered dithering: " + std::to_string(ordered_n) + " x " + std::to_string(ordered_n) + " Bayer pattern, amplitude " + std::to_string(ordered_amp));
-    if (!level_amps.empty()) {
+    if (!level_amps.empty() && !set_level_opts) {
         std::string m = "Per-tile dither levels: " + std::to_string(level_amps.size()) + " levels, amplitudes";
         for (size_t j = 0; j < level_amps.size(); j++) m += (j ? ", " : " ") + std::to_string(level_amps[j]);
         log_info(m);
@@ -462,6 +576,22 @@ int main(int argc, char **argv) {
         for (snesimage_ctx *m : frames) if (snesimage_set_chunk(m, chunk) != 0) die(snesimage_last_error());
         if (snesimage_shared_create(frames.data(), (uint32_t)frames.size(), &set) != 0) die(snesimage_last_error());
         log_info("Sharing one palette between " + std::to_string(frames.size()) + " images");
+        if (set_level_opts) { // the set owns the bank; every tile of every frame starts on the full amplitude, the table the frames were created with
+            const uint32_t L = (uint32_t)level_amps.size();
+            if (snesimage_shared_set_ordered_dither_bank(set, level_bank.data(), ordered_n, L, L - 1) != 0) die(snesimage_last_error());
+            std::string m = std::string("Per-tile dither levels of the set (") + (set_tied ? "tied" : "per frame") + "): " + std::to_string(L) + " levels, amplitudes";
+            for (size_t j = 0; j < level_amps.size(); j++) m += (j ? ", " : " ") + std::to_string(level_amps[j]);
+            log_info(m);
+            if (!set_levels_in_file.empty()) {
+                for (size_t i = 0; i < frames.size(); i++) {
+                    if (set_levels_in[i].size() != 32 * (size_t)(h / 8)) die(set_levels_in_file + " does not match the images: one level per 8 x 8 tile expected (" + std::to_string(32 * (size_t)(h / 8)) + ")");
+                    std::vector<uint8_t> lv(1024, 0);
+                    for (size_t t = 0; t < set_levels_in[i].size(); t++) lv[t] = (uint8_t)set_levels_in[i][t];
+                    if (snesimage_shared_set_tile_levels(set, (uint32_t)i, lv.data()) != 0) die(snesimage_last_error());
+                }
+                log_info("Tile levels of the set from " + set_levels_in_file);
+            }
+        }
     }
     if (!resume_file.empty()) { // palette + tile_palettes of an earlier output (src/lib.rs:579-625); the tiles follow from optimize()
         std::vector<long> pal, tp;
@@ -541,6 +671,15 @@ int main(int argc, char **argv) {
         log_info("Tile dither: " + std::to_string(ts.calls) + " calls, " + std::to_string(ts.accepted) + " accepted in " + std::to_string(ts.windows) + " launch sets; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
     };
+    auto set_level_sweep = [&]() { // one level sweep of the set over all tiles: tied calls decided by E, or every frame's own calls
+        snesimage_run_stats ts{};
+        double e0 = 0.0, e1 = 0.0;
+        if (snesimage_shared_error(set, &e0) != 0 || snesimage_shared_level_sweep(set, 0, 32 * (h / 8), 0, set_tied ? 1 : 0, nullptr, &ts) != 0 || snesimage_shared_error(set, &e1) != 0)
+            die(std::string("Unable to choose the dither levels of the set: ") + snesimage_last_error());
+        log_info(std::string("Set tile dither (") + (set_tied ? "tied" : "per frame") + "): " + std::to_string(ts.calls) + " calls, " + std::to_string(ts.accepted) + " accepted in " + std::to_string(ts.windows) +
+                 " launch sets; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
+    };
     auto end_of_sweep = [&]() {
         if (reassign_every && step != sweep && step % reassign_every == 0) { // a sweep over every slot has just ended (src/lib.rs:925-931)
             uint32_t moved = 0;
@@ -558,6 +697,7 @@ int main(int argc, char **argv) {
             if (std::abs(e - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e)); last_error = e; }
         }
         if (level_every && step != sweep && step % level_every == 0) level_sweep(); // behind the tile moves: the levels are chosen for the subpalettes the tiles ended on
+        if (set_level_every && step != sweep && step % set_level_every == 0) set_level_sweep();
         sweep = step;
     };
     if (ncand <= 64 && window != 1) {
@@ -571,7 +711,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every || level_every || backdrop_fixed) { // calls left in the current sweep
+            if (reassign_every || tile_every || level_every || set_level_every || backdrop_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;
@@ -614,6 +754,7 @@ int main(int argc, char **argv) {
         end_of_sweep();
     }
     if (level_every) level_sweep(); // once behind the last call; the character budget and the refit run behind it
+    if (set_level_every) set_level_sweep(); // in front of --max-set-tiles and --refit-set-tiles
     if (max_tiles_given) { // the last stage: anything that re-runs optimize() would replace the merged map
         uint32_t u0 = 0, u1 = 0, merges = 0;
         double e0 = 0.0, e1 = 0.0;
@@ -674,6 +815,24 @@ int main(int argc, char **argv) {
         fwrite(js.data(), 1, js.size(), f);
         fclose(f);
         log_info("Wrote tile levels to " + levels_out_file);
+    }
+    if (!set_levels_out_file.empty()) { // the ladder and every frame's levels, frames in command-line order
+        std::string js = "{\"n\":" + std::to_string(ordered_n) + ",\"amplitudes\":[";
+        for (size_t j = 0; j < level_amps.size(); j++) js += (j ? "," : "") + std::to_string(level_amps[j]);
+        js += std::string("],\"tied\":") + (set_tied ? "true" : "false") + ",\"frames\":[";
+        for (size_t m = 0; m < frames.size(); m++) {
+            std::vector<uint8_t> lv(1024);
+            if (snesimage_get_tile_levels(frames[m], lv.data()) != 0) die(snesimage_last_error());
+            js += m ? ",[" : "[";
+            for (size_t i = 0; i < 32 * (size_t)(h / 8); i++) js += (i ? "," : "") + std::to_string((unsigned)lv[i]);
+            js += "]";
+        }
+        js += "]}";
+        FILE *f = fopen(set_levels_out_file.c_str(), "wb");
+        if (!f) die("cannot create " + set_levels_out_file);
+        fwrite(js.data(), 1, js.size(), f);
+        fclose(f);
+        log_info("Wrote the set's tile levels to " + set_levels_out_file);
     }
     if (!tilemap_file.empty()) {
         const int64_t need = snesimage_as_tilemap_json(ctx, nullptr, 0);

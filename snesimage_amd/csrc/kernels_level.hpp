@@ -140,4 +140,69 @@ __global__ __launch_bounds__(1024) void k_level_commit(LevelCommitParams P, Orde
     }
 }
 
+// ---- tied levels of a shared-palette set (shared_level_host.inc; DESIGN 5d'') ----------------------------------------------
+// One candidate list for all members: candidate j is "every member's tile ltiles[j] on level llevels[j]", scored by each member
+// as candidate j of its own tile workspace (k_level_remap as it is).
+constexpr int kSetLevelCands = 512; // most candidates of a window: kTileGroup of tile_host.inc
+struct SetLevelMember {
+    const uint8_t *orig; const float *lab_eotf; const double *errs; const uint8_t *lmaps; // errs, lmaps: the member's tile workspace
+    uint8_t *level, *map, *target; float *labpx, *labpxT; double *inc_err;                // labpx == nullptr: no Lab planes
+};
+struct SetLevelCommitParams {
+    const SetLevelMember *tab; int F; const TileCall *calls; int ncalls, ncand; const uint8_t *llevels; int npx, n, W, H;
+    TileLog *log; TileWinRes *res;
+};
+// The window's tied level calls in order.  E and every candidate's E_l are the members' errors summed in member order — first,
+// then plain + (as ks_commit, ks_refit_commit and snesimage_shared_error sum: no tree, no reordering); per call best := E,
+// ascending level, strict < (lib.rs:216-219 on the joint error; a NaN never wins).  Every call up to and including the first that
+// accepts is logged; that one's maps, level and errors become EVERY member's, and tile t of every member's T (with Lab(T) in
+// both layouts, through the functions k_level_commit uses) is rewritten.  One block.
+__global__ __launch_bounds__(1024) void ks_level_commit(SetLevelCommitParams P, OrderedBank bank) {
+    __shared__ double s_E[kSetLevelCands];
+    __shared__ int s_win, s_call;
+    for (int j = threadIdx.x; j < P.ncand && j < kSetLevelCands; j += 1024) {
+        double e = 0.0;
+        for (int i = 0; i < P.F; i++) { const double v = P.tab[i].errs[j]; e = i == 0 ? v : e + v; }
+        s_E[j] = e;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double inc = 0.0;
+        for (int i = 0; i < P.F; i++) { const double v = *P.tab[i].inc_err; inc = i == 0 ? v : inc + v; }
+        int win = -1, used = P.ncalls, acc = -1;
+        for (int i = 0; i < P.ncalls && win < 0; i++) {
+            const TileCall c = P.calls[i];
+            double best = inc; int bj = -1;
+            for (uint32_t j = c.first; j < c.first + c.count && j < (uint32_t)kSetLevelCands; j++) { const double e = s_E[j]; if (e < best) { best = e; bj = (int)j; } }
+            TileLog r; r.error = best; r.sub = bj >= 0 ? (int32_t)P.llevels[bj] : (int32_t)c.cur; r.changed = bj >= 0 ? 1 : 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+            P.log[i] = r;
+            if (bj >= 0) { win = bj; acc = i; used = i + 1; }
+        }
+        P.res->consumed = used; P.res->accepted = acc;
+        s_win = win; s_call = acc;
+    }
+    __syncthreads(); // the records are written before the state changes hands
+    const int win = s_win;
+    if (win < 0) return;
+    const int ct = (int)P.calls[s_call].tile, lv = P.llevels[win] & 7;
+    for (int m = 0; m < P.F; m++) {
+        const SetLevelMember M = P.tab[m];
+        const uint4 *src = reinterpret_cast<const uint4 *>(M.lmaps + (size_t)win * P.npx);
+        uint4 *dst = reinterpret_cast<uint4 *>(M.map);
+        for (int i = threadIdx.x; i < P.npx / 16; i += 1024) dst[i] = src[i];
+        if (threadIdx.x == 0) { M.level[ct] = (uint8_t)lv; *M.inc_err = M.errs[win]; }
+        if (threadIdx.x < 64) {
+            const int t = threadIdx.x, x = (ct & 31) * 8 + (t & 7), y = (ct >> 5) * 8 + (t >> 3), px = y * P.W + x;
+            const uint32_t o = level_target_px(reinterpret_cast<const uint32_t *>(M.orig)[px], (int)bank.d[256 * lv + (y & (P.n - 1)) * P.n + (x & (P.n - 1))]);
+            reinterpret_cast<uint32_t *>(M.target)[px] = o;
+            if (M.labpx) {
+                Lab l = linear_to_lab(M.lab_eotf[o & 0xff], M.lab_eotf[(o >> 8) & 0xff], M.lab_eotf[(o >> 16) & 0xff]);
+                const size_t pt = (size_t)x * P.H + y;
+                M.labpx[3 * (size_t)px] = l.l; M.labpx[3 * (size_t)px + 1] = l.a; M.labpx[3 * (size_t)px + 2] = l.b;
+                M.labpxT[3 * pt] = l.l; M.labpxT[3 * pt + 1] = l.a; M.labpxT[3 * pt + 2] = l.b;
+            }
+        }
+    }
+}
+
 } // namespace snes

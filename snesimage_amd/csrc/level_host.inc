@@ -75,17 +75,19 @@ int32_t level_setter_check(snesimage_ctx *c) {
     return SNES_OK;
 }
 
-// nc candidates, pairs at lvl->ltiles / lvl->llevels [0, nc): maps into t.lmaps, errors into d_errors[0, nc)
-int32_t level_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors) {
+// nc candidates, pairs at ltiles / llevels [0, nc) in device memory: maps into t.lmaps, errors into d_errors[0, nc)
+int32_t level_score_pairs(snesimage_ctx *c, const uint16_t *ltiles, const uint8_t *llevels, uint32_t nc, const uint8_t *base_map, double *d_errors) {
     snesimage_tilework &t = *c->tile;
     tile_score_head(c, nc);
     snes::LevelRemapParams R{};
     R.orig = c->d_orig; R.base_map = base_map; R.tile_pal = c->d_tile_pal; R.pal_rgb8 = c->d_pal_rgb8; R.pal_lab = c->d_pal_lab; R.lab_eotf = c->d_lab_eotf;
-    R.ltiles = c->lvl->ltiles; R.llevels = c->lvl->llevels; R.tiles = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps;
+    R.ltiles = ltiles; R.llevels = llevels; R.tiles = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps;
     R.W = (int)c->W; R.H = (int)c->H; R.sub_size = (int)c->sub_size; R.perceptual = c->perceptual ? 1 : 0; R.n = (int)c->od_n;
     hipLaunchKernelGGL(k_level_remap, dim3(nc), dim3(256), 0, c->stream, R, level_bank(c));
     return tile_score_tail(c, nc, d_errors);
 }
+// ... the pairs in the context's own arrays
+int32_t level_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors) { return level_score_pairs(c, c->lvl->ltiles, c->lvl->llevels, nc, base_map, d_errors); }
 
 int32_t level_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats &S) {
     const uint32_t ntile = (c->W / 8) * (c->H / 8);

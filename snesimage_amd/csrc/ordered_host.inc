@@ -31,32 +31,8 @@ void ordered_invalidate(snesimage_ctx *c) {
             }
 }
 
-} // namespace
-
-extern "C" {
-
-void snesimage_bayer_offsets(uint32_t n, uint32_t amplitude, int8_t *out) {
-    if (!out || (n != 2 && n != 4 && n != 8 && n != 16) || amplitude < 1 || amplitude > 255) return;
-    const long long den = 2ll * n * n;
-    for (uint32_t y = 0; y < n; y++)
-        for (uint32_t x = 0; x < n; x++) {
-            long long m = 0; // M_2k = [[4M, 4M+2], [4M+3, 4M+1]]: the coarsest quadrant contributes the lowest two bits
-            for (uint32_t half = n / 2, scale = 1; half >= 1; half /= 2, scale *= 4) {
-                const bool right = (x / half) & 1, low = (y / half) & 1;
-                m += (long long)scale * (low ? (right ? 1 : 3) : (right ? 2 : 0));
-            }
-            const long long num = (long long)amplitude * (2 * m + 1 - (long long)n * n), mag = (2 * (num < 0 ? -num : num) + den) / (2 * den);
-            out[y * n + x] = (int8_t)(num < 0 ? -mag : mag);
-        }
-}
-
-int32_t snesimage_set_ordered_dither(snesimage_ctx *c, const int8_t *offsets, uint32_t n) {
-    if (!c) return fail(SNES_ERR_ARG, "null context");
-    if (n != 0 && n != 2 && n != 4 && n != 8 && n != 16) return fail(SNES_ERR_ARG, "an ordered-dither table is 2, 4, 8 or 16 offsets wide (0 switches it off)");
-    if (n && !offsets) return fail(SNES_ERR_ARG, "null table");
-    if (n && c->dither) return fail(SNES_ERR_UNSUPPORTED, "the context was created with SNES_DITHER: error diffusion and ordered dithering are alternatives");
-    if (c->pend || c->win_pend) return fail(SNES_ERR_STATE, "a split-phase step is pending: commit it first (its candidates were scored against the current target image)");
-    if (c->owner || c->group) return fail(SNES_ERR_STATE, "the context is lent to a batch, a set or a group, whose members share one table: destroy that first");
+// the setter behind its refusals (a set switches its members' tables off through this: shared_level_host.inc)
+int32_t ordered_set_body(snesimage_ctx *c, const int8_t *offsets, uint32_t n) {
     CHECK(set_device(c));
     CHECK(ensure_map(c)); // the owed optimize() belongs to the state before this change
     uint8_t *t = nullptr; float *l = nullptr, *lT = nullptr;
@@ -87,6 +63,35 @@ int32_t snesimage_set_ordered_dither(snesimage_ctx *c, const int8_t *offsets, ui
     if (c->d_level) HIPCHK(hipMemsetAsync(c->d_level, 0, 1024, c->stream));
     ordered_invalidate(c);
     return SNES_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void snesimage_bayer_offsets(uint32_t n, uint32_t amplitude, int8_t *out) {
+    if (!out || (n != 2 && n != 4 && n != 8 && n != 16) || amplitude < 1 || amplitude > 255) return;
+    const long long den = 2ll * n * n;
+    for (uint32_t y = 0; y < n; y++)
+        for (uint32_t x = 0; x < n; x++) {
+            long long m = 0; // M_2k = [[4M, 4M+2], [4M+3, 4M+1]]: the coarsest quadrant contributes the lowest two bits
+            for (uint32_t half = n / 2, scale = 1; half >= 1; half /= 2, scale *= 4) {
+                const bool right = (x / half) & 1, low = (y / half) & 1;
+                m += (long long)scale * (low ? (right ? 1 : 3) : (right ? 2 : 0));
+            }
+            const long long num = (long long)amplitude * (2 * m + 1 - (long long)n * n), mag = (2 * (num < 0 ? -num : num) + den) / (2 * den);
+            out[y * n + x] = (int8_t)(num < 0 ? -mag : mag);
+        }
+}
+
+int32_t snesimage_set_ordered_dither(snesimage_ctx *c, const int8_t *offsets, uint32_t n) {
+    if (!c) return fail(SNES_ERR_ARG, "null context");
+    if (n != 0 && n != 2 && n != 4 && n != 8 && n != 16) return fail(SNES_ERR_ARG, "an ordered-dither table is 2, 4, 8 or 16 offsets wide (0 switches it off)");
+    if (n && !offsets) return fail(SNES_ERR_ARG, "null table");
+    if (n && c->dither) return fail(SNES_ERR_UNSUPPORTED, "the context was created with SNES_DITHER: error diffusion and ordered dithering are alternatives");
+    if (c->pend || c->win_pend) return fail(SNES_ERR_STATE, "a split-phase step is pending: commit it first (its candidates were scored against the current target image)");
+    if (c->owner || c->group) return fail(SNES_ERR_STATE, "the context is lent to a batch, a set or a group, whose members share one table: destroy that first");
+    return ordered_set_body(c, offsets, n);
 }
 
 int32_t snesimage_get_ordered_dither(snesimage_ctx *c, int8_t *out, uint32_t *n) {

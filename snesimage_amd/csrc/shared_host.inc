@@ -6,7 +6,8 @@
 
 struct snesimage_shared_window; // slot windows of the set (shared_window_host.inc)
 struct snesimage_sharedchar;    // workspace of the set's character budget (shared_char_host.inc)
-namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); }
+struct snesimage_sharedlevel;   // workspace of the set's per-tile dither levels (shared_level_host.inc)
+namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); void shared_level_free(snesimage_sharedlevel *w); }
 
 struct snesimage_shared {
     snesimage_batch *b = nullptr;
@@ -16,6 +17,7 @@ struct snesimage_shared {
     const double **d_tab = nullptr;           // the members' error vectors, for ks_sum
     std::vector<unsigned long long> epoch;    // each member's palette / tile-map generation when the set last touched it
     snesimage_sharedchar *chr = nullptr;      // the character budget of the set, made on first use
+    snesimage_sharedlevel *lvl = nullptr;     // the tied level calls of the set, made on first use
     bool reduced = false;                     // snesimage_shared_reduce_characters left merged maps: stored maps that are no optimize() of the palette
 };
 
@@ -234,6 +236,7 @@ void snesimage_shared_destroy(snesimage_shared *s) {
     if (s->b->stream) (void)hipStreamSynchronize(s->b->stream);
     if (s->win) { shared_window_free(s->win); s->win = nullptr; } // (its slot contexts borrow the members' planes: before the members go)
     if (s->chr) { shared_char_free(s->chr); s->chr = nullptr; }
+    if (s->lvl) { shared_level_free(s->lvl); s->lvl = nullptr; }
     snesimage_batch_destroy(s->b); // (waits for its stream)
     if (s->d_joint) (void)hipFree(s->d_joint);
     if (s->d_sum) (void)hipFree(s->d_sum);

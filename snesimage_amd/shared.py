@@ -150,6 +150,60 @@ class SharedPalette:
         out = np.array([(r.error, r.sub, r.changed) for r in log[:F * n_tiles]], dtype=TILE_LOG_DTYPE).reshape(F, n_tiles)
         return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
+    # -- per-tile ordered-dither levels of the set, tied or per frame (not in the reference; include/snesimage_hip.h) ----
+    def set_ordered_dither_bank(self, bank, start_level=0):
+        """The set's bank: `bank` is (L, n, n) int8, 1 <= L <= 8 tables of one side n = 2, 4, 8 or 16, given to every member
+        with every tile of every member on `start_level`; None switches the tables of all members off.  The set is settled
+        afterwards (optimize() has run on every member)."""
+        if bank is None:
+            self._chk(self._L.snesimage_shared_set_ordered_dither_bank(self._s, None, 0, 0, 0))
+            return
+        t = np.asarray(bank)
+        if t.ndim != 3 or t.shape[1] != t.shape[2] or t.shape[1] not in (2, 4, 8, 16):
+            raise ValueError("an ordered-dither bank is (L, n, n) with n = 2, 4, 8 or 16")
+        if t.min() < -128 or t.max() > 127:
+            raise ValueError("ordered-dither offsets are int8")
+        t = np.ascontiguousarray(t, np.int8)
+        self._chk(self._L.snesimage_shared_set_ordered_dither_bank(self._s, _p(t, _ffi._i8p), t.shape[1], t.shape[0], int(start_level)))
+
+    def set_tile_levels(self, member, levels):
+        """OptimizedImage.tile_levels = levels on member `member` of the set (1024 uint8); the set is settled afterwards."""
+        v = np.ascontiguousarray(levels, np.uint8).reshape(1024)
+        self._chk(self._L.snesimage_shared_set_tile_levels(self._s, int(member), _p(v, _ffi._u8p)))
+
+    @property
+    def tile_levels(self):
+        """The level every tile of every member is on, (F, 1024) uint8."""
+        return np.stack([img.tile_levels for img in self.images])
+
+    def score_tile_levels(self, tiles, levels):
+        """E of the set with EVERY member's tile tiles[j] on level levels[j], for every j; the state is left unchanged.
+        Returns (errors[n], member_errors[n, F]): a member already on that level keeps its incumbent bit for bit."""
+        tiles = np.ascontiguousarray(tiles, np.uint16).reshape(-1)
+        levels = np.ascontiguousarray(levels, np.uint8).reshape(-1)
+        if tiles.size != levels.size:
+            raise ValueError("tiles and levels differ in length")
+        errs, mem = np.zeros(tiles.size, np.float64), np.zeros((tiles.size, len(self.images)), np.float64)
+        self._chk(self._L.snesimage_shared_score_tile_levels(self._s, _p(tiles, _ffi._u16p), _p(levels, _ffi._u8p), tiles.size, _p(errs, _ffi._f64p), _p(mem, _ffi._f64p)))
+        return errs, mem
+
+    def level_sweep(self, first_tile=0, n_tiles=None, window=0, tied=True):
+        """tied: tied level calls on tile positions first_tile .. first_tile + n_tiles - 1 in order — one level per position for
+        all members, decided on E (a single member's error may rise) — several per launch set, bit-identical for every `window`
+        (0 = chosen by the library, 1 = call by call, K = at most K calls per launch set); log[n_tiles] holds (E, the common
+        level, changed).  Not tied: OptimizedImage.level_sweep on every member, member after member, each call decided on the
+        member's own error; log[F, n_tiles].  Returns (log, stats)."""
+        if n_tiles is None:
+            n_tiles = self._ntile() - int(first_tile)
+        F = 1 if tied else len(self.images)
+        log = (_ffi.TileResult * max(1, F * n_tiles))()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_shared_level_sweep(self._s, int(first_tile), int(n_tiles), int(window), 1 if tied else 0, log, C.byref(stats)))
+        out = np.array([(r.error, r.sub, r.changed) for r in log[:F * n_tiles]], dtype=TILE_LOG_DTYPE)
+        if not tied:
+            out = out.reshape(F, n_tiles)
+        return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
     # -- the character budget of the set (not in the reference; include/snesimage_hip.h) ---------------------------
     def _ntile(self):
         return (self.images[0].w // 8) * (self.images[0].h // 8)
