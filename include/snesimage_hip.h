@@ -55,7 +55,8 @@ enum { SNES_DITHER = 1, SNES_PERCEPTUAL = 2, SNES_NES = 4 };
  *   - snesimage_as_json: slot 0 of every palette row holds B as a BGR555 word; `tiles` holds 0 for a transparent or a backdrop
  *     pixel, else map + 1;
  *   - snesimage_batch_create, snesimage_group_create, snesimage_shared_create, snesimage_slots_begin and _commit refuse a
- *     backdrop context with SNES_ERR_UNSUPPORTED (their hosts do not carry the backdrop schedule). */
+ *     backdrop context with SNES_ERR_UNSUPPORTED (their hosts do not carry the backdrop schedule); a shared-palette set of
+ *     backdrop contexts is made by snesimage_shared_create_backdrop (below). */
 enum { SNES_BACKDROP = 8 };
 /* optimizer methods: lib.rs:191 (random), :286 (channel), :242 (nes) */
 enum { SNES_METHOD_RANDOM = 0, SNES_METHOD_CHANNEL = 1, SNES_METHOD_NES = 2 };
@@ -265,6 +266,34 @@ int32_t snesimage_shared_run_slots(snesimage_shared *set, uint32_t n_calls, uint
 /* Slot contexts for windows of up to n_slots calls (clamped to SNES_WINDOW_MAX / F) now rather than on first use.
  * Allocation is grow-only; a failed allocation returns SNES_ERR_HIP and leaves the set usable. */
 int32_t snesimage_shared_slots_reserve(snesimage_shared *set, uint32_t n_slots);
+
+/* THE BACKDROP COLOUR OF A SET (DESIGN 5c'').  The frames of one background read the same CGRAM word 0, so a set can carry B:
+ * every member is a SNES_BACKDROP context — the expanded context (sub_count, sub_size + 1) with a tied last column — and the set
+ * keeps one B in all of them, as it keeps one palette.  snesimage_shared_create_backdrop takes SNES_BACKDROP members only
+ * (a plain member: SNES_ERR_ARG, the message names snesimage_shared_create, which takes those); their REGULAR entries must agree
+ * (SNES_ERR_STATE), B of every member is then written by the set: backdrop_rgb5 (three 5-bit values; > 31: SNES_ERR_ARG) when
+ * given, else snesimage_create's rule on the member stack — per channel (sum over the opaque pixels of all members + n/2) / n in
+ * integers, n = their count, then >> 3; snapped to the table with SNES_NES; (0,0,0) without an opaque pixel.  Everything else a
+ * set refuses is refused here; snesimage_shared_create, snesimage_batch_create and snesimage_group_create keep refusing backdrop
+ * members.  On such a set:
+ *   - snesimage_shared_step(_async) and snesimage_shared_score_candidates take the backdrop slot (palette == sub_count,
+ *     index == 0): a candidate replaces B in every subpalette of every member, E_k = sum of the members' e_{i,k} in member
+ *     order, the acceptance rule is that of any set call; the winner goes to all tied entries of all members.  A set of one
+ *     steps exactly as snesimage_step on a backdrop context;
+ *   - snesimage_shared_run_slots follows snesimage_schedule_next_backdrop (a window ends in front of a backdrop call, which is
+ *     stepped on its own), bit-identical to call by call for every `window`;
+ *   - the initialisers are the reference's on the member stack at (sub_count, sub_size) and never move B;
+ *   - snesimage_shared_set_palette_rgb5 takes the sub_count*sub_size regular entries and leaves B; B has the pair below (the
+ *     setter behaves as snesimage_shared_set_palette_rgb5: optimize() on every member afterwards);
+ *   - snesimage_shared_error, _reassign_tiles and _tile_sweep work as on the expanded members;
+ *   - the character budget, the refit, the set tilemap and the per-tile dither levels of a set (snesimage_shared_characters,
+ *     _merge_shortlist, _score_merges, _reduce_characters, _character_fits, _score_refits, _refit_characters, _as_tilemap_json,
+ *     _set_ordered_dither_bank, _set_tile_levels, _score_tile_levels, _level_sweep) answer SNES_ERR_UNSUPPORTED and leave the
+ *     set usable. */
+int32_t snesimage_shared_create_backdrop(snesimage_ctx **ctxs, uint32_t n, const uint8_t *backdrop_rgb5 /*3, may be NULL*/,
+                                         snesimage_shared **out);
+int32_t snesimage_shared_get_backdrop_rgb5(snesimage_shared *set, uint8_t *out /*3*/);
+int32_t snesimage_shared_set_backdrop_rgb5(snesimage_shared *set, const uint8_t *in /*3*/);
 
 /* Dynamic tile -> subpalette reassignment — NOT a reference method: /root/reference/TODO.md:36-37 lists it as missing ("no
  * attempt is made to reassign tiles dynamically if it could improve the overall result").  Every tile with an opaque pixel

@@ -138,6 +138,9 @@ SIGNATURES = [
     ("snesimage_shared_run_slots", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, _u32p, _u32p, _u32p, _u32p, C.c_uint32,
                                                C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
     ("snesimage_shared_slots_reserve", C.c_int32, [C.c_void_p, C.c_uint32]),
+    ("snesimage_shared_create_backdrop", C.c_int32, [C.POINTER(C.c_void_p), C.c_uint32, _u8p, C.POINTER(C.c_void_p)]),
+    ("snesimage_shared_get_backdrop_rgb5", C.c_int32, [C.c_void_p, _u8p]),
+    ("snesimage_shared_set_backdrop_rgb5", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_get_tile_palettes", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_tile_palettes", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_get_palette_rgb5", C.c_int32, [C.c_void_p, _u8p]),

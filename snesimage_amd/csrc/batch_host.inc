@@ -194,7 +194,12 @@ void batch_forget(snesimage_batch *b, snesimage_ctx *c) {
     b->dead = true;
 }
 
-int32_t snesimage_batch_create(snesimage_ctx **ctxs, uint32_t n, snesimage_batch **out) {
+} // extern "C"
+
+namespace {
+// snesimage_batch_create; backdrop_ok: the members may be SNES_BACKDROP contexts (a backdrop set, shared_host.inc, whose host
+// carries the backdrop schedule: the batched launches only ever see the regular slots of the expanded contexts)
+int32_t batch_create_members(snesimage_ctx **ctxs, uint32_t n, snesimage_batch **out, bool backdrop_ok) {
     if (!ctxs || !out || n == 0) return fail(SNES_ERR_ARG, "null pointer or empty batch");
     *out = nullptr;
     snesimage_ctx *c0 = ctxs[0];
@@ -202,7 +207,7 @@ int32_t snesimage_batch_create(snesimage_ctx **ctxs, uint32_t n, snesimage_batch
         snesimage_ctx *c = ctxs[i];
         if (!c) return fail(SNES_ERR_ARG, "null context in batch");
         if (c->owner) return fail(SNES_ERR_STATE, "context already belongs to a batch");
-        if (c->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
+        if (c->backdrop && !backdrop_ok) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
         if (c->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
         if (c->device != c0->device || c->W != c0->W || c->H != c0->H || c->sub_count != c0->sub_count || c->sub_size != c0->sub_size || c->chunk != c0->chunk)
             return fail(SNES_ERR_ARG, "contexts of a batch must share device, image size, palette geometry and chunk");
@@ -236,6 +241,11 @@ int32_t snesimage_batch_create(snesimage_ctx **ctxs, uint32_t n, snesimage_batch
     *out = b.release();
     return SNES_OK;
 }
+} // namespace
+
+extern "C" {
+
+int32_t snesimage_batch_create(snesimage_ctx **ctxs, uint32_t n, snesimage_batch **out) { return batch_create_members(ctxs, n, out, false); }
 
 void snesimage_batch_destroy(snesimage_batch *b) {
     if (!b) return;

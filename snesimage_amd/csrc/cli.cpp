@@ -12,6 +12,8 @@
 // src/lib.rs:836, for that format), a raw RGBA8 file of 256*H*4 bytes, or `synth:SEED`.
 // --backdrop gives every tile one more colour, the SNES backdrop colour shared by all tiles (include/snesimage_hip.h:
 // SNES_BACKDROP), optimized like any entry; --backdrop-fixed R,G,B (5-bit) keeps it at the given colour.
+// --set-backdrop / --set-backdrop-fixed R,G,B do the same for a --share set (snesimage_shared_create_backdrop): one backdrop colour
+// for all frames, decided on the set's error; with them --resume restarts every frame from its own earlier JSON.
 // --share SOURCE=TARGET (repeatable) optimizes one palette for the main image and every such image together (a set,
 // include/snesimage_hip.h): the frames of an animation share one CGRAM on the console.
 // --ordered-dither N [--dither-amplitude A] adds the N x N Bayer pattern of amplitude A to the picture before the nearest-colour
@@ -84,6 +86,12 @@ void usage() {
             "                           it is optimized like any entry and written to slot 0 of every palette row (needs -s <= 15,\n"
             "                           c*(s+1) <= 253; not with --share or --devices)\n"
             "      --backdrop-fixed <R,G,B>  the same with the backdrop colour given (5-bit channels) and never changed\n"
+            "      --set-backdrop       with --share: the backdrop colour of the set, one CGRAM word 0 for all frames, optimized on the set's\n"
+            "                           error; it starts as the mean of all frames' opaque pixels and is written to slot 0 of every palette\n"
+            "                           row of every frame's JSON; --resume <F> then restarts the main frame from F and every --share frame\n"
+            "                           from its own TARGET, the backdrop colour from slot 0 of F; not with --devices, --backdrop(-fixed),\n"
+            "                           --max-set-tiles, --refit-set-tiles, --set-tilemap or the --set-tile-dither family\n"
+            "      --set-backdrop-fixed <R,G,B>  the same with the backdrop colour given (5-bit channels) and never changed\n"
             "      --ordered-dither <N> ordered dithering with the N x N Bayer pattern (N = 2, 4, 8 or 16) instead of -d: a fixed pattern,\n"
             "                           so frames of an animation do not shimmer against each other; works with every other option\n"
             "                           but -d; the output does not record it: name it again with --resume\n"
@@ -291,6 +299,7 @@ int main(int argc, char **argv) {
     bool decode_only = false;
     uint32_t ordered_n = 0, ordered_amp = 32; bool ordered_given = false, amp_given = false; std::string ordered_arg, amp_arg;
     bool backdrop = false, backdrop_fixed = false; uint8_t backdrop_rgb[3] = {0, 0, 0}; std::string backdrop_arg;
+    bool set_backdrop = false, set_backdrop_fixed = false; std::string set_backdrop_arg; // the backdrop colour of a --share set
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
     for (int i = 1; i < argc; i++) {
@@ -303,6 +312,8 @@ int main(int argc, char **argv) {
         else if (a == "--nes") flags |= SNES_NES;
         else if (a == "--backdrop") backdrop = true;
         else if (a == "--backdrop-fixed") { backdrop_fixed = true; backdrop_arg = need("--backdrop-fixed"); }
+        else if (a == "--set-backdrop") set_backdrop = true;
+        else if (a == "--set-backdrop-fixed") { set_backdrop_fixed = true; set_backdrop_arg = need("--set-backdrop-fixed"); }
         else if (a == "--ordered-dither") { ordered_given = true; ordered_arg = need("--ordered-dither"); }
         else if (a == "--dither-amplitude") { amp_given = true; amp_arg = need("--dither-amplitude"); }
         else if (a == "--tile-dither") { level_given = true; level_arg = need("--tile-dither"); }
@@ -390,8 +401,26 @@ int main(int argc, char **argv) {
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
-    if (!shares.empty()) { // a set runs on one device, from the k-means initialisers; its windows are sized by the library (--window 0) or off (--window 1)
-        const char *bad = !resume_file.empty() ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
+    const bool set_bd = set_backdrop || set_backdrop_fixed;
+    if (set_bd) { // the backdrop colour of a set: said before any file or device is touched
+        const char *opt = set_backdrop_fixed ? "--set-backdrop-fixed <R,G,B>" : "--set-backdrop";
+        if (shares.empty()) { fprintf(stderr, "error: '%s' needs '--share <SOURCE=TARGET>': it carries the backdrop colour of a set (one image: --backdrop)\n", opt); return 2; }
+        const char *bad = !devices.empty() ? "'--devices'" : backdrop ? "'--backdrop'" : backdrop_fixed ? "'--backdrop-fixed'" : (set_backdrop && set_backdrop_fixed) ? "'--set-backdrop-fixed'"
+                        : max_set_given ? "'--max-set-tiles'" : refit_set_given ? "'--refit-set-tiles'" : !set_tilemap_file.empty() ? "'--set-tilemap'"
+                        : set_level_given ? "'--set-tile-dither'" : set_mode_given ? "'--set-levels'" : !set_levels_out_file.empty() ? "'--set-tile-levels-out'" : !set_levels_in_file.empty() ? "'--set-tile-levels-in'" : nullptr;
+        if (bad) { fprintf(stderr, "error: the argument '%s' cannot be used with %s\n", set_backdrop ? "--set-backdrop" : opt, bad); return 2; }
+        if (set_backdrop_fixed) {
+            unsigned v[3]; char tail = 0;
+            if (sscanf(set_backdrop_arg.c_str(), "%u,%u,%u%c", &v[0], &v[1], &v[2], &tail) != 3 || v[0] > 31 || v[1] > 31 || v[2] > 31) {
+                fprintf(stderr, "error: invalid value '%s' for '--set-backdrop-fixed <R,G,B>': expected three 5-bit values, such as 0,0,31\n", set_backdrop_arg.c_str()); return 2; }
+            for (int k = 0; k < 3; k++) backdrop_rgb[k] = (uint8_t)v[k];
+        }
+        if (size > 15 || (unsigned long long)count * (size + 1) > 253) {
+            fprintf(stderr, "error: '%s' needs --subpalette-size <= 15 and count * (size + 1) <= 253: a row of 16 colours holds the backdrop colour and 15 of its own\n", opt); return 2; }
+        flags |= SNES_BACKDROP;
+    }
+    if (!shares.empty()) { // a set runs on one device, from the k-means initialisers (a backdrop set also from --resume); its windows are sized by the library (--window 0) or off (--window 1)
+        const char *bad = (!resume_file.empty() && !set_bd) ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--share <SOURCE=TARGET>' cannot be used with %s\n", bad); return 2; }
     }
     if (ordered_given || amp_given) { // said before any device is touched
@@ -516,7 +545,8 @@ int main(int argc, char **argv) {
             fprintf(stderr, "error: '%s' needs --subpalette-size <= 15 and count * (size + 1) <= 253: a row of 16 colours holds the backdrop colour and 15 of its own\n", opt); return 1; }
         flags |= SNES_BACKDROP;
     }
-    const bool bd = (flags & SNES_BACKDROP) != 0, bd_sched = bd && !backdrop_fixed; // --backdrop-fixed runs the plain schedule: B is never a call's slot
+    const bool bd_fixed = backdrop_fixed || set_backdrop_fixed;
+    const bool bd = (flags & SNES_BACKDROP) != 0, bd_sched = bd && !bd_fixed; // --backdrop-fixed and --set-backdrop-fixed run the plain schedule: B is never a call's slot
     auto sched_next = [&](uint32_t *p, uint32_t *ix, uint32_t *ch, uint32_t *st, uint32_t *m) {
         if (bd_sched) snesimage_schedule_next_backdrop(count, size, (flags & SNES_NES) ? 1 : 0, p, ix, ch, st, m); else snesimage_schedule_next(count, size, (flags & SNES_NES) ? 1 : 0, p, ix, ch, st, m);
     };
@@ -562,6 +592,27 @@ int main(int argc, char **argv) {
         }
     }
     if (backdrop_fixed && snesimage_set_backdrop_rgb5(ctx, backdrop_rgb) != 0) die(snesimage_last_error()); // (the initialisers end with optimize(), which sees it)
+    // palette + tile_palettes (+ B, from slot 0) of an earlier output (src/lib.rs:579-625); the tiles follow from optimize()
+    auto read_resume = [&](const std::string &file, std::vector<uint8_t> &tp8, std::vector<uint8_t> &rgb5, uint8_t *b) {
+        std::vector<long> pal, tp;
+        if (!json_int_array(file, "palette", pal) || !json_int_array(file, "tile_palettes", tp)) die("cannot read palette and tile_palettes from " + file);
+        // as_json writes one tile palette per tile of the image (src/lib.rs:598-616): 32 per 8 rows, 1,024 at 256 rows, 896 at 224
+        const size_t ntiles = 32 * (size_t)(h / 8);
+        if (pal.size() != 16 * (size_t)count || tp.size() != ntiles)
+            die("resume file does not match the image and --subpalette-count (palette must hold 16 entries per subpalette, tile_palettes one per 8 x 8 tile: " + std::to_string(ntiles) + ")");
+        tp8.assign(1024, 0); rgb5.assign(3 * (size_t)count * size, 0); // (the rows of tiles below the image keep subpalette 0, as after snesimage_create)
+        for (size_t i = 0; i < ntiles; i++) { if (tp[i] < 0 || tp[i] >= (long)count) die("resume file: tile palette out of range"); tp8[i] = (uint8_t)tp[i]; }
+        for (uint32_t p = 0; p < count; p++)
+            for (uint32_t i = 0; i < size; i++) { // slot 0 of every 16 is the transparent colour (src/lib.rs:583-585)
+                const long v = pal[16 * (size_t)p + 1 + i];
+                if (v < 0 || v > 0x7fff) die("resume file: colour out of range");
+                uint8_t *o = &rgb5[3 * ((size_t)p * size + i)];
+                o[0] = (uint8_t)(v & 31); o[1] = (uint8_t)((v >> 5) & 31); o[2] = (uint8_t)((v >> 10) & 31);
+            }
+        const long v = pal[0]; // a backdrop run wrote B into slot 0 of every row (and 0 into `tiles` where a pixel shows it: optimize() finds those again)
+        if (bd && (v < 0 || v > 0x7fff)) die("resume file: colour out of range");
+        b[0] = (uint8_t)(v & 31); b[1] = (uint8_t)((v >> 5) & 31); b[2] = (uint8_t)((v >> 10) & 31);
+    };
     // --share: one context per image, every member's storage sized for one call's candidates (about 4.45 MB each), one set
     std::vector<snesimage_ctx *> frames{ctx};
     snesimage_shared *set = nullptr;
@@ -574,8 +625,28 @@ int main(int argc, char **argv) {
         uint32_t chunk = ncand > 32 ? ncand : 32; // the largest call of the schedule: random (ncand), channel (32) or NES (56)
         if ((flags & SNES_NES) && chunk < 56) chunk = 56;
         for (snesimage_ctx *m : frames) if (snesimage_set_chunk(m, chunk) != 0) die(snesimage_last_error());
-        if (snesimage_shared_create(frames.data(), (uint32_t)frames.size(), &set) != 0) die(snesimage_last_error());
+        const uint8_t *set_b = set_backdrop_fixed ? backdrop_rgb : nullptr; // nullptr: the mean of all frames' opaque pixels
+        uint8_t resumed_b[3] = {0, 0, 0};
+        if (set_bd && !resume_file.empty()) { // every frame from its own earlier output: the main one from --resume, the others from their targets
+            for (size_t i = 0; i < frames.size(); i++) {
+                const std::string &file = i ? shares[i - 1].second : resume_file;
+                std::vector<uint8_t> tp8, rgb5; uint8_t b[3];
+                read_resume(file, tp8, rgb5, b);
+                if (i == 0) memcpy(resumed_b, b, 3);
+                if (snesimage_set_tile_palettes(frames[i], tp8.data()) != 0 || snesimage_set_palette_rgb5(frames[i], rgb5.data()) != 0) die(snesimage_last_error());
+            }
+            if (!set_backdrop_fixed) set_b = resumed_b;
+        }
+        if ((set_bd ? snesimage_shared_create_backdrop(frames.data(), (uint32_t)frames.size(), set_b, &set) : snesimage_shared_create(frames.data(), (uint32_t)frames.size(), &set)) != 0) die(snesimage_last_error());
         log_info("Sharing one palette between " + std::to_string(frames.size()) + " images");
+        if (set_bd) {
+            uint8_t b[3];
+            if (snesimage_shared_get_backdrop_rgb5(set, b) != 0) die(snesimage_last_error());
+            char m[120];
+            snprintf(m, sizeof m, "Backdrop colour of the set%s: (%u, %u, %u)", set_backdrop_fixed ? " (fixed)" : "", b[0], b[1], b[2]);
+            log_info(m);
+            if (!resume_file.empty()) log_info("Resumed the set from " + resume_file + " and the --share targets");
+        }
         if (set_level_opts) { // the set owns the bank; every tile of every frame starts on the full amplitude, the table the frames were created with
             const uint32_t L = (uint32_t)level_amps.size();
             if (snesimage_shared_set_ordered_dither_bank(set, level_bank.data(), ordered_n, L, L - 1) != 0) die(snesimage_last_error());
@@ -593,30 +664,14 @@ int main(int argc, char **argv) {
             }
         }
     }
-    if (!resume_file.empty()) { // palette + tile_palettes of an earlier output (src/lib.rs:579-625); the tiles follow from optimize()
-        std::vector<long> pal, tp;
-        if (!json_int_array(resume_file, "palette", pal) || !json_int_array(resume_file, "tile_palettes", tp)) die("cannot read palette and tile_palettes from " + resume_file);
-        // as_json writes one tile palette per tile of the image (src/lib.rs:598-616): 32 per 8 rows, 1,024 at 256 rows, 896 at 224
-        const size_t ntiles = 32 * (size_t)(h / 8);
-        if (pal.size() != 16 * (size_t)count || tp.size() != ntiles)
-            die("resume file does not match the image and --subpalette-count (palette must hold 16 entries per subpalette, tile_palettes one per 8 x 8 tile: " + std::to_string(ntiles) + ")");
-        std::vector<uint8_t> tp8(1024, 0), rgb5(3 * (size_t)count * size); // (the rows of tiles below the image keep subpalette 0, as after snesimage_create)
-        for (size_t i = 0; i < ntiles; i++) { if (tp[i] < 0 || tp[i] >= (long)count) die("resume file: tile palette out of range"); tp8[i] = (uint8_t)tp[i]; }
-        for (uint32_t p = 0; p < count; p++)
-            for (uint32_t i = 0; i < size; i++) { // slot 0 of every 16 is the transparent colour (src/lib.rs:583-585)
-                const long v = pal[16 * (size_t)p + 1 + i];
-                if (v < 0 || v > 0x7fff) die("resume file: colour out of range");
-                uint8_t *o = &rgb5[3 * ((size_t)p * size + i)];
-                o[0] = (uint8_t)(v & 31); o[1] = (uint8_t)((v >> 5) & 31); o[2] = (uint8_t)((v >> 10) & 31);
-            }
-        if (bd && !backdrop_fixed) { // a backdrop run wrote B into slot 0 of every row (and 0 into `tiles` where a pixel shows it: optimize() below finds those again)
-            const long v = pal[0];
-            if (v < 0 || v > 0x7fff) die("resume file: colour out of range");
-            const uint8_t b[3] = {(uint8_t)(v & 31), (uint8_t)((v >> 5) & 31), (uint8_t)((v >> 10) & 31)};
-            if (snesimage_set_backdrop_rgb5(ctx, b) != 0) die(snesimage_last_error());
+    if (!resume_file.empty()) {
+        if (!set) { // (a backdrop set was resumed above, before it was formed)
+            std::vector<uint8_t> tp8, rgb5; uint8_t b[3];
+            read_resume(resume_file, tp8, rgb5, b);
+            if (bd && !backdrop_fixed && snesimage_set_backdrop_rgb5(ctx, b) != 0) die(snesimage_last_error());
+            if (snesimage_set_tile_palettes(ctx, tp8.data()) != 0 || snesimage_set_palette_rgb5(ctx, rgb5.data()) != 0 || snesimage_optimize(ctx) != 0) die(snesimage_last_error());
+            log_info("Resumed from " + resume_file);
         }
-        if (snesimage_set_tile_palettes(ctx, tp8.data()) != 0 || snesimage_set_palette_rgb5(ctx, rgb5.data()) != 0 || snesimage_optimize(ctx) != 0) die(snesimage_last_error());
-        log_info("Resumed from " + resume_file);
     } else if (set) { // the reference's initialisers on the images stacked top to bottom
         if (snesimage_shared_initialize_tiles(set) != 0) die(std::string("Unable to initialize tiles: ") + snesimage_last_error());
         log_info("Finished assigning initial tiles");
@@ -711,7 +766,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every || level_every || set_level_every || backdrop_fixed) { // calls left in the current sweep
+            if (reassign_every || tile_every || level_every || set_level_every || bd_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;
@@ -723,7 +778,7 @@ int main(int argc, char **argv) {
                  : group ? snesimage_group_run_slots(group, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)
                          : snesimage_run_slots(ctx, n, seed, call, &palette, &index, &channel, &step, ncand, window, log.data(), &rs)) != 0) die(std::string("Unable to optimize palette: ") + snesimage_last_error());
             total.calls += rs.calls; total.accepted += rs.accepted; total.windows += rs.windows; total.scored += rs.scored; total.useful += rs.useful;
-            if (backdrop_fixed && palette == count) { palette = 0; index = 0; channel = 0; step += 1; } // the library's schedule has arrived at the backdrop slot: this run passes it by
+            if (bd_fixed && palette == count) { palette = 0; index = 0; channel = 0; step += 1; } // the library's schedule has arrived at the backdrop slot: this run passes it by
             for (uint32_t j = 0; j < n; j++) {
                 const uint32_t cp = p, ci = ix;
                 sched_next(&p, &ix, &ch, &st, &method);

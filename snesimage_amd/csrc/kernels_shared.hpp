@@ -158,6 +158,52 @@ __global__ __launch_bounds__(1024) void ksw_take_map(const BatchArgs *__restrict
     for (int i = threadIdx.x; i < npx / 16; i += 1024) dst[i] = src[i];
 }
 
+// ---- the backdrop colour of a set (snesimage_shared_create_backdrop, shared_host.inc; DESIGN §5c'') -------------------
+// A call on the backdrop slot of a set: every member scored the one candidate list on its own stream through its dense tied
+// path (pack mode 3) into its own error vector; this is the one commit behind them.  The joint (E, k) minimum and the decision
+// are ks_commit's, word for word; every member then takes the decision as k_commit leaves a tied call of a single context:
+// commit_apply on the first tied entry `slot` with the member's own e_{i,k*} as its incumbent, then tied_spread over the
+// member's tied_count tied entries, tied_stride apart (the colour and its rows of pal_rgb8 / pal_lin / pal_xyb / pal_lab).
+struct TiedMember { const double *errors; const uint8_t *cand; uint8_t *colors; double *inc_err; StepResult *last; PaletteTables T; };
+__global__ __launch_bounds__(256) void ks_commit_tied(const TiedMember *__restrict__ A, int K, int n, int nes, int slot, int tied_count, int tied_stride, StepResult *__restrict__ joint) {
+    __shared__ double s_e[256];
+    __shared__ int s_k[256];
+    const int t = threadIdx.x;
+    double be = __longlong_as_double(0x7ff0000000000000ll); int bk = 0x7fffffff;
+    for (int k = t; k < n; k += 256) {
+        double e = A[0].errors[k];
+        for (int i = 1; i < K; i++) e = e + A[i].errors[k];
+        if (e < be) { be = e; bk = k; } // NaN never wins, as in the reference
+    }
+    s_e[t] = be; s_k[t] = bk;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (t < st) {
+            const double e2 = s_e[t + st]; const int k2 = s_k[t + st];
+            if (e2 < s_e[t] || (e2 == s_e[t] && k2 < s_k[t])) { s_e[t] = e2; s_k[t] = k2; }
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    double inc = *A[0].inc_err;
+    for (int i = 1; i < K; i++) inc = inc + *A[i].inc_err;
+    const double start = nes ? 1.7976931348623157e308 : inc;
+    int best_k = -1;
+    if (s_k[0] != 0x7fffffff && s_e[0] < start) best_k = s_k[0];
+    const bool took = best_k >= 0;
+    if (nes && best_k < 0) best_k = 0; // best_index = 0 (lib.rs:249)
+    double E = 0.0;
+    for (int i = 0; i < K; i++) {
+        const TiedMember &a = A[i];
+        commit_apply(took ? a.errors[best_k] : 1.7976931348623157e308, best_k, a.cand, a.colors, slot, a.inc_err, a.last, a.T);
+        if (best_k >= 0 && tied_count > 1) tied_spread(a.colors, slot, tied_count, tied_stride, a.T);
+        E = i == 0 ? a.last->error : E + a.last->error;
+    }
+    StepResult r = *A[0].last;
+    r.error = E;
+    *joint = r;
+}
+
 // Joint sum for explicit candidate lists: out[k] = errs[0][k] + errs[1][k] + ... in member order.
 __global__ __launch_bounds__(256) void ks_sum(const double *const *__restrict__ errs, int K, int n, double *__restrict__ out) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);

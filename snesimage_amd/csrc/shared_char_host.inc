@@ -162,6 +162,7 @@ int32_t sc_score_member(snesimage_shared *s, uint32_t m, uint32_t nc) {
 extern "C" {
 
 int32_t snesimage_shared_characters(snesimage_shared *s, uint32_t *unique, uint16_t *rep, uint8_t *flip, uint8_t *chars) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_characters"));
     CHECK(sc_check(s));
     CHECK(sc_enter(s, false));
     CHECK(sc_alloc(s));
@@ -181,6 +182,7 @@ int32_t snesimage_shared_characters(snesimage_shared *s, uint32_t *unique, uint1
 
 int32_t snesimage_shared_merge_shortlist(snesimage_shared *s, uint32_t k, uint16_t *mem, uint16_t *tiles, uint16_t *donor_members, uint16_t *donors, uint8_t *flips, uint64_t *costs,
                                          uint32_t *n) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_merge_shortlist"));
     if (!s || !n) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(char_shortlist_len(&k));
     CHECK(sc_check(s));
@@ -212,6 +214,7 @@ int32_t snesimage_shared_merge_shortlist(snesimage_shared *s, uint32_t k, uint16
 
 int32_t snesimage_shared_score_merges(snesimage_shared *s, const uint16_t *mem, const uint16_t *tiles, const uint16_t *donor_members, const uint16_t *donors, const uint8_t *flips, uint32_t n,
                                       double *errors, uint8_t *maps_out) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_score_merges"));
     if (!s || !mem || !tiles || !donor_members || !donors || !flips || !errors) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(sc_check(s));
     CHECK(shared_enter(s, true, true)); // (the set intact before a member is asked which of its tiles are pinned)
@@ -260,6 +263,7 @@ int32_t snesimage_shared_score_merges(snesimage_shared *s, const uint16_t *mem, 
 
 int32_t snesimage_shared_reduce_characters(snesimage_shared *s, uint32_t max_unique, uint32_t shortlist, snesimage_shared_merge_result *log, uint32_t log_cap, uint32_t *merges,
                                            uint32_t *unique) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_reduce_characters"));
     if (!s) return fail(SNES_ERR_ARG, "null set");
     if (max_unique == 0) return fail(SNES_ERR_ARG, "a budget of no characters cannot be met");
     CHECK(char_shortlist_len(&shortlist));
@@ -337,6 +341,7 @@ int32_t snesimage_shared_reduce_characters(snesimage_shared *s, uint32_t max_uni
 
 // keys sorted, no spaces: character, hflip, palette, vflip as lists of F lists in member order; characters one list for the set
 int64_t snesimage_shared_as_tilemap_json(snesimage_shared *s, char *out, int64_t cap) {
+    { const int32_t rc = shared_refuse_backdrop(s, "snesimage_shared_as_tilemap_json"); if (rc != SNES_OK) return rc; }
     { const int32_t rc = sc_check(s); if (rc != SNES_OK) return rc; }
     auto &M = members(s);
     const uint32_t ntile = sc_ntile(s), F = (uint32_t)M.size(), G = F * ntile;

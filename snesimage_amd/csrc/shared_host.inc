@@ -19,11 +19,21 @@ struct snesimage_shared {
     snesimage_sharedchar *chr = nullptr;      // the character budget of the set, made on first use
     snesimage_sharedlevel *lvl = nullptr;     // the tied level calls of the set, made on first use
     bool reduced = false;                     // snesimage_shared_reduce_characters left merged maps: stored maps that are no optimize() of the palette
+    // a backdrop set (snesimage_shared_create_backdrop; DESIGN §5c''): every member is a SNES_BACKDROP context and holds the set's B
+    bool backdrop = false;
+    hipEvent_t ev_tied = nullptr;             // orders the members' streams and the set's around a call on the backdrop slot
+    snes::TiedMember *d_tied = nullptr; std::vector<snes::TiedMember> h_tied; // ks_commit_tied's member table, and what it holds
 };
 
 namespace {
 
 std::vector<snesimage_ctx *> &members(snesimage_shared *s) { return s->b->ctx; }
+
+// What a backdrop set does not carry yet: the character budget, the refit, the set tilemap and the per-tile dither levels.
+int32_t shared_refuse_backdrop(snesimage_shared *s, const char *call) {
+    if (s && s->backdrop) return fail(SNES_ERR_UNSUPPORTED, std::string(call) + " is not supported on a backdrop set (snesimage_shared_create_backdrop): the character budget, the refit, the set tilemap and the per-tile dither levels do not carry the backdrop colour yet");
+    return SNES_OK;
+}
 
 // Every set call starts here: the set is intact, and no member was changed behind its back since the set last touched it.
 // wait: the call works on the members outside the batched launches, so the set's stream must be idle first.
@@ -66,14 +76,28 @@ int32_t shared_settle(snesimage_shared *s) {
     return SNES_OK;
 }
 
-// The palette of every member := rgb5 (as snesimage_set_palette_rgb5 does); optimize() follows in shared_settle.
+// The palette of every member := rgb5 (as snesimage_set_palette_rgb5 does: on a backdrop set the sub_count * user_size regular
+// entries, B stays); optimize() follows in shared_settle.
 int32_t shared_put_palette(snesimage_shared *s, const uint8_t *rgb5) {
     for (auto *c : members(s)) {
         CHECK(ensure_map(c));
+        if (c->backdrop) for (uint32_t p = 0; p < c->sub_count; p++) HIPCHK(hipMemcpyAsync(c->d_colors + 3 * (size_t)p * c->sub_size, rgb5 + 3 * (size_t)p * c->user_size, 3 * (size_t)c->user_size, hipMemcpyHostToDevice, c->stream));
+        else
         HIPCHK(hipMemcpyAsync(c->d_colors, rgb5, 3 * (size_t)c->ncol, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         c->tables_valid = false; c->pack_valid = false; c->inc_valid = false; c->map_synced = false; c->epoch++; c->epoch_by_commit = false;
     }
+    return SNES_OK;
+}
+
+// The regular entries of member 0's palette, sub_count * user_size of them: the whole palette of a plain context, the expanded
+// palette without its tied column of a backdrop context.
+int32_t shared_read_regular(snesimage_ctx *c0, std::vector<uint8_t> &col) {
+    std::vector<uint8_t> all(3 * (size_t)c0->ncol);
+    HIPCHK(hipMemcpyAsync(all.data(), c0->d_colors, all.size(), hipMemcpyDeviceToHost, c0->stream));
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    col.resize(3 * (size_t)c0->sub_count * c0->user_size);
+    for (uint32_t p = 0; p < c0->sub_count; p++) memcpy(&col[3 * (size_t)p * c0->user_size], &all[3 * (size_t)p * c0->sub_size], 3 * (size_t)c0->user_size);
     return SNES_OK;
 }
 
@@ -114,7 +138,7 @@ int32_t shared_kmeans_recalculate(snesimage_shared *s, const std::vector<uint32_
         }
         n.push_back((int)((long long)index.size() - off.back()));
     }
-    const int k = (int)c0->sub_size;
+    const int k = (int)c0->user_size; // (a backdrop set: the regular entries; B is not an initialiser's to move, as in kmeans_host.inc)
     for (size_t p = 0; p < n.size(); p++)
         if (!(2 <= k && k < n[p])) return fail(SNES_ERR_KMEANS, "k-means precondition 2 <= k < n violated (the reference panics here)");
     CHECK(kmeans_reserve(c0, index.size(), (int)which.size(), k));
@@ -127,11 +151,10 @@ int32_t shared_kmeans_recalculate(snesimage_shared *s, const std::vector<uint32_
     HIPCHK(hipGetLastError());
     std::vector<double> centres;
     CHECK(kmeans_run(c0, n, off, k, centres, nullptr));
-    std::vector<uint8_t> col(3 * (size_t)c0->ncol);
-    HIPCHK(hipMemcpyAsync(col.data(), c0->d_colors, col.size(), hipMemcpyDeviceToHost, c0->stream));
-    HIPCHK(hipStreamSynchronize(c0->stream));
+    std::vector<uint8_t> col;
+    CHECK(shared_read_regular(c0, col));
     for (size_t p = 0; p < which.size(); p++)
-        for (int i = 0; i < k; i++) host_centre_to_color(c0, &centres[3 * (p * k + i)], &col[3 * ((size_t)which[p] * c0->sub_size + i)]);
+        for (int i = 0; i < k; i++) host_centre_to_color(c0, &centres[3 * (p * k + i)], &col[3 * ((size_t)which[p] * c0->user_size + i)]);
     return shared_put_palette(s, col.data());
 }
 
@@ -181,17 +204,79 @@ int32_t shared_kmeans_initialize_tiles(snesimage_shared *s) {
         HIPCHK(hipStreamSynchronize(M[i]->stream));
     }
     for (size_t t = 0; t < map.size(); t++) tp[map[t].first][map[t].second] = (uint8_t)assign[t]; // lib.rs:133-138
-    std::vector<uint8_t> col(3 * (size_t)c0->ncol);
+    std::vector<uint8_t> col(3 * (size_t)c0->sub_count * c0->user_size); // (the regular entries: all there is in a plain set)
     for (int i = 0; i < k; i++) {
         uint8_t color[3];
         host_centre_to_color(c0, &centres[3 * (size_t)i], color);
-        for (uint32_t j = 0; j < c0->sub_size; j++) memcpy(&col[3 * ((size_t)i * c0->sub_size + j)], color, 3); // lib.rs:181-183
+        for (uint32_t j = 0; j < c0->user_size; j++) memcpy(&col[3 * ((size_t)i * c0->user_size + j)], color, 3); // lib.rs:181-183
     }
     for (size_t i = 0; i < F; i++) {
         HIPCHK(hipMemcpyAsync(M[i]->d_tile_pal, tp[i].data(), 1024, hipMemcpyHostToDevice, M[i]->stream));
         HIPCHK(hipStreamSynchronize(M[i]->stream));
     }
     return shared_put_palette(s, col.data());
+}
+
+// One optimizer call on the backdrop slot of a backdrop set (DESIGN §5c'').  A backdrop call leaves no row group untouched, so
+// the group-sparse launches gain nothing: every member scores the one candidate list — snesimage_step's for (seed, step_id) —
+// through its own dense tied path (SlotScope, pack mode 3) on its own stream, behind whatever the set's stream still holds,
+// so the members overlap; ks_commit_tied follows on the set's stream behind the members' events.  With SNES_DITHER every
+// member then takes the winner's map from its lanes (k_take_best_map + do_optimize(may_skip), as commit() does for a single
+// context) on its own stream, and the set's stream waits for that.  No host synchronisation once the workspaces exist.
+int32_t shared_tied_call(snesimage_shared *s, uint32_t method, uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random) {
+    auto &M = members(s);
+    snesimage_ctx *c0 = M[0];
+    if (method > 2 || channel > 2) return fail(SNES_ERR_ARG, "bad method or channel");
+    const uint32_t n = method_count(method, n_random), F = (uint32_t)M.size();
+    HIPCHK(hipSetDevice(s->b->device));
+    hipStream_t st = s->b->stream;
+    if (!s->ev_tied) HIPCHK(hipEventCreateWithFlags(&s->ev_tied, hipEventDisableTiming));
+    for (auto *c : M)
+        if (!c->tables_valid || !c->src_valid || !c->inc_valid) return fail(SNES_ERR_STATE, "a member context was modified outside the set");
+    if (s->b->busy) HIPCHK(hipEventRecord(s->ev_tied, st)); // the batched call before this one may still be running
+    std::vector<snes::TiedMember> tab(F);
+    for (uint32_t i = 0; i < F; i++) {
+        snesimage_ctx *c = M[i];
+        if (s->b->busy) HIPCHK(hipStreamWaitEvent(c->stream, s->ev_tied, 0));
+        CHECK(ensure_cand_capacity(c, n));
+        SlotScope sc(c, c->sub_count, 0);
+        CHECK(gen_candidates(c, method, sc.sp, sc.si, channel, seed, step_id, n));
+        CHECK(prep_for_slot(c, (int)sc.sp, (int)sc.si));
+        CHECK(score_list(c, c->d_cand, n, c->d_errs, 1, 0, (int)sc.sp, (int)sc.si, nullptr));
+        if (!c->ev_own) HIPCHK(hipEventCreateWithFlags(&c->ev_own, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->ev_own, c->stream));
+        HIPCHK(hipStreamWaitEvent(st, c->ev_own, 0));
+        snes::TiedMember &a = tab[i];
+        a.errors = c->d_errs; a.cand = c->d_cand; a.colors = c->d_colors; a.inc_err = c->d_inc_err; a.last = c->d_last;
+        a.T.eotf = c->d_eotf; a.T.lab_eotf = c->d_lab_eotf; a.T.rgb8 = c->d_pal_rgb8; a.T.lin = c->d_pal_lin; a.T.xyb = c->d_pal_xyb; a.T.lab = c->perceptual ? c->d_pal_lab : nullptr;
+    }
+    if (s->h_tied.size() != F || memcmp(s->h_tied.data(), tab.data(), sizeof(snes::TiedMember) * F) != 0) { // first call, or a member's candidate storage grew
+        HIPCHK(hipStreamSynchronize(st));
+        if (!s->d_tied) HIPCHK(hipMalloc(&s->d_tied, sizeof(snes::TiedMember) * F));
+        HIPCHK(hipMemcpy(s->d_tied, tab.data(), sizeof(snes::TiedMember) * F, hipMemcpyHostToDevice));
+        s->h_tied = tab;
+    }
+    hipLaunchKernelGGL(ks_commit_tied, dim3(1), dim3(256), 0, st, (const snes::TiedMember *)s->d_tied, (int)F, (int)n, method == SNES_METHOD_NES ? 1 : 0, (int)c0->user_size, (int)c0->sub_count,
+                       (int)c0->sub_size, s->d_joint);
+    HIPCHK(hipGetLastError());
+    if (c0->dither) HIPCHK(hipEventRecord(s->ev_tied, st));
+    for (auto *c : M) { // what commit() leaves behind in a context after a tied call
+        c->pack_valid = false; c->sp.plist_valid = false; c->sp.counters_cleared = false; c->epoch++; c->epoch_by_commit = false;
+        if (!c->dither) { c->map_pending = true; c->map_synced = true; c->inc_valid = true; continue; }
+        HIPCHK(hipStreamWaitEvent(c->stream, s->ev_tied, 0));
+        bool may_skip = false;
+        if (c->d_skip) { // the winner's map is optimize() of the committed palette when a lane of this member scored it
+            hipLaunchKernelGGL(k_take_best_map, dim3(1), dim3(1024), 0, c->stream, c->d_last, c->d_bestrecs_all, c->best_valid ? (int)c->nlanes : 0, c->d_bestmaps_all, (int)c->npx, 1, c->d_map, c->d_skip);
+            may_skip = true;
+        }
+        c->best_valid = false;
+        CHECK(do_optimize(c, may_skip)); // lib.rs:237
+        c->inc_valid = true; // ks_commit_tied left the committed state's error in d_inc_err
+        HIPCHK(hipEventRecord(c->ev_own, c->stream));
+        HIPCHK(hipStreamWaitEvent(st, c->ev_own, 0));
+    }
+    s->b->busy = true;
+    return SNES_OK;
 }
 
 } // namespace
@@ -230,6 +315,70 @@ int32_t snesimage_shared_create(snesimage_ctx **ctxs, uint32_t n, snesimage_shar
     return SNES_OK;
 }
 
+// A set of SNES_BACKDROP members that carries B (DESIGN §5c''): the batch's checks through its internal path, the regular
+// entries compared, B written to every member, then everything a set call takes for granted (shared_settle).
+int32_t snesimage_shared_create_backdrop(snesimage_ctx **ctxs, uint32_t n, const uint8_t *backdrop_rgb5, snesimage_shared **out) {
+    if (!ctxs || !out || n == 0) return fail(SNES_ERR_ARG, "null pointer or empty set");
+    *out = nullptr;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!ctxs[i]) return fail(SNES_ERR_ARG, "null context in set");
+        if (ctxs[i]->group) return fail(SNES_ERR_STATE, "context belongs to a group");
+        if (!ctxs[i]->backdrop) return fail(SNES_ERR_ARG, "member " + std::to_string(i) + " was created without SNES_BACKDROP: a set of plain contexts is made by snesimage_shared_create");
+        if (ctxs[i]->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
+        for (uint32_t j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(SNES_ERR_ARG, "a context appears twice in the set");
+    }
+    if (backdrop_rgb5 && (backdrop_rgb5[0] > 31 || backdrop_rgb5[1] > 31 || backdrop_rgb5[2] > 31)) return fail(SNES_ERR_ARG, "backdrop channels are 5-bit values");
+    snesimage_batch *b = nullptr;
+    CHECK(batch_create_members(ctxs, n, &b, true));
+    std::unique_ptr<snesimage_shared> s(new snesimage_shared());
+    s->b = b; s->backdrop = true;
+    auto undo = [&](int32_t rc) { std::string keep = g_err; snesimage_shared_destroy(s.release()); g_err = keep; return rc; };
+    std::vector<uint8_t> p0, pi;
+    for (uint32_t i = 0; i < n; i++) {
+        if (shared_read_regular(ctxs[i], i ? pi : p0) != SNES_OK) return undo(SNES_ERR_HIP);
+        if (i && pi != p0) return undo(fail(SNES_ERR_STATE, "the members of a set must hold the same palette (the regular entries of member " + std::to_string(i) + " differ from member 0's)"));
+    }
+    if (hipMalloc(&s->d_joint, sizeof(snes::StepResult)) != hipSuccess || hipMalloc(&s->d_tab, sizeof(double *) * n) != hipSuccess)
+        return undo(fail(SNES_ERR_HIP, "hipMalloc failed"));
+    uint8_t B[3] = {0, 0, 0};
+    if (backdrop_rgb5) memcpy(B, backdrop_rgb5, 3);
+    else { // snesimage_create's rule on the member stack
+        snesimage_ctx *c0 = ctxs[0];
+        unsigned long long sum[3] = {0, 0, 0}, cnt = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint8_t *rgba = ctxs[i]->h_orig.data();
+            for (size_t px = 0; px < c0->npx; px++)
+                if (rgba[4 * px + 3] != 0) { sum[0] += rgba[4 * px]; sum[1] += rgba[4 * px + 1]; sum[2] += rgba[4 * px + 2]; cnt++; }
+        }
+        if (cnt) for (int ch = 0; ch < 3; ch++) B[ch] = (uint8_t)(((sum[ch] + cnt / 2) / cnt) >> 3);
+        if (c0->nes) { uint8_t raw[3] = {B[0], B[1], B[2]}; host_new_nes_only(raw, c0->perceptual, c0->h_lab_eotf, B); }
+    }
+    s->epoch.resize(n);
+    for (uint32_t i = 0; i < n; i++) { const int32_t rc = write_backdrop(ctxs[i], B); if (rc != SNES_OK) return undo(rc); }
+    { const int32_t rc = shared_settle(s.get()); if (rc != SNES_OK) return undo(rc); }
+    *out = s.release();
+    return SNES_OK;
+}
+
+int32_t snesimage_shared_get_backdrop_rgb5(snesimage_shared *s, uint8_t *out) {
+    if (!out) return fail(SNES_ERR_ARG, "null pointer");
+    CHECK(shared_enter(s, true, true));
+    if (!s->backdrop) return fail(SNES_ERR_ARG, "the set was created without a backdrop colour (snesimage_shared_create_backdrop)");
+    snesimage_ctx *c0 = members(s)[0];
+    HIPCHK(hipMemcpyAsync(out, c0->d_colors + 3 * (size_t)c0->user_size, 3, hipMemcpyDeviceToHost, c0->stream));
+    HIPCHK(hipStreamSynchronize(c0->stream));
+    return SNES_OK;
+}
+
+int32_t snesimage_shared_set_backdrop_rgb5(snesimage_shared *s, const uint8_t *in) {
+    if (!in) return fail(SNES_ERR_ARG, "null pointer");
+    CHECK(shared_enter(s));
+    if (!s->backdrop) return fail(SNES_ERR_ARG, "the set was created without a backdrop colour (snesimage_shared_create_backdrop)");
+    if (in[0] > 31 || in[1] > 31 || in[2] > 31) return fail(SNES_ERR_ARG, "backdrop channels are 5-bit values");
+    for (auto *c : members(s)) CHECK(write_backdrop(c, in));
+    return shared_settle(s);
+}
+
 void snesimage_shared_destroy(snesimage_shared *s) {
     if (!s) return;
     (void)hipSetDevice(s->b->device);
@@ -241,6 +390,8 @@ void snesimage_shared_destroy(snesimage_shared *s) {
     if (s->d_joint) (void)hipFree(s->d_joint);
     if (s->d_sum) (void)hipFree(s->d_sum);
     if (s->d_tab) (void)hipFree(s->d_tab);
+    if (s->d_tied) (void)hipFree(s->d_tied);
+    if (s->ev_tied) (void)hipEventDestroy(s->ev_tied);
     delete s;
 }
 
@@ -299,8 +450,9 @@ int32_t snesimage_shared_score_candidates(snesimage_shared *s, uint32_t palette,
         snesimage_ctx *c = M[i];
         CHECK(ensure_cand_capacity(c, n));
         HIPCHK(hipMemcpyAsync(c->d_cand_sel, rgb5, 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        CHECK(prep_for_slot(c, (int)palette, (int)index));
-        CHECK(score_list(c, c->d_cand_sel, n, c->d_errs_sel, 1, 0, (int)palette, (int)index, nullptr));
+        SlotScope sc(c, palette, index); // (the backdrop slot of a backdrop set: the member's dense tied path)
+        CHECK(prep_for_slot(c, (int)sc.sp, (int)sc.si));
+        CHECK(score_list(c, c->d_cand_sel, n, c->d_errs_sel, 1, 0, (int)sc.sp, (int)sc.si, nullptr));
         tab[i] = c->d_errs_sel;
     }
     for (auto *c : M) HIPCHK(hipStreamSynchronize(c->stream));
@@ -316,6 +468,11 @@ int32_t snesimage_shared_score_candidates(snesimage_shared *s, uint32_t palette,
 int32_t snesimage_shared_step_async(snesimage_shared *s, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random) {
     CHECK(shared_enter(s, false));
     auto &M = members(s);
+    if (s->backdrop && palette == M[0]->sub_count && index == 0) { // the backdrop slot
+        CHECK(shared_tied_call(s, method, channel, seed, step_id, n_random));
+        for (size_t i = 0; i < M.size(); i++) s->epoch[i] = M[i]->epoch;
+        return SNES_OK;
+    }
     const std::vector<uint64_t> seeds(M.size(), seed); // one candidate list for every member: snesimage_step's for (seed, step_id)
     CHECK(batch_call(s->b, method, palette, index, channel, seeds.data(), step_id, n_random, s->d_joint));
     for (size_t i = 0; i < M.size(); i++) s->epoch[i] = M[i]->epoch;

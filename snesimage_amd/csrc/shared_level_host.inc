@@ -193,6 +193,7 @@ int32_t sl_tied_sweep(snesimage_shared *s, uint32_t first_tile, uint32_t n_tiles
 extern "C" {
 
 int32_t snesimage_shared_set_ordered_dither_bank(snesimage_shared *s, const int8_t *tables, uint32_t n, uint32_t L, uint32_t start_level) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_set_ordered_dither_bank"));
     if (!s) return fail(SNES_ERR_ARG, "null set");
     const bool off = L == 0 || n == 0;
     if (!off) {
@@ -243,6 +244,7 @@ int32_t snesimage_shared_set_ordered_dither_bank(snesimage_shared *s, const int8
 }
 
 int32_t snesimage_shared_set_tile_levels(snesimage_shared *s, uint32_t member, const uint8_t *in) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_set_tile_levels"));
     if (!s || !in) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(shared_enter(s));
     auto &M = members(s);
@@ -264,6 +266,7 @@ int32_t snesimage_shared_set_tile_levels(snesimage_shared *s, uint32_t member, c
 }
 
 int32_t snesimage_shared_score_tile_levels(snesimage_shared *s, const uint16_t *tiles, const uint8_t *levels, uint32_t n, double *errors, double *member_errors) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_score_tile_levels"));
     if (!s) return fail(SNES_ERR_ARG, "null set");
     if (!tiles || !levels || !errors) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(shared_enter(s, true, true)); // (the state is left as it is: merged maps of a character reduction are refused below, not replaced)
@@ -296,6 +299,7 @@ int32_t snesimage_shared_score_tile_levels(snesimage_shared *s, const uint16_t *
 }
 
 int32_t snesimage_shared_level_sweep(snesimage_shared *s, uint32_t first_tile, uint32_t n_tiles, uint32_t window, uint32_t tied, snesimage_tile_result *log, snesimage_run_stats *stats) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_level_sweep"));
     if (!s) return fail(SNES_ERR_ARG, "null set");
     snesimage_run_stats T{};
     if (stats) *stats = T;

@@ -141,6 +141,7 @@ int32_t sr_incumbents(snesimage_shared *s, std::vector<double> &inc, double *E) 
 extern "C" {
 
 int32_t snesimage_shared_character_fits(snesimage_shared *s, uint16_t *reps, uint16_t *mem, uint64_t *gains, uint8_t *fits, uint32_t *n) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_character_fits"));
     CHECK(sc_check(s));
     SrSnapshot snap;
     CHECK(sr_snapshot(s, snap));
@@ -164,6 +165,7 @@ int32_t snesimage_shared_character_fits(snesimage_shared *s, uint16_t *reps, uin
 }
 
 int32_t snesimage_shared_score_refits(snesimage_shared *s, const uint16_t *reps, uint32_t n, double *errors, double *member_errors, uint8_t *maps_out) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_score_refits"));
     if (!s) return fail(SNES_ERR_ARG, "null set");
     if (!reps || !errors) return fail(SNES_ERR_ARG, "null pointer");
     CHECK(sc_check(s));
@@ -223,6 +225,7 @@ int32_t snesimage_shared_score_refits(snesimage_shared *s, const uint16_t *reps,
 
 int32_t snesimage_shared_refit_characters(snesimage_shared *s, uint32_t window, snesimage_shared_refit_result *log, uint32_t log_cap, uint32_t *calls, uint32_t *accepted, uint32_t *unique,
                                           snesimage_run_stats *stats) {
+    CHECK(shared_refuse_backdrop(s, "snesimage_shared_refit_characters"));
     if (!s) return fail(SNES_ERR_ARG, "null set");
     CHECK(sc_check(s));
     SrSnapshot snap; // holds for the whole sweep, as w.rep, w.flip, w.rfits and w.rfit do

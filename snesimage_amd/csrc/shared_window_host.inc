@@ -109,7 +109,8 @@ int32_t shared_window_run(snesimage_shared *s, uint32_t n_slots, uint64_t seed, 
     { uint32_t p = palette, i = index, ch = channel, st = step, m = 0, m0 = 0;
       while (K < n_slots) {
           const uint32_t cp = p, ci = i, cc = ch;
-          snesimage_schedule_next(c0->sub_count, c0->sub_size, c0->nes ? 1 : 0, &p, &i, &ch, &st, &m);
+          if (s->backdrop && cp == c0->sub_count) break; // a window ends in front of a backdrop call (snesimage_shared_run_slots steps it on its own)
+          ctx_schedule_next(c0, c0->nes ? 1 : 0, &p, &i, &ch, &st, &m); // (a backdrop set: snesimage_schedule_next_backdrop)
           if (K == 0) m0 = m; else if (m != m0) break;
           calls[K++] = Call{m, cp, ci, cc};
       } }
@@ -217,11 +218,13 @@ int32_t snesimage_shared_run_slots(snesimage_shared *s, uint32_t n_calls, uint64
             if (K > kmax) K = kmax;
         }
         uint32_t taken = 1, used = 1, acc = 0, n = 0;
-        if (!windows || !synced || (window == 0 && K == 1 && s->win->adapt == 1)) {
-            // One call on its own: what the windows do not cover, a first call that starts from a palette_map which is not
-            // optimize() of the palette, and a phase in which the size policy finds one call per launch set fastest
+        const bool tied = s->backdrop && *palette == c0->sub_count; // a backdrop call: no window's, and nothing the size policy learns from
+        if (!windows || !synced || (window == 0 && K == 1 && s->win->adapt == 1) || tied) {
+            // One call on its own: what the windows do not cover (a backdrop call among it: DESIGN §5c''), a first call that starts
+            // from a palette_map which is not optimize() of the palette, and a phase in which the size policy finds one call per
+            // launch set fastest
             uint32_t p = *palette, i = *index, ch = *channel, m = 0, st = *step;
-            snesimage_schedule_next(c0->sub_count, c0->sub_size, nes, &p, &i, &ch, &st, &m);
+            ctx_schedule_next(c0, nes, &p, &i, &ch, &st, &m);
             CHECK(snesimage_shared_step_async(s, m, *palette, *index, *channel, seed, first_step_id + done, n_random));
             snesimage_call_result r;
             CHECK(snesimage_shared_last_step(s, &r));
@@ -231,10 +234,10 @@ int32_t snesimage_shared_run_slots(snesimage_shared *s, uint32_t n_calls, uint64
         } else {
             CHECK(shared_window_run(s, K, seed, first_step_id + done, *palette, *index, *channel, *step, n_random, log ? log + done : nullptr, &taken, &n, &used, &acc));
         }
-        for (uint32_t j = 0; j < used; j++) snesimage_schedule_next(c0->sub_count, c0->sub_size, nes, palette, index, channel, step, &method);
+        for (uint32_t j = 0; j < used; j++) ctx_schedule_next(c0, nes, palette, index, channel, step, &method);
         done += used;
         S.calls += used; S.windows++; S.scored += (uint64_t)taken * n; S.useful += (uint64_t)used * n; S.accepted += acc;
-        if (windows && synced) s->win->adapt = s->win->policy.next(used, acc, 1, kmax, 1, taken, (double)F);
+        if (windows && synced && !tied) s->win->adapt = s->win->policy.next(used, acc, 1, kmax, 1, taken, (double)F);
     }
     if (stats) *stats = S;
     return SNES_OK;

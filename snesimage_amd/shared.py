@@ -5,6 +5,10 @@ screens of one level — on the SNES everything drawn on one background reads th
 the same palette, and optimizes that palette for all of them: the error of the set is the sum of the members' errors, in
 member order, and every optimizer call commits once on that sum.  Each member keeps its own tile palettes and palette map.
 The initialisers are the reference's own on the member stack (the members top to bottom, W x F*H).
+
+`SharedPalette(images, backdrop=True)` (or `backdrop=(r, g, b)`) makes a backdrop set (DESIGN §5c''): every member is an
+`OptimizedImage(..., backdrop=True)` and the set keeps one backdrop colour — CGRAM word 0, which all frames of a background
+read — in all of them, optimized on the set's error at the backdrop slot `(sub_count, 0)`.
 """
 import ctypes as C
 
@@ -24,9 +28,12 @@ SHARED_REFIT_LOG_DTYPE = np.dtype([("error", np.float64), ("gain", np.uint64), (
 class SharedPalette:
     """A set over `images` (OptimizedImage, in member order).  Destroy the set (close) before its members."""
 
-    def __init__(self, images, ordered_dither=None):
+    def __init__(self, images, ordered_dither=None, backdrop=None):
         """ordered_dither: an ordered-dither table (api.bayer_offsets or any (n, n) int8 tile) given to every member before the
-        set is formed; None leaves the members' tables as they are (the library refuses members whose tables differ)."""
+        set is formed; None leaves the members' tables as they are (the library refuses members whose tables differ).
+        backdrop: None — a plain set; True — a backdrop set (every member an OptimizedImage(..., backdrop=True)) whose B starts
+        as the mean of the opaque pixels of all members; three 5-bit values — a backdrop set with that B
+        (snesimage_shared_create_backdrop)."""
         self.images = list(images)
         self._L = _ffi.load()
         if ordered_dither is not None:
@@ -37,7 +44,12 @@ class SharedPalette:
                     img.set_ordered_dither(ordered_dither)
         arr = (C.c_void_p * len(self.images))(*[img._c for img in self.images])
         h = C.c_void_p()
-        self._chk(self._L.snesimage_shared_create(arr if self.images else None, len(self.images), C.byref(h)))
+        self.has_backdrop = backdrop is not None and backdrop is not False
+        if not self.has_backdrop:
+            self._chk(self._L.snesimage_shared_create(arr if self.images else None, len(self.images), C.byref(h)))
+        else:
+            b = None if backdrop is True else np.ascontiguousarray(backdrop, np.uint8).reshape(3)
+            self._chk(self._L.snesimage_shared_create_backdrop(arr if self.images else None, len(self.images), None if b is None else _p(b, _ffi._u8p), C.byref(h)))
         self._s = h
         first = self.images[0]
         self.sub_count, self.sub_size, self.flags = first.sub_count, first.sub_size, first.flags
@@ -109,7 +121,7 @@ class SharedPalette:
         log = []
         for j in range(n_calls):
             p, idx, ch = st[0].value, st[1].value, st[2].value
-            self._L.snesimage_schedule_next(self.sub_count, self.sub_size, nes, C.byref(st[0]), C.byref(st[1]), C.byref(st[2]),
+            (self._L.snesimage_schedule_next_backdrop if self.has_backdrop else self._L.snesimage_schedule_next)(self.sub_count, self.sub_size, nes, C.byref(st[0]), C.byref(st[1]), C.byref(st[2]),
                                             C.byref(st[3]), C.byref(m))
             self._chk(self._L.snesimage_shared_step_async(self._s, m.value, p, idx, ch, seed, first_step_id + j,
                                                           n_random if m.value == METHOD_RANDOM else 0))
@@ -304,7 +316,20 @@ class SharedPalette:
     # -- state ------------------------------------------------------------------------------------
     @property
     def palette(self):
+        """The shared palette: sub_count * sub_size entries (on a backdrop set the regular entries; B is `backdrop`)."""
         return self.images[0].palette
+
+    @property
+    def backdrop(self):
+        """B of a backdrop set (three raw 5-bit values); setting it writes all tied entries of all members, then optimize()."""
+        out = np.zeros(3, np.uint8)
+        self._chk(self._L.snesimage_shared_get_backdrop_rgb5(self._s, _p(out, _ffi._u8p)))
+        return out
+
+    @backdrop.setter
+    def backdrop(self, v):
+        v = np.ascontiguousarray(v, np.uint8).reshape(3)
+        self._chk(self._L.snesimage_shared_set_backdrop_rgb5(self._s, _p(v, _ffi._u8p)))
 
     @palette.setter
     def palette(self, v):
