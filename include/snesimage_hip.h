@@ -706,6 +706,45 @@ int32_t snesimage_shared_set_ordered_dither_bank(snesimage_shared *set, const in
 int32_t snesimage_shared_set_tile_levels(snesimage_shared *set, uint32_t member, const uint8_t *levels /* 1024 */);
 int32_t snesimage_shared_score_tile_levels(snesimage_shared *set, const uint16_t *tiles, const uint8_t *levels, uint32_t n, double *errors, double *member_errors /* n*F, optional */);
 int32_t snesimage_shared_level_sweep(snesimage_shared *set, uint32_t first_tile, uint32_t n_tiles, uint32_t window, uint32_t tied, snesimage_tile_result *log, snesimage_run_stats *stats);
+/* NOT a reference method: GUIDED CALLS.  optimize_palette_entry_random (lib.rs:191-240) draws its candidates
+ * uniformly from the 32,768 colours of BGR555; the reference's TODO.md:33-35 asks for something better.  A guided call ranks
+ * ALL 32,768 colours for the slot by a cheap, exact, integer proxy and lets error() decide among the K the proxy likes, as the
+ * merges of the character budget do.  Off unless called: no other entry point changes, snesimage_step keeps refusing
+ * method > 2.  Integers only, except the objective.  For a slot (p, i) of a context (C, S):
+ *   POPULATION: the pixels with alpha > 0 in tiles with tile_palettes[t] == p.  Colours are those of the TARGET image T (the
+ *     original, or what an ordered-dither table or bank made of it).
+ *   FLOOR m(x): the minimum of red_mean_key(T(x), 8-bit expansion of entry j) over the entries j != i of subpalette p — the
+ *     integer key of lib.rs:1080-1088 without the square root.  On a backdrop context the expanded subpalette counts: B is one of
+ *     the other entries.  With S == 1, m(x) = 0xFFFFFFFF.
+ *   COST of colour c, for every BGR555 colour, indexed u = r | g << 5 | b << 10 (as_u16, lib.rs:679-681):
+ *     cost(u) = sum over the population of min(m(x), red_mean_key(T(x), 8-bit expansion of c)), in a uint64_t (below 2^45):
+ *     what the pixels of subpalette p would cost if entry i were c — the k-means objective in the redmean metric.
+ *   TIED SLOT of a backdrop context (palette == C, index == 0): the population is every opaque pixel, m(x) runs over the S
+ *     regular entries of the pixel's own subpalette.
+ *   The proxy is this key on every context, SNES_PERCEPTUAL and SNES_DITHER included: it only shortlists, the error decides.
+ *   SHORTLIST of K (1..64, 0 = 16; the default mirrors --merge-shortlist and is a choice, not a measurement): the K colours
+ *     lowest in (cost, u), compared lexicographically, the slot's current colour left out; candidates 0 .. K-1 in that order.  An
+ *     empty population needs no rule: every cost is 0, the first K colours are scored, all tie with the incumbent.
+ *   GUIDED CALL: the shortlist scored as snesimage_score_candidates scores it, acceptance as lib.rs:216-219 (best := incumbent,
+ *     strict <, ascending k).  Afterwards the context is exactly what snesimage_step(SNES_METHOD_RANDOM, ...) leaves after a call
+ *     that drew these K candidates: the same commit (its --dither branch, the tied spread of a backdrop slot), the same
+ *     snesimage_last_step record.
+ *   GUIDED SWEEP: one guided call on every slot in the order of snesimage_schedule_next (snesimage_schedule_next_backdrop on a
+ *     backdrop context: the tied slot last), enqueued without a host synchronisation between them — the generator reads the
+ *     palette and tile_palettes on the device, so call j + 1 sees call j's commit; the records are read back once at the end.
+ *     stats: calls = windows = the slots, accepted = the calls that changed the palette, scored = useful = calls * K.
+ * snesimage_guided_costs: cost(u) for all 32,768 u; synchronous; the state is unchanged.  snesimage_guided_candidates: the
+ * shortlist (k * 3 raw 5-bit values) and optionally its costs; the state is unchanged.
+ * The workspace (the pixel list, 512 KB at 256 x 256, and the cost table, 256 KB) is allocated by the first of these calls and
+ * freed with the context; a failed allocation (SNES_ERR_HIP) leaves the context as it was.
+ * Refusals: SNES_ERR_ARG for a null context or pointer, a slot out of range or k > 64; SNES_ERR_UNSUPPORTED on a SNES_NES
+ * context (its NES call already scores all 56 colours of the table); SNES_ERR_STATE between the phases of a split-phase step or
+ * window and on a context lent to a batch, a set or a group. */
+int32_t snesimage_guided_costs(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint64_t *costs /* 32768, indexed by u */);
+int32_t snesimage_guided_candidates(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k, uint8_t *rgb5 /* k*3 */, uint64_t *costs /* k, optional */);
+int32_t snesimage_guided_step(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k, double *best_error, uint8_t *best_rgb5);
+int32_t snesimage_guided_step_async(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k); /* results via snesimage_last_step */
+int32_t snesimage_guided_sweep(snesimage_ctx *ctx, uint32_t k, snesimage_call_result *log /* optional, one per slot */, snesimage_run_stats *stats /* optional */);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);

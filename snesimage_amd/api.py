@@ -500,6 +500,43 @@ class OptimizedImage:
         out = np.array([(r.error, r.sub, r.changed) for r in log[:n_tiles]], dtype=TILE_LOG_DTYPE)
         return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
+    # -- guided calls (not in the reference; include/snesimage_hip.h) -------------------------------------------------
+    def guided_costs(self, palette, index):
+        """The proxy cost of every BGR555 colour for the slot: 32,768 uint64, indexed u = r | g << 5 | b << 10 — what the
+        slot's pixels would cost in the redmean key if the entry were that colour.  The state is left unchanged."""
+        out = np.zeros(32768, np.uint64)
+        self._chk(self._L.snesimage_guided_costs(self._c, int(palette), int(index), _p(out, _ffi._u64p)))
+        return out
+
+    def guided_candidates(self, palette, index, k=0):
+        """The k (1..64, 0 = 16) colours lowest in (cost, u) but the slot's current colour, in that order; the state is
+        left unchanged.  Returns (rgb5[k, 3], costs[k])."""
+        n = int(k) if k else 16
+        rgb5, costs = np.zeros((max(n, 1), 3), np.uint8), np.zeros(max(n, 1), np.uint64)
+        self._chk(self._L.snesimage_guided_candidates(self._c, int(palette), int(index), int(k), _p(rgb5, _ffi._u8p), _p(costs, _ffi._u64p)))
+        return rgb5[:n], costs[:n]
+
+    def guided_step(self, palette, index, k=0):
+        """One guided call: the shortlist of k goes through the scorer and the acceptance of `step` -> (error, best rgb5);
+        `last_step` reports the record."""
+        err = C.c_double(0)
+        best = np.zeros(3, np.uint8)
+        self._chk(self._L.snesimage_guided_step(self._c, int(palette), int(index), int(k), C.byref(err), _p(best, _ffi._u8p)))
+        return err.value, best
+
+    def guided_step_async(self, palette, index, k=0):
+        self._chk(self._L.snesimage_guided_step_async(self._c, int(palette), int(index), int(k)))
+
+    def guided_sweep(self, k=0):
+        """One guided call on every slot in the schedule's order (the backdrop slot last), enqueued back to back.
+        Returns (log, stats): log[j] = (error, best_k, rgb5, changed) after call j, as `run_slots` reports."""
+        n = self.sub_count * self.sub_size + (1 if self.has_backdrop else 0)
+        log = (_ffi.CallResult * n)()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_guided_sweep(self._c, int(k), log, C.byref(stats)))
+        out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log]
+        return out, {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
     def target_rgba(self):
         """The image the nearest-colour choice is made against: the original plus the table's offsets, clamped; alpha kept."""
         out = np.zeros((self.h, self.w, 4), np.uint8)

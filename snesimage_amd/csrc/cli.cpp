@@ -37,6 +37,8 @@
 // --set-tilemap FILE writes the set's characters and one tilemap per frame (snesimage_shared_as_tilemap_json).
 // --refit-set-tiles N (with --share) runs up to N refit sweeps over the whole set behind that (snesimage_shared_refit_characters):
 // every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
+// --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_sweep): on every
+// slot the --guided-shortlist K colours an integer proxy ranks best among all 32,768 are scored, and the error decides.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -129,6 +131,11 @@ void usage() {
             "      --tile-moves <K>     every K sweeps of the palette, try every tile in every other subpalette and keep the moves that\n"
             "                           lower the error itself (dithering included); cannot be used with --reassign-tiles, which\n"
             "                           moves tiles by colour distance and undoes these moves, nor with --devices\n"
+            "      --guided <G>         behind every G sweeps of the palette, one guided sweep: on every slot, all 32,768 colours are ranked by what\n"
+            "                           the slot's pixels would cost in colour distance, and the --guided-shortlist best are scored by the error\n"
+            "                           itself; runs in front of --reassign-tiles, --tile-moves and --tile-dither; with --backdrop-fixed the\n"
+            "                           backdrop slot is passed by; not with --share, --devices or --nes\n"
+            "      --guided-shortlist <K>  colours scored per guided call, 1..64 [default: 16: a choice, not a measurement]; needs --guided\n"
             "      --max-tiles <N>      after the last optimizer call, merge tiles until at most N distinct characters are left (tiles equal\n"
             "                           under the tilemap's flips count once); each merge is the one with the lowest error among the\n"
             "                           --merge-shortlist cheapest by colour distance; not with --share or --devices\n"
@@ -302,6 +309,7 @@ int main(int argc, char **argv) {
     bool set_backdrop = false, set_backdrop_fixed = false; std::string set_backdrop_arg; // the backdrop colour of a --share set
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
+    uint32_t guided_every = 0, guided_short = 16; bool guided_given = false, guided_short_given = false; std::string guided_arg, guided_short_arg;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -335,6 +343,8 @@ int main(int argc, char **argv) {
         else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
         else if (a == "--tile-moves") tile_every = (uint32_t)strtoul(need("--tile-moves"), nullptr, 10);
         else if (a == "--resume") resume_file = need("--resume");
+        else if (a == "--guided") { guided_given = true; guided_arg = need("--guided"); }
+        else if (a == "--guided-shortlist") { guided_short_given = true; guided_short_arg = need("--guided-shortlist"); }
         else if (a == "--max-tiles") { max_tiles_given = true; max_tiles_arg = need("--max-tiles"); }
         else if (a == "--merge-shortlist") { merge_short_given = true; merge_short_arg = need("--merge-shortlist"); }
         else if (a == "--refit-tiles") { refit_given = true; refit_arg = need("--refit-tiles"); }
@@ -357,6 +367,20 @@ int main(int argc, char **argv) {
     if (tile_every) { // objective-scored moves and the colour-distance proxy undo each other; no group entry point for the moves
         const char *bad = !devices.empty() ? "'--devices'" : (reassign_every ? "'--reassign-tiles'" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--tile-moves <K>' cannot be used with %s\n", bad); return 2; }
+    }
+    if (guided_given || guided_short_given) { // guided sweeps: said before any file or device is touched
+        if (!guided_given) { fprintf(stderr, "error: '--guided-shortlist <K>' needs '--guided <G>'\n"); return 2; }
+        const char *bad = !shares.empty() ? "'--share'" : !devices.empty() ? "'--devices'" : (flags & SNES_NES) ? "'--nes'" : nullptr; // one context of its own; the NES call scores its whole table already
+        if (bad) { fprintf(stderr, "error: the argument '--guided <G>' cannot be used with %s\n", bad); return 2; }
+        char *end = nullptr;
+        const unsigned long g = strtoul(guided_arg.c_str(), &end, 10);
+        if (guided_arg.empty() || guided_arg[0] == '-' || *end || g < 1 || g > 1000000) { fprintf(stderr, "error: invalid value '%s' for '--guided <G>': expected a number of sweeps, 1 or more\n", guided_arg.c_str()); return 2; }
+        guided_every = (uint32_t)g;
+        if (guided_short_given) {
+            const unsigned long k = strtoul(guided_short_arg.c_str(), &end, 10);
+            if (guided_short_arg.empty() || guided_short_arg[0] == '-' || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--guided-shortlist <K>': expected 1..64\n", guided_short_arg.c_str()); return 2; }
+            guided_short = (uint32_t)k;
+        }
     }
     if (max_tiles_given || merge_short_given || refit_given || !tilemap_file.empty()) { // said before any file or device is touched
         char *end = nullptr;
@@ -735,7 +759,25 @@ int main(int argc, char **argv) {
                  " launch sets; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
     };
+    auto guided_sweep = [&]() { // one guided call on every slot, each decided by error(); --backdrop-fixed passes the backdrop slot by
+        snesimage_run_stats gs{};
+        double e0 = 0.0, e1 = 0.0;
+        if (snesimage_error(ctx, &e0) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+        if (bd_fixed) {
+            for (uint32_t p = 0; p < count; p++)
+                for (uint32_t ix = 0; ix < size; ix++) {
+                    int32_t k = -1;
+                    if (snesimage_guided_step_async(ctx, p, ix, guided_short) != 0 || snesimage_last_step(ctx, nullptr, nullptr, &k) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+                    gs.calls += 1; gs.accepted += k >= 0 ? 1u : 0u;
+                }
+        } else if (snesimage_guided_sweep(ctx, guided_short, nullptr, &gs) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+        if (snesimage_error(ctx, &e1) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+        log_info("Guided sweep: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
+        load_before(); // (the colours the next calls' reports compare with)
+    };
     auto end_of_sweep = [&]() {
+        if (guided_every && step != sweep && step % guided_every == 0) guided_sweep(); // in front of everything that moves tiles: they see the palette it leaves
         if (reassign_every && step != sweep && step % reassign_every == 0) { // a sweep over every slot has just ended (src/lib.rs:925-931)
             uint32_t moved = 0;
             if (set) { if (snesimage_shared_reassign_tiles(set, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error()); }
@@ -766,7 +808,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every || level_every || set_level_every || bd_fixed) { // calls left in the current sweep
+            if (reassign_every || tile_every || level_every || set_level_every || guided_every || bd_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;
