@@ -745,6 +745,38 @@ int32_t snesimage_guided_candidates(snesimage_ctx *ctx, uint32_t palette, uint32
 int32_t snesimage_guided_step(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k, double *best_error, uint8_t *best_rgb5);
 int32_t snesimage_guided_step_async(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k); /* results via snesimage_last_step */
 int32_t snesimage_guided_sweep(snesimage_ctx *ctx, uint32_t k, snesimage_call_result *log /* optional, one per slot */, snesimage_run_stats *stats /* optional */);
+/* NOT a reference method: GUIDED CALLS OF A SET (DESIGN 5f').  The proxy above carries over to a shared-palette set without a new
+ * definition: the palette and the slot are shared and the floor of a pixel depends on that pixel's own tile only.  Integers only,
+ * except the objective.  For a set of F members with geometry (C, S), the shared palette and slot (p, i):
+ *   POPULATION: the opaque pixels (alpha > 0) of every tile of every member whose tile_palettes value is p.  Colours are read from
+ *     each member's own TARGET image T_f, so a member's ordered-dither table or level bank is followed without another argument.
+ *   FLOOR m(x) and the key: exactly as above, with the shared palette; on a backdrop set the expanded subpalette counts.
+ *   COST: cost(u) = sum over the members f, sum over the pixels x of member f, of min(m(x), red_mean_key(T_f(x), rgb8(u))), in a
+ *     uint64_t: the sum over the members of the table above for that member.
+ *   TIED SLOT of a backdrop set (palette == C, index == 0): every opaque pixel of every member; the floor runs over the S regular
+ *     entries of the pixel's own subpalette.
+ *   SHORTLIST: the rule above: K in 1..64 (0 = 16), lowest (cost, u), the slot's current colour left out, candidates 0 .. K-1 in
+ *     that order.
+ *   CAP: a set of more than 8,192 tiles in all (the character budget's cap) is refused with SNES_ERR_UNSUPPORTED.  The selection
+ *     packs cost << 15 | u, so a cost must stay below 2^49; 8,192 tiles x 64 pixels x 299,505,150 (the largest key) < 2^47.2.
+ *   GUIDED SET CALL: the shortlist is written into every member's candidate list; from there the call is
+ *     snesimage_shared_step_async(SNES_METHOD_RANDOM, ...) word for word — scored by every member, committed once on the joint error
+ *     (best := E, strict <, ascending k), the tied slot through the members' dense tied paths.  Afterwards the set is exactly what
+ *     snesimage_shared_step(SNES_METHOD_RANDOM, ...) leaves after a call that drew these K candidates: every member's palette, map,
+ *     incumbent and cache flags, and the record of snesimage_shared_last_step.
+ *   GUIDED SET SWEEP: one guided call on every slot in the schedule's slot order, on a backdrop set the tied slot last, enqueued
+ *     without a host synchronisation between them (beyond what the batched calls' ring of four argument blocks asks for); the records
+ *     are read back once at the end.  stats as for snesimage_guided_sweep.
+ * The workspace (the pixel list, 8 bytes x 64 per tile of the set: 4 MB at 8,192 tiles; the cost table; 256 call records) lives on
+ * the set, is made by the first of these calls and freed with the set; a failed allocation (SNES_ERR_HIP) leaves the set as it was.
+ * Refusals: SNES_ERR_ARG for a null set or pointer, a slot out of range (the backdrop slot of a plain set included) or k > 64;
+ * SNES_ERR_UNSUPPORTED for SNES_NES members and beyond the cap; whatever every set call answers for a member changed outside the
+ * set or destroyed.  A refusal leaves the set usable.  snesimage_guided_* on a lent member keeps answering SNES_ERR_STATE. */
+int32_t snesimage_shared_guided_costs(snesimage_shared *set, uint32_t palette, uint32_t index, uint64_t *costs /* 32768 */);
+int32_t snesimage_shared_guided_candidates(snesimage_shared *set, uint32_t palette, uint32_t index, uint32_t k, uint8_t *rgb5 /* k*3 */, uint64_t *costs /* k, optional */);
+int32_t snesimage_shared_guided_step_async(snesimage_shared *set, uint32_t palette, uint32_t index, uint32_t k); /* result: snesimage_shared_last_step */
+int32_t snesimage_shared_guided_step(snesimage_shared *set, uint32_t palette, uint32_t index, uint32_t k, double *error, uint8_t *best_rgb5);
+int32_t snesimage_shared_guided_sweep(snesimage_shared *set, uint32_t k, snesimage_call_result *log /* optional, one per slot */, snesimage_run_stats *stats /* optional */);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);

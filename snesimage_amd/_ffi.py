@@ -168,6 +168,11 @@ SIGNATURES = [
     ("snesimage_guided_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f64p, _u8p]),
     ("snesimage_guided_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("snesimage_guided_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
+    ("snesimage_shared_guided_costs", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u64p]),
+    ("snesimage_shared_guided_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, _u64p]),
+    ("snesimage_shared_guided_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_shared_guided_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("snesimage_shared_guided_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
     ("snesimage_get_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_as_rgba", C.c_int32, [C.c_void_p, _u8p]),

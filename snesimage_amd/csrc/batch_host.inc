@@ -274,7 +274,11 @@ namespace {
 // The launches of one optimizer call for every member of b, on the batch's stream: member i's candidate stream keyed
 // (seeds[i], step_id).  joint == nullptr: every member commits its own call (kb_commit); otherwise the members share one
 // palette (a set, shared_host.inc) and ks_commit decides once for all of them, its record going to *joint.
-int32_t batch_call(snesimage_batch *b, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, const uint64_t *seeds, uint64_t step_id, uint32_t n_random, snes::StepResult *joint) {
+// gen: a generator in kb_gen_candidates' place (a set's guided call, shared_guide_host.inc): it enqueues on the batch's stream
+// whatever writes the call's n candidates into every member's list; a call without one issues the launches it always did.
+struct BatchGen { int32_t (*enqueue)(void *self, hipStream_t st, uint32_t palette, uint32_t index, uint32_t n); void *self; };
+int32_t batch_call(snesimage_batch *b, uint32_t method, uint32_t palette, uint32_t index, uint32_t channel, const uint64_t *seeds, uint64_t step_id, uint32_t n_random, snes::StepResult *joint,
+                   const BatchGen *gen = nullptr) {
     snesimage_ctx *c0 = b->ctx[0];
     CHECK(check_slot(c0, palette, index));
     if (method > 2 || channel > 2) return fail(SNES_ERR_ARG, "bad method or channel");
@@ -303,7 +307,8 @@ int32_t batch_call(snesimage_batch *b, uint32_t method, uint32_t palette, uint32
     const snes::BatchArgs *A = b->d_args[r];
     HIPCHK(hipMemcpyAsync(b->d_args[r], ha, sizeof(snes::BatchArgs) * K, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(b->used[r], st));
-    hipLaunchKernelGGL(kb_gen_candidates, dim3((n + 63) / 64, 1, K), dim3(64), 0, st, A, (const int *)nullptr);
+    if (gen) CHECK(gen->enqueue(gen->self, st, palette, index, n));
+    else hipLaunchKernelGGL(kb_gen_candidates, dim3((n + 63) / 64, 1, K), dim3(64), 0, st, A, (const int *)nullptr);
     CHECK(enqueue_batched_scoring(st, A, K, n, c0, nullptr, nullptr, c0->dither)); // (one stream: with 128 images' working sets the second stream of the slot windows costs 12 %)
     if (joint) hipLaunchKernelGGL(ks_commit, dim3(1), dim3(256), 0, st, A, (int)K, joint);
     else hipLaunchKernelGGL(kb_commit, dim3(1, 1, K), dim3(256), 0, st, A, (const int *)nullptr);

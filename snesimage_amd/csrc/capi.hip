@@ -13,6 +13,7 @@
 #include "kernels_char.hpp"
 #include "kernels_char_set.hpp"
 #include "kernels_guide.hpp"
+#include "kernels_guide_set.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1750,3 +1751,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "level_host.inc"
 #include "shared_level_host.inc"
 #include "guide_host.inc"
+#include "shared_guide_host.inc"

@@ -39,6 +39,8 @@
 // every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
 // --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_sweep): on every
 // slot the --guided-shortlist K colours an integer proxy ranks best among all 32,768 are scored, and the error decides.
+// --set-guided G (with --share) does the same for a set (snesimage_shared_guided_sweep): the proxy runs over the tiles of all
+// frames, every frame scores the --set-guided-shortlist K colours, and the set's error decides.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
 #include "../../include/snesimage_hip.h"
@@ -136,6 +138,12 @@ void usage() {
             "                           itself; runs in front of --reassign-tiles, --tile-moves and --tile-dither; with --backdrop-fixed the\n"
             "                           backdrop slot is passed by; not with --share, --devices or --nes\n"
             "      --guided-shortlist <K>  colours scored per guided call, 1..64 [default: 16: a choice, not a measurement]; needs --guided\n"
+            "      --set-guided <G>     with --share: behind every G sweeps of the palette, one guided sweep of the set: the colours are ranked\n"
+            "                           over the tiles of all frames, every frame scores the --set-guided-shortlist best, and the set's error\n"
+            "                           decides; runs in front of --reassign-tiles, --tile-moves and --set-tile-dither; with\n"
+            "                           --set-backdrop-fixed the backdrop slot is passed by; not with --devices or --nes\n"
+            "      --set-guided-shortlist <K>  colours scored per guided call of the set, 1..64 [default: 16: a choice, not a measurement];\n"
+            "                           needs --set-guided\n"
             "      --max-tiles <N>      after the last optimizer call, merge tiles until at most N distinct characters are left (tiles equal\n"
             "                           under the tilemap's flips count once); each merge is the one with the lowest error among the\n"
             "                           --merge-shortlist cheapest by colour distance; not with --share or --devices\n"
@@ -310,6 +318,7 @@ int main(int argc, char **argv) {
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
     uint32_t guided_every = 0, guided_short = 16; bool guided_given = false, guided_short_given = false; std::string guided_arg, guided_short_arg;
+    uint32_t set_guided_every = 0, set_guided_short = 16; bool set_guided_given = false, set_guided_short_given = false; std::string set_guided_arg, set_guided_short_arg;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -345,6 +354,8 @@ int main(int argc, char **argv) {
         else if (a == "--resume") resume_file = need("--resume");
         else if (a == "--guided") { guided_given = true; guided_arg = need("--guided"); }
         else if (a == "--guided-shortlist") { guided_short_given = true; guided_short_arg = need("--guided-shortlist"); }
+        else if (a == "--set-guided") { set_guided_given = true; set_guided_arg = need("--set-guided"); }
+        else if (a == "--set-guided-shortlist") { set_guided_short_given = true; set_guided_short_arg = need("--set-guided-shortlist"); }
         else if (a == "--max-tiles") { max_tiles_given = true; max_tiles_arg = need("--max-tiles"); }
         else if (a == "--merge-shortlist") { merge_short_given = true; merge_short_arg = need("--merge-shortlist"); }
         else if (a == "--refit-tiles") { refit_given = true; refit_arg = need("--refit-tiles"); }
@@ -380,6 +391,21 @@ int main(int argc, char **argv) {
             const unsigned long k = strtoul(guided_short_arg.c_str(), &end, 10);
             if (guided_short_arg.empty() || guided_short_arg[0] == '-' || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--guided-shortlist <K>': expected 1..64\n", guided_short_arg.c_str()); return 2; }
             guided_short = (uint32_t)k;
+        }
+    }
+    if (set_guided_given || set_guided_short_given) { // guided sweeps of a set: said before any file or device is touched
+        if (!set_guided_given) { fprintf(stderr, "error: '--set-guided-shortlist <K>' needs '--set-guided <G>'\n"); return 2; }
+        if (shares.empty()) { fprintf(stderr, "error: '--set-guided <G>' needs '--share <SOURCE=TARGET>': it runs the guided sweeps of a set (one image: --guided)\n"); return 2; }
+        const char *bad = !devices.empty() ? "'--devices'" : (flags & SNES_NES) ? "'--nes'" : nullptr; // a set runs on one device; the NES call scores its whole table already
+        if (bad) { fprintf(stderr, "error: the argument '--set-guided <G>' cannot be used with %s\n", bad); return 2; }
+        char *end = nullptr;
+        const unsigned long g = strtoul(set_guided_arg.c_str(), &end, 10);
+        if (set_guided_arg.empty() || set_guided_arg[0] == '-' || *end || g < 1 || g > 1000000) { fprintf(stderr, "error: invalid value '%s' for '--set-guided <G>': expected a number of sweeps, 1 or more\n", set_guided_arg.c_str()); return 2; }
+        set_guided_every = (uint32_t)g;
+        if (set_guided_short_given) {
+            const unsigned long k = strtoul(set_guided_short_arg.c_str(), &end, 10);
+            if (set_guided_short_arg.empty() || set_guided_short_arg[0] == '-' || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--set-guided-shortlist <K>': expected 1..64\n", set_guided_short_arg.c_str()); return 2; }
+            set_guided_short = (uint32_t)k;
         }
     }
     if (max_tiles_given || merge_short_given || refit_given || !tilemap_file.empty()) { // said before any file or device is touched
@@ -776,8 +802,27 @@ int main(int argc, char **argv) {
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
         load_before(); // (the colours the next calls' reports compare with)
     };
+    auto set_guided_sweep = [&]() { // one guided call of the set on every slot, each decided by E; --set-backdrop-fixed passes the backdrop slot by
+        const std::string what = "Unable to run a guided sweep of the set: ";
+        snesimage_run_stats gs{};
+        double e0 = 0.0, e1 = 0.0;
+        if (snesimage_shared_error(set, &e0) != 0) die(what + snesimage_last_error());
+        if (bd_fixed) {
+            for (uint32_t p = 0; p < count; p++)
+                for (uint32_t ix = 0; ix < size; ix++) {
+                    snesimage_call_result r{};
+                    if (snesimage_shared_guided_step_async(set, p, ix, set_guided_short) != 0 || snesimage_shared_last_step(set, &r) != 0) die(what + snesimage_last_error());
+                    gs.calls += 1; gs.accepted += r.best_k >= 0 ? 1u : 0u;
+                }
+        } else if (snesimage_shared_guided_sweep(set, set_guided_short, nullptr, &gs) != 0) die(what + snesimage_last_error());
+        if (snesimage_shared_error(set, &e1) != 0) die(what + snesimage_last_error());
+        log_info("Guided sweep of the set: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
+        load_before(); // (the colours the next calls' reports compare with)
+    };
     auto end_of_sweep = [&]() {
         if (guided_every && step != sweep && step % guided_every == 0) guided_sweep(); // in front of everything that moves tiles: they see the palette it leaves
+        if (set_guided_every && step != sweep && step % set_guided_every == 0) set_guided_sweep(); // (the same place for a set)
         if (reassign_every && step != sweep && step % reassign_every == 0) { // a sweep over every slot has just ended (src/lib.rs:925-931)
             uint32_t moved = 0;
             if (set) { if (snesimage_shared_reassign_tiles(set, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error()); }
@@ -808,7 +853,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every || level_every || set_level_every || guided_every || bd_fixed) { // calls left in the current sweep
+            if (reassign_every || tile_every || level_every || set_level_every || guided_every || set_guided_every || bd_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;

@@ -7,7 +7,8 @@
 struct snesimage_shared_window; // slot windows of the set (shared_window_host.inc)
 struct snesimage_sharedchar;    // workspace of the set's character budget (shared_char_host.inc)
 struct snesimage_sharedlevel;   // workspace of the set's per-tile dither levels (shared_level_host.inc)
-namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); void shared_level_free(snesimage_sharedlevel *w); }
+struct snesimage_sharedguide;   // workspace of the set's guided calls (shared_guide_host.inc)
+namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); void shared_level_free(snesimage_sharedlevel *w); void shared_guide_free(snesimage_sharedguide *w); }
 
 struct snesimage_shared {
     snesimage_batch *b = nullptr;
@@ -18,6 +19,7 @@ struct snesimage_shared {
     std::vector<unsigned long long> epoch;    // each member's palette / tile-map generation when the set last touched it
     snesimage_sharedchar *chr = nullptr;      // the character budget of the set, made on first use
     snesimage_sharedlevel *lvl = nullptr;     // the tied level calls of the set, made on first use
+    snesimage_sharedguide *guide = nullptr;   // the guided calls of the set, made on first use
     bool reduced = false;                     // snesimage_shared_reduce_characters left merged maps: stored maps that are no optimize() of the palette
     // a backdrop set (snesimage_shared_create_backdrop; DESIGN §5c''): every member is a SNES_BACKDROP context and holds the set's B
     bool backdrop = false;
@@ -223,7 +225,13 @@ int32_t shared_kmeans_initialize_tiles(snesimage_shared *s) {
 // so the members overlap; ks_commit_tied follows on the set's stream behind the members' events.  With SNES_DITHER every
 // member then takes the winner's map from its lanes (k_take_best_map + do_optimize(may_skip), as commit() does for a single
 // context) on its own stream, and the set's stream waits for that.  No host synchronisation once the workspaces exist.
-int32_t shared_tied_call(snesimage_shared *s, uint32_t method, uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random) {
+// gen: the set's generator in gen_candidates' place (a guided call, shared_guide_host.inc).  It runs ONCE, on the set's stream,
+// and writes the list into every member's d_cand.  It reads the members' targets and tile_palettes (constant during set calls)
+// and the palette, which ks_commit / ks_commit_tied write on the set's stream: stream order covers that.  It overwrites the
+// lists the members' score_list of the previous call read on their own streams: the set's stream waited for those (ev_own)
+// before that call's commit — or, when the set's stream is idle, waits for the members' streams here.  Every member's stream
+// then waits for the generator (ev_tied) before prep_for_slot / score_list.
+int32_t shared_tied_call(snesimage_shared *s, uint32_t method, uint32_t channel, uint64_t seed, uint64_t step_id, uint32_t n_random, const BatchGen *gen = nullptr) {
     auto &M = members(s);
     snesimage_ctx *c0 = M[0];
     if (method > 2 || channel > 2) return fail(SNES_ERR_ARG, "bad method or channel");
@@ -233,14 +241,23 @@ int32_t shared_tied_call(snesimage_shared *s, uint32_t method, uint32_t channel,
     if (!s->ev_tied) HIPCHK(hipEventCreateWithFlags(&s->ev_tied, hipEventDisableTiming));
     for (auto *c : M)
         if (!c->tables_valid || !c->src_valid || !c->inc_valid) return fail(SNES_ERR_STATE, "a member context was modified outside the set");
+    if (gen) {
+        if (!s->b->busy) for (auto *c : M) { // work a member queued on its own stream since the last set call (as batch_call orders it)
+            if (!c->ev_own) HIPCHK(hipEventCreateWithFlags(&c->ev_own, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(c->ev_own, c->stream));
+            HIPCHK(hipStreamWaitEvent(st, c->ev_own, 0));
+        }
+        CHECK(gen->enqueue(gen->self, st, c0->sub_count, 0, n));
+        HIPCHK(hipEventRecord(s->ev_tied, st)); // behind the generator, and so behind the batched call before it
+    } else
     if (s->b->busy) HIPCHK(hipEventRecord(s->ev_tied, st)); // the batched call before this one may still be running
     std::vector<snes::TiedMember> tab(F);
     for (uint32_t i = 0; i < F; i++) {
         snesimage_ctx *c = M[i];
-        if (s->b->busy) HIPCHK(hipStreamWaitEvent(c->stream, s->ev_tied, 0));
-        CHECK(ensure_cand_capacity(c, n));
+        if (gen || s->b->busy) HIPCHK(hipStreamWaitEvent(c->stream, s->ev_tied, 0));
+        CHECK(ensure_cand_capacity(c, n)); // (a guided call has made room before its generator ran)
         SlotScope sc(c, c->sub_count, 0);
-        CHECK(gen_candidates(c, method, sc.sp, sc.si, channel, seed, step_id, n));
+        if (!gen) CHECK(gen_candidates(c, method, sc.sp, sc.si, channel, seed, step_id, n));
         CHECK(prep_for_slot(c, (int)sc.sp, (int)sc.si));
         CHECK(score_list(c, c->d_cand, n, c->d_errs, 1, 0, (int)sc.sp, (int)sc.si, nullptr));
         if (!c->ev_own) HIPCHK(hipEventCreateWithFlags(&c->ev_own, hipEventDisableTiming));
@@ -386,6 +403,7 @@ void snesimage_shared_destroy(snesimage_shared *s) {
     if (s->win) { shared_window_free(s->win); s->win = nullptr; } // (its slot contexts borrow the members' planes: before the members go)
     if (s->chr) { shared_char_free(s->chr); s->chr = nullptr; }
     if (s->lvl) { shared_level_free(s->lvl); s->lvl = nullptr; }
+    if (s->guide) { shared_guide_free(s->guide); s->guide = nullptr; }
     snesimage_batch_destroy(s->b); // (waits for its stream)
     if (s->d_joint) (void)hipFree(s->d_joint);
     if (s->d_sum) (void)hipFree(s->d_sum);

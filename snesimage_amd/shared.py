@@ -162,6 +162,43 @@ class SharedPalette:
         out = np.array([(r.error, r.sub, r.changed) for r in log[:F * n_tiles]], dtype=TILE_LOG_DTYPE).reshape(F, n_tiles)
         return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
+    # -- guided calls of the set (not in the reference; include/snesimage_hip.h, DESIGN 5f') ---------------------------
+    def guided_costs(self, palette, index):
+        """The proxy cost of every BGR555 colour for the slot over all members: 32,768 uint64, indexed u = r | g << 5 | b << 10 —
+        the sum of OptimizedImage.guided_costs over the members.  The state is left unchanged."""
+        out = np.zeros(32768, np.uint64)
+        self._chk(self._L.snesimage_shared_guided_costs(self._s, int(palette), int(index), _p(out, _ffi._u64p)))
+        return out
+
+    def guided_candidates(self, palette, index, k=0):
+        """The k (1..64, 0 = 16) colours lowest in (cost, u) but the slot's current colour, in that order; the state is
+        left unchanged.  Returns (rgb5[k, 3], costs[k])."""
+        n = int(k) if k else 16
+        rgb5, costs = np.zeros((max(n, 1), 3), np.uint8), np.zeros(max(n, 1), np.uint64)
+        self._chk(self._L.snesimage_shared_guided_candidates(self._s, int(palette), int(index), int(k), _p(rgb5, _ffi._u8p), _p(costs, _ffi._u64p)))
+        return rgb5[:n], costs[:n]
+
+    def guided_step(self, palette, index, k=0):
+        """One guided call on the set: every member scores the shortlist of k, the joint error decides as in `step`
+        -> (E after the call, the slot's colour); `last_step` reports the record."""
+        err = C.c_double(0)
+        best = np.zeros(3, np.uint8)
+        self._chk(self._L.snesimage_shared_guided_step(self._s, int(palette), int(index), int(k), C.byref(err), _p(best, _ffi._u8p)))
+        return err.value, best
+
+    def guided_step_async(self, palette, index, k=0):
+        self._chk(self._L.snesimage_shared_guided_step_async(self._s, int(palette), int(index), int(k)))
+
+    def guided_sweep(self, k=0):
+        """One guided call on every slot in the schedule's order (the backdrop slot of a backdrop set last), enqueued back to
+        back.  Returns (log, stats): log[j] = (E, best_k, rgb5, changed) after call j, as `run_slots` reports."""
+        n = self.sub_count * self.sub_size + (1 if self.has_backdrop else 0)
+        log = (_ffi.CallResult * n)()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_shared_guided_sweep(self._s, int(k), log, C.byref(stats)))
+        out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log]
+        return out, {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
     # -- per-tile ordered-dither levels of the set, tied or per frame (not in the reference; include/snesimage_hip.h) ----
     def set_ordered_dither_bank(self, bank, start_level=0):
         """The set's bank: `bank` is (L, n, n) int8, 1 <= L <= 8 tables of one side n = 2, 4, 8 or 16, given to every member
