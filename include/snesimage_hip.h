@@ -777,6 +777,31 @@ int32_t snesimage_shared_guided_candidates(snesimage_shared *set, uint32_t palet
 int32_t snesimage_shared_guided_step_async(snesimage_shared *set, uint32_t palette, uint32_t index, uint32_t k); /* result: snesimage_shared_last_step */
 int32_t snesimage_shared_guided_step(snesimage_shared *set, uint32_t palette, uint32_t index, uint32_t k, double *error, uint8_t *best_rgb5);
 int32_t snesimage_shared_guided_sweep(snesimage_shared *set, uint32_t k, snesimage_call_result *log /* optional, one per slot */, snesimage_run_stats *stats /* optional */);
+/* NOT a reference method: THE CIELAB PROXY OF GUIDED CALLS (DESIGN 5f'').  On a SNES_PERCEPTUAL context the pixels choose their
+ * entry by CIEDE2000, so the redmean table ranks colours by a population cost the remap does not reproduce.  This second proxy is
+ * the same k-means objective in the remap's own metric, made an exact integer by fixed point.  The slot, the population, the
+ * target image T, the tied slot, the set population and the shortlist rule are those above; only the distance changes:
+ *   DISTANCE d(c, x) = ciede2000(Lab(rgb8(c)), Lab(T(x))) in f32: entry first, target second, through the sRGB table and the Lab
+ *     pipeline of the remap (lib.rs:1090-1100: distance_cielab(entry, target)).
+ *   FIXED POINT q(d) = min((uint32_t)(d * 65536.0f), 0xFFFFFF).  The product by 2^16 is exact in f32, so the truncation is exact; q
+ *     is monotone, so q(min) = min(q).
+ *   FLOOR m(x) = the minimum of q(d(entry j, x)) over the entries j != i of the subpalette (the expanded one on a backdrop
+ *     context); 0xFFFFFFFF with S == 1.  A transparent pixel adds 0 to every sum.
+ *   COST cost(u) = sum over the population of min(m(x), q(d(c_u, x))) in a uint64_t, in Q16 units of dE00: at most
+ *     2^24 * 2^19 = 2^43 for a set of 8,192 tiles.  A set's table is the integer sum over all its members' tiles.
+ * snesimage_set_guided_proxy selects the table that snesimage_guided_costs / _candidates / _step(_async) / _sweep use:
+ * SNES_GUIDE_REDMEAN (the default) or SNES_GUIDE_CIELAB.  Legal on every context but SNES_NES (SNES_ERR_UNSUPPORTED), perceptual or
+ * not; SNES_ERR_ARG for another value; SNES_ERR_STATE between the phases of a split-phase step or window and on a context lent to a
+ * batch, a set or a group, as snesimage_set_ordered_dither refuses.  A refusal leaves the setting as it was.  The state of the
+ * context is not touched; the CIELAB pixel list (16 bytes a pixel: 1 MB at 256 x 256) is allocated by the first guided call under
+ * SNES_GUIDE_CIELAB.  A context that never selects SNES_GUIDE_CIELAB issues exactly the launches it issued before.
+ * snesimage_shared_set_guided_proxy does the same for snesimage_shared_guided_*: the set's setting is its own, the members' settings
+ * are neither read nor written (list: 8 MB at 8,192 tiles).  It refuses what every set call refuses, SNES_NES members and a bad value. */
+enum { SNES_GUIDE_REDMEAN = 0, SNES_GUIDE_CIELAB = 1 };
+int32_t snesimage_set_guided_proxy(snesimage_ctx *ctx, uint32_t proxy);
+int32_t snesimage_get_guided_proxy(snesimage_ctx *ctx, uint32_t *proxy);
+int32_t snesimage_shared_set_guided_proxy(snesimage_shared *set, uint32_t proxy);
+int32_t snesimage_shared_get_guided_proxy(snesimage_shared *set, uint32_t *proxy);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);

@@ -173,6 +173,10 @@ SIGNATURES = [
     ("snesimage_shared_guided_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f64p, _u8p]),
     ("snesimage_shared_guided_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("snesimage_shared_guided_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
+    ("snesimage_set_guided_proxy", C.c_int32, [C.c_void_p, C.c_uint32]),
+    ("snesimage_get_guided_proxy", C.c_int32, [C.c_void_p, _u32p]),
+    ("snesimage_shared_set_guided_proxy", C.c_int32, [C.c_void_p, C.c_uint32]),
+    ("snesimage_shared_get_guided_proxy", C.c_int32, [C.c_void_p, _u32p]),
     ("snesimage_get_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_set_palette_map", C.c_int32, [C.c_void_p, _u8p]),
     ("snesimage_as_rgba", C.c_int32, [C.c_void_p, _u8p]),

@@ -12,6 +12,7 @@ from . import _ffi
 
 DITHER, PERCEPTUAL, NES, BACKDROP = 1, 2, 4, 8
 METHOD_RANDOM, METHOD_CHANNEL, METHOD_NES = 0, 1, 2
+GUIDED_PROXIES = ("redmean", "cielab")  # SNES_GUIDE_REDMEAN, SNES_GUIDE_CIELAB
 TILE_LOG_DTYPE = np.dtype([("error", np.float64), ("sub", np.int32), ("changed", np.uint8)])  # one record of a tile sweep's log
 # one record of a character reduction's log (snesimage_merge_result)
 MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("cost", np.uint64), ("tile", np.uint16), ("donor", np.uint16), ("flip", np.uint8), ("rank", np.uint8),
@@ -536,6 +537,20 @@ class OptimizedImage:
         self._chk(self._L.snesimage_guided_sweep(self._c, int(k), log, C.byref(stats)))
         out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log]
         return out, {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    @property
+    def guided_proxy(self):
+        """The metric of the guided calls' cost table: "redmean" (the default) or "cielab" — the same objective measured in
+        CIEDE2000, the metric a perceptual context remaps by, in Q16 units (include/snesimage_hip.h)."""
+        v = C.c_uint32(0)
+        self._chk(self._L.snesimage_get_guided_proxy(self._c, C.byref(v)))
+        return GUIDED_PROXIES[v.value]
+
+    @guided_proxy.setter
+    def guided_proxy(self, name):
+        if name not in GUIDED_PROXIES:
+            raise ValueError("guided_proxy is 'redmean' or 'cielab', not %r" % (name,))
+        self._chk(self._L.snesimage_set_guided_proxy(self._c, GUIDED_PROXIES.index(name)))
 
     def target_rgba(self):
         """The image the nearest-colour choice is made against: the original plus the table's offsets, clamped; alpha kept."""

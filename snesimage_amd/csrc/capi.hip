@@ -14,6 +14,7 @@
 #include "kernels_char_set.hpp"
 #include "kernels_guide.hpp"
 #include "kernels_guide_set.hpp"
+#include "kernels_guide_lab.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -235,6 +236,7 @@ struct snesimage_ctx {
     struct snesimage_tilework *tile = nullptr; // workspace of the objective-scored tile moves (tile_host.inc), created on first use
     struct snesimage_charwork *chr = nullptr;  // workspace of the character budget (char_host.inc), created on first use
     struct snesimage_guidework *guide = nullptr; // workspace of the guided calls (guide_host.inc), created on first use
+    uint32_t guide_proxy = 0;                    // snesimage_set_guided_proxy: the metric of the guided calls' table (SNES_GUIDE_REDMEAN)
 
     // cache keys
     bool tables_valid = false, src_valid = false, inc_valid = false;

@@ -39,6 +39,7 @@
 // every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
 // --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_sweep): on every
 // slot the --guided-shortlist K colours an integer proxy ranks best among all 32,768 are scored, and the error decides.
+// --guided-proxy / --set-guided-proxy redmean|cielab choose the proxy's distance (snesimage_set_guided_proxy; DESIGN 5f'').
 // --set-guided G (with --share) does the same for a set (snesimage_shared_guided_sweep): the proxy runs over the tiles of all
 // frames, every frame scores the --set-guided-shortlist K colours, and the set's error decides.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
@@ -138,11 +139,15 @@ void usage() {
             "                           itself; runs in front of --reassign-tiles, --tile-moves and --tile-dither; with --backdrop-fixed the\n"
             "                           backdrop slot is passed by; not with --share, --devices or --nes\n"
             "      --guided-shortlist <K>  colours scored per guided call, 1..64 [default: 16: a choice, not a measurement]; needs --guided\n"
+            "      --guided-proxy <PROXY>  the distance that ranks the colours: redmean, or cielab (CIEDE2000, the distance the pixels choose\n"
+            "                           their entry by under --perceptual-palettes) [default: redmean]; needs --guided\n"
             "      --set-guided <G>     with --share: behind every G sweeps of the palette, one guided sweep of the set: the colours are ranked\n"
             "                           over the tiles of all frames, every frame scores the --set-guided-shortlist best, and the set's error\n"
             "                           decides; runs in front of --reassign-tiles, --tile-moves and --set-tile-dither; with\n"
             "                           --set-backdrop-fixed the backdrop slot is passed by; not with --devices or --nes\n"
             "      --set-guided-shortlist <K>  colours scored per guided call of the set, 1..64 [default: 16: a choice, not a measurement];\n"
+            "                           needs --set-guided\n"
+            "      --set-guided-proxy <PROXY>  the same choice for the guided sweeps of the set: redmean or cielab [default: redmean];\n"
             "                           needs --set-guided\n"
             "      --max-tiles <N>      after the last optimizer call, merge tiles until at most N distinct characters are left (tiles equal\n"
             "                           under the tilemap's flips count once); each merge is the one with the lowest error among the\n"
@@ -318,6 +323,7 @@ int main(int argc, char **argv) {
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
     uint32_t guided_every = 0, guided_short = 16; bool guided_given = false, guided_short_given = false; std::string guided_arg, guided_short_arg;
+    uint32_t guided_proxy = SNES_GUIDE_REDMEAN, set_guided_proxy = SNES_GUIDE_REDMEAN; bool guided_proxy_given = false, set_guided_proxy_given = false; std::string guided_proxy_arg, set_guided_proxy_arg;
     uint32_t set_guided_every = 0, set_guided_short = 16; bool set_guided_given = false, set_guided_short_given = false; std::string set_guided_arg, set_guided_short_arg;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -354,6 +360,8 @@ int main(int argc, char **argv) {
         else if (a == "--resume") resume_file = need("--resume");
         else if (a == "--guided") { guided_given = true; guided_arg = need("--guided"); }
         else if (a == "--guided-shortlist") { guided_short_given = true; guided_short_arg = need("--guided-shortlist"); }
+        else if (a == "--guided-proxy") { guided_proxy_given = true; guided_proxy_arg = need("--guided-proxy"); }
+        else if (a == "--set-guided-proxy") { set_guided_proxy_given = true; set_guided_proxy_arg = need("--set-guided-proxy"); }
         else if (a == "--set-guided") { set_guided_given = true; set_guided_arg = need("--set-guided"); }
         else if (a == "--set-guided-shortlist") { set_guided_short_given = true; set_guided_short_arg = need("--set-guided-shortlist"); }
         else if (a == "--max-tiles") { max_tiles_given = true; max_tiles_arg = need("--max-tiles"); }
@@ -379,8 +387,13 @@ int main(int argc, char **argv) {
         const char *bad = !devices.empty() ? "'--devices'" : (reassign_every ? "'--reassign-tiles'" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--tile-moves <K>' cannot be used with %s\n", bad); return 2; }
     }
-    if (guided_given || guided_short_given) { // guided sweeps: said before any file or device is touched
-        if (!guided_given) { fprintf(stderr, "error: '--guided-shortlist <K>' needs '--guided <G>'\n"); return 2; }
+    if (guided_given || guided_short_given || guided_proxy_given) { // guided sweeps: said before any file or device is touched
+        if (!guided_given && guided_short_given) { fprintf(stderr, "error: '--guided-shortlist <K>' needs '--guided <G>'\n"); return 2; }
+        if (!guided_given) { fprintf(stderr, "error: '--guided-proxy <PROXY>' needs '--guided <G>'\n"); return 2; }
+        if (guided_proxy_given) {
+            if (guided_proxy_arg != "redmean" && guided_proxy_arg != "cielab") { fprintf(stderr, "error: invalid value '%s' for '--guided-proxy <PROXY>': expected redmean or cielab\n", guided_proxy_arg.c_str()); return 2; }
+            guided_proxy = guided_proxy_arg == "cielab" ? SNES_GUIDE_CIELAB : SNES_GUIDE_REDMEAN;
+        }
         const char *bad = !shares.empty() ? "'--share'" : !devices.empty() ? "'--devices'" : (flags & SNES_NES) ? "'--nes'" : nullptr; // one context of its own; the NES call scores its whole table already
         if (bad) { fprintf(stderr, "error: the argument '--guided <G>' cannot be used with %s\n", bad); return 2; }
         char *end = nullptr;
@@ -393,8 +406,13 @@ int main(int argc, char **argv) {
             guided_short = (uint32_t)k;
         }
     }
-    if (set_guided_given || set_guided_short_given) { // guided sweeps of a set: said before any file or device is touched
-        if (!set_guided_given) { fprintf(stderr, "error: '--set-guided-shortlist <K>' needs '--set-guided <G>'\n"); return 2; }
+    if (set_guided_given || set_guided_short_given || set_guided_proxy_given) { // guided sweeps of a set: said before any file or device is touched
+        if (!set_guided_given && set_guided_short_given) { fprintf(stderr, "error: '--set-guided-shortlist <K>' needs '--set-guided <G>'\n"); return 2; }
+        if (!set_guided_given) { fprintf(stderr, "error: '--set-guided-proxy <PROXY>' needs '--set-guided <G>'\n"); return 2; }
+        if (set_guided_proxy_given) {
+            if (set_guided_proxy_arg != "redmean" && set_guided_proxy_arg != "cielab") { fprintf(stderr, "error: invalid value '%s' for '--set-guided-proxy <PROXY>': expected redmean or cielab\n", set_guided_proxy_arg.c_str()); return 2; }
+            set_guided_proxy = set_guided_proxy_arg == "cielab" ? SNES_GUIDE_CIELAB : SNES_GUIDE_REDMEAN;
+        }
         if (shares.empty()) { fprintf(stderr, "error: '--set-guided <G>' needs '--share <SOURCE=TARGET>': it runs the guided sweeps of a set (one image: --guided)\n"); return 2; }
         const char *bad = !devices.empty() ? "'--devices'" : (flags & SNES_NES) ? "'--nes'" : nullptr; // a set runs on one device; the NES call scores its whole table already
         if (bad) { fprintf(stderr, "error: the argument '--set-guided <G>' cannot be used with %s\n", bad); return 2; }
@@ -628,6 +646,7 @@ int main(int argc, char **argv) {
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
+    if (guided_proxy != SNES_GUIDE_REDMEAN && snesimage_set_guided_proxy(ctx, guided_proxy) != 0) die(snesimage_last_error()); // (before the context is lent to anything)
     if (ordered_n) log_info("Ordered dithering: " + std::to_string(ordered_n) + " x " + std::to_string(ordered_n) + " Bayer pattern, amplitude " + std::to_string(ordered_amp));
     if (!level_amps.empty() && !set_level_opts) {
         std::string m = "Per-tile dither levels: " + std::to_string(level_amps.size()) + " levels, amplitudes";
@@ -689,6 +708,7 @@ int main(int argc, char **argv) {
         }
         if ((set_bd ? snesimage_shared_create_backdrop(frames.data(), (uint32_t)frames.size(), set_b, &set) : snesimage_shared_create(frames.data(), (uint32_t)frames.size(), &set)) != 0) die(snesimage_last_error());
         log_info("Sharing one palette between " + std::to_string(frames.size()) + " images");
+        if (set_guided_proxy != SNES_GUIDE_REDMEAN && snesimage_shared_set_guided_proxy(set, set_guided_proxy) != 0) die(snesimage_last_error());
         if (set_bd) {
             uint8_t b[3];
             if (snesimage_shared_get_backdrop_rgb5(set, b) != 0) die(snesimage_last_error());
@@ -798,7 +818,7 @@ int main(int argc, char **argv) {
                 }
         } else if (snesimage_guided_sweep(ctx, guided_short, nullptr, &gs) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
         if (snesimage_error(ctx, &e1) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
-        log_info("Guided sweep: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        log_info("Guided sweep: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + (guided_proxy == SNES_GUIDE_CIELAB ? "cielab" : "redmean") + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
         load_before(); // (the colours the next calls' reports compare with)
     };
@@ -816,7 +836,7 @@ int main(int argc, char **argv) {
                 }
         } else if (snesimage_shared_guided_sweep(set, set_guided_short, nullptr, &gs) != 0) die(what + snesimage_last_error());
         if (snesimage_shared_error(set, &e1) != 0) die(what + snesimage_last_error());
-        log_info("Guided sweep of the set: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted; error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        log_info("Guided sweep of the set: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + (set_guided_proxy == SNES_GUIDE_CIELAB ? "cielab" : "redmean") + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
         load_before(); // (the colours the next calls' reports compare with)
     };

@@ -4,9 +4,12 @@
 // The generator (gather, cost, select) writes the shortlist where k_gen_candidates writes a call's random candidates; from there
 // a guided call is snesimage_step_async word for word: prep_for_slot, score_list, commit.  It reads the palette and tile_palettes
 // on the device, so the calls of a sweep are enqueued back to back.  Included by capi.hip behind level_host.inc.
+// snesimage_set_guided_proxy selects the table's metric: the redmean key (kernels_guide.hpp) or CIEDE2000 in Q16
+// (kernels_guide_lab.hpp; DESIGN 5f''); k_guide_select and everything behind it take either table as it is.
 
 struct snesimage_guidework {
     GuidePixel *list = nullptr;          // the population: (w/8)*(h/8)*64 pixels at most, 512 KB at 256 x 256
+    GuideLabPixel *lab = nullptr;        // the same population under SNES_GUIDE_CIELAB, 16 bytes a pixel: made when that proxy is first used
     unsigned long long *tab = nullptr;   // cost[32768], the list's tile count (8 bytes), the shortlist's costs [64]
     StepResult *log = nullptr;           // a sweep's records
     unsigned long long *costs() const { return tab; }
@@ -16,15 +19,23 @@ struct snesimage_guidework {
 
 namespace {
 
-void guide_free(snesimage_ctx *c) { if (c->guide) { dfree(c->guide->list); dfree(c->guide->tab); dfree(c->guide->log); delete c->guide; c->guide = nullptr; } }
+void guide_free(snesimage_ctx *c) { if (c->guide) { dfree(c->guide->list); dfree(c->guide->lab); dfree(c->guide->tab); dfree(c->guide->log); delete c->guide; c->guide = nullptr; } }
 
 int32_t guide_alloc(snesimage_ctx *c) { // all or nothing: a failed allocation leaves the context without a workspace, as it was
-    if (c->guide) return SNES_OK;
-    snesimage_guidework w;
     const size_t ntile = (size_t)(c->W / 8) * (c->H / 8);
+    if (c->guide) {
+        if (c->guide_proxy == SNES_GUIDE_CIELAB && !c->guide->lab && dmalloc(&c->guide->lab, sizeof(GuideLabPixel) * 64 * ntile) != hipSuccess) {
+            c->guide->lab = nullptr;
+            return fail(SNES_ERR_HIP, "out of device memory for the guided calls' workspace");
+        }
+        return SNES_OK;
+    }
+    snesimage_guidework w;
+    if (c->guide_proxy == SNES_GUIDE_CIELAB && dmalloc(&w.lab, sizeof(GuideLabPixel) * 64 * ntile) != hipSuccess)
+        return fail(SNES_ERR_HIP, "out of device memory for the guided calls' workspace");
     if (dmalloc(&w.list, sizeof(GuidePixel) * 64 * ntile) != hipSuccess || dmalloc(&w.tab, sizeof(unsigned long long) * (kGuideColors + 1 + kGuideShort)) != hipSuccess ||
         dmalloc(&w.log, sizeof(StepResult) * 256) != hipSuccess) {
-        dfree(w.list); dfree(w.tab); dfree(w.log);
+        dfree(w.list); dfree(w.lab); dfree(w.tab); dfree(w.log);
         return fail(SNES_ERR_HIP, "out of device memory for the guided calls' workspace");
     }
     c->guide = new snesimage_guidework(w);
@@ -45,6 +56,14 @@ int32_t guide_costs(snesimage_ctx *c, uint32_t sp, uint32_t si) {
     snesimage_guidework &w = *c->guide;
     const uint32_t ntile = (c->W / 8) * (c->H / 8);
     HIPCHK(hipMemsetAsync(w.tab, 0, sizeof(unsigned long long) * (kGuideColors + 1), c->stream)); // the table and the count
+    if (c->guide_proxy == SNES_GUIDE_CIELAB) {
+        hipLaunchKernelGGL(k_guide_gather_lab, dim3(ntile), dim3(64), 0, c->stream, (const uint8_t *)c->d_target, (const uint8_t *)c->d_tile_pal, (const uint8_t *)c->d_colors, (const float *)c->d_lab_eotf,
+                           (int)c->W, (int)c->sub_size, c->tied_call ? -1 : (int)sp, (int)si, w.lab, w.count());
+        hipLaunchKernelGGL(k_guide_cost_lab, dim3(kGuideColors / 256, (ntile * 64 + kGuideSlice - 1) / kGuideSlice), dim3(256), 0, c->stream, (const GuideLabPixel *)w.lab, (const unsigned int *)w.count(),
+                           (const float *)c->d_lab_eotf, w.costs());
+        HIPCHK(hipGetLastError());
+        return SNES_OK;
+    }
     hipLaunchKernelGGL(k_guide_gather, dim3(ntile), dim3(64), 0, c->stream, (const uint8_t *)c->d_target, (const uint8_t *)c->d_tile_pal, (const uint8_t *)c->d_colors, (int)c->W, (int)c->sub_size,
                        c->tied_call ? -1 : (int)sp, (int)si, w.list, w.count());
     hipLaunchKernelGGL(k_guide_cost, dim3(kGuideColors / 256, (ntile * 64 + kGuideSlice - 1) / kGuideSlice), dim3(256), 0, c->stream, (const GuidePixel *)w.list, (const unsigned int *)w.count(), w.costs());
@@ -74,6 +93,22 @@ int32_t guide_step_async(snesimage_ctx *c, uint32_t palette, uint32_t index, uin
 } // namespace
 
 extern "C" {
+
+int32_t snesimage_set_guided_proxy(snesimage_ctx *c, uint32_t proxy) {
+    if (!c) return fail(SNES_ERR_ARG, "null context");
+    if (proxy != SNES_GUIDE_REDMEAN && proxy != SNES_GUIDE_CIELAB) return fail(SNES_ERR_ARG, "a guided proxy is SNES_GUIDE_REDMEAN (0) or SNES_GUIDE_CIELAB (1)");
+    if (c->nes) return fail(SNES_ERR_UNSUPPORTED, "the context was created with SNES_NES: it makes no guided calls");
+    if (c->pend || c->win_pend) return fail(SNES_ERR_STATE, "a split-phase step is pending: commit it first");
+    if (c->owner || c->group) return fail(SNES_ERR_STATE, "the context is lent to a batch, a set or a group: guided calls run on a context of its own");
+    c->guide_proxy = proxy;
+    return SNES_OK;
+}
+
+int32_t snesimage_get_guided_proxy(snesimage_ctx *c, uint32_t *proxy) {
+    if (!c || !proxy) return fail(SNES_ERR_ARG, "null pointer");
+    *proxy = c->guide_proxy;
+    return SNES_OK;
+}
 
 int32_t snesimage_guided_costs(snesimage_ctx *c, uint32_t palette, uint32_t index, uint64_t *costs) {
     CHECK(guide_check(c, palette, index, 0));

@@ -10,6 +10,7 @@
 
 struct snesimage_sharedguide {
     GuidePixel *list = nullptr;          // the population: 64 pixels per global tile, 4 MB at kSetTiles
+    GuideLabPixel *lab = nullptr;        // the same under SNES_GUIDE_CIELAB, 16 bytes a pixel (8 MB at kSetTiles): made when that proxy is first used
     unsigned long long *tab = nullptr;   // cost[32768], the list's tile count (8 bytes), the shortlist's costs [64]
     StepResult *log = nullptr;           // a sweep's records (256: a palette holds at most 253 entries and B)
     GuideMember *d_mem = nullptr;        // the member table, and what it holds
@@ -21,7 +22,7 @@ struct snesimage_sharedguide {
 
 namespace {
 
-void shared_guide_free(snesimage_sharedguide *w) { if (w) { dfree(w->list); dfree(w->tab); dfree(w->log); dfree(w->d_mem); delete w; } }
+void shared_guide_free(snesimage_sharedguide *w) { if (w) { dfree(w->list); dfree(w->lab); dfree(w->tab); dfree(w->log); dfree(w->d_mem); delete w; } }
 
 uint32_t sg_ntile(snesimage_shared *s) { const snesimage_ctx *c0 = members(s)[0]; return (c0->W / 8) * (c0->H / 8); }
 
@@ -37,12 +38,20 @@ int32_t sg_check(snesimage_shared *s, uint32_t palette, uint32_t index, uint32_t
 }
 
 int32_t sg_alloc(snesimage_shared *s) { // all or nothing: a failed allocation leaves the set without a workspace, as it was
-    if (s->guide) return SNES_OK;
-    snesimage_sharedguide w;
     const size_t F = members(s).size(), G = F * sg_ntile(s);
+    if (s->guide) {
+        if (s->guide_proxy == SNES_GUIDE_CIELAB && !s->guide->lab && dmalloc(&s->guide->lab, sizeof(GuideLabPixel) * 64 * G) != hipSuccess) {
+            s->guide->lab = nullptr;
+            return fail(SNES_ERR_HIP, "out of device memory for the workspace of the set's guided calls");
+        }
+        return SNES_OK;
+    }
+    snesimage_sharedguide w;
+    if (s->guide_proxy == SNES_GUIDE_CIELAB && dmalloc(&w.lab, sizeof(GuideLabPixel) * 64 * G) != hipSuccess)
+        return fail(SNES_ERR_HIP, "out of device memory for the workspace of the set's guided calls");
     if (dmalloc(&w.list, sizeof(GuidePixel) * 64 * G) != hipSuccess || dmalloc(&w.tab, sizeof(unsigned long long) * (kGuideColors + 1 + kGuideShort)) != hipSuccess ||
         dmalloc(&w.log, sizeof(StepResult) * 256) != hipSuccess || dmalloc(&w.d_mem, sizeof(GuideMember) * F) != hipSuccess) {
-        dfree(w.list); dfree(w.tab); dfree(w.log); dfree(w.d_mem);
+        dfree(w.list); dfree(w.lab); dfree(w.tab); dfree(w.log); dfree(w.d_mem);
         return fail(SNES_ERR_HIP, "out of device memory for the workspace of the set's guided calls");
     }
     s->guide = new snesimage_sharedguide(w);
@@ -84,6 +93,14 @@ int32_t sg_costs(snesimage_shared *s, hipStream_t st, uint32_t palette, uint32_t
     const uint32_t ntile = sg_ntile(s), G = (uint32_t)members(s).size() * ntile;
     const SgSlot q = sg_slot(s, palette, index);
     HIPCHK(hipMemsetAsync(w.tab, 0, sizeof(unsigned long long) * (kGuideColors + 1), st)); // the table and the count
+    if (s->guide_proxy == SNES_GUIDE_CIELAB) { // (the members' sRGB tables are one table: the first member's serves all)
+        hipLaunchKernelGGL(ks_guide_gather_lab, dim3(G), dim3(64), 0, st, (const GuideMember *)w.d_mem, (const uint8_t *)c0->d_colors, (const float *)c0->d_lab_eotf, (int)ntile, (int)c0->W, (int)c0->sub_size,
+                           q.sp, q.si, w.lab, w.count());
+        hipLaunchKernelGGL(k_guide_cost_lab, dim3(kGuideColors / 256, (G * 64 + kGuideSlice - 1) / kGuideSlice), dim3(256), 0, st, (const GuideLabPixel *)w.lab, (const unsigned int *)w.count(),
+                           (const float *)c0->d_lab_eotf, w.costs());
+        HIPCHK(hipGetLastError());
+        return SNES_OK;
+    }
     hipLaunchKernelGGL(ks_guide_gather, dim3(G), dim3(64), 0, st, (const GuideMember *)w.d_mem, (const uint8_t *)c0->d_colors, (int)ntile, (int)c0->W, (int)c0->sub_size, q.sp, q.si, w.list, w.count());
     // the host does not know the count: the grid covers the largest list, G * 64 pixels (at most 512 slices at kSetTiles)
     hipLaunchKernelGGL(k_guide_cost, dim3(kGuideColors / 256, (G * 64 + kGuideSlice - 1) / kGuideSlice), dim3(256), 0, st, (const GuidePixel *)w.list, (const unsigned int *)w.count(), w.costs());
@@ -129,6 +146,20 @@ int32_t sg_step_async(snesimage_shared *s, uint32_t palette, uint32_t index, uin
 } // namespace
 
 extern "C" {
+
+int32_t snesimage_shared_set_guided_proxy(snesimage_shared *s, uint32_t proxy) {
+    CHECK(shared_enter(s, true, true)); // (nothing on the device is touched)
+    if (proxy != SNES_GUIDE_REDMEAN && proxy != SNES_GUIDE_CIELAB) return fail(SNES_ERR_ARG, "a guided proxy is SNES_GUIDE_REDMEAN (0) or SNES_GUIDE_CIELAB (1)");
+    if (members(s)[0]->nes) return fail(SNES_ERR_UNSUPPORTED, "the members were created with SNES_NES: the set makes no guided calls");
+    s->guide_proxy = proxy;
+    return SNES_OK;
+}
+
+int32_t snesimage_shared_get_guided_proxy(snesimage_shared *s, uint32_t *proxy) {
+    if (!s || !proxy) return fail(SNES_ERR_ARG, "null pointer");
+    *proxy = s->guide_proxy;
+    return SNES_OK;
+}
 
 int32_t snesimage_shared_guided_costs(snesimage_shared *s, uint32_t palette, uint32_t index, uint64_t *costs) {
     CHECK(shared_enter(s, true, true)); // (the generator reads targets, tile_palettes and the palette: the stored maps are not read)

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .api import METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
+from .api import GUIDED_PROXIES, METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
 
 
 SHARED_MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("member_error", np.float64), ("cost", np.uint64), ("member", np.uint16), ("tile", np.uint16),
@@ -198,6 +198,20 @@ class SharedPalette:
         self._chk(self._L.snesimage_shared_guided_sweep(self._s, int(k), log, C.byref(stats)))
         out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log]
         return out, {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    @property
+    def guided_proxy(self):
+        """The metric of the set's guided cost table: "redmean" (the default) or "cielab".  The set's own setting: the
+        members' `guided_proxy` is neither read nor written."""
+        v = C.c_uint32(0)
+        self._chk(self._L.snesimage_shared_get_guided_proxy(self._s, C.byref(v)))
+        return GUIDED_PROXIES[v.value]
+
+    @guided_proxy.setter
+    def guided_proxy(self, name):
+        if name not in GUIDED_PROXIES:
+            raise ValueError("guided_proxy is 'redmean' or 'cielab', not %r" % (name,))
+        self._chk(self._L.snesimage_shared_set_guided_proxy(self._s, GUIDED_PROXIES.index(name)))
 
     # -- per-tile ordered-dither levels of the set, tied or per frame (not in the reference; include/snesimage_hip.h) ----
     def set_ordered_dither_bank(self, bank, start_level=0):
