@@ -13,7 +13,6 @@
 #include "kernels_char.hpp"
 #include "kernels_char_set.hpp"
 #include "kernels_guide.hpp"
-#include "kernels_guide_set.hpp"
 #include "kernels_guide_lab.hpp"
 
 #include <hip/hip_runtime.h>
@@ -235,7 +234,7 @@ struct snesimage_ctx {
     bool pack_borrowed = false;              // a slot context of a --dither window: pack and subpalette planes are the parent's
     struct snesimage_tilework *tile = nullptr; // workspace of the objective-scored tile moves (tile_host.inc), created on first use
     struct snesimage_charwork *chr = nullptr;  // workspace of the character budget (char_host.inc), created on first use
-    struct snesimage_guidework *guide = nullptr; // workspace of the guided calls (guide_host.inc), created on first use
+    struct snesimage_guidework *guide = nullptr; // workspace and generator of the guided calls (guide_host.inc), created on first use
     uint32_t guide_proxy = 0;                    // snesimage_set_guided_proxy: the metric of the guided calls' table (SNES_GUIDE_REDMEAN)
 
     // cache keys
@@ -1267,14 +1266,14 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
 
 void batch_forget(struct snesimage_batch *b, snesimage_ctx *c);
 void group_forget(struct snesimage_group *g, snesimage_ctx *c);
-namespace { void window_free(struct snesimage_window *w); void tile_free(snesimage_ctx *c); void char_free(snesimage_ctx *c); void level_free(snesimage_ctx *c); void guide_free(snesimage_ctx *c); }
+namespace { void window_free(struct snesimage_window *w); void tile_free(snesimage_ctx *c); void char_free(snesimage_ctx *c); void level_free(snesimage_ctx *c); void guide_free(struct snesimage_guidework *&w); }
 void snesimage_destroy(snesimage_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->tile) { if (c->stream) (void)hipStreamSynchronize(c->stream); tile_free(c); }
     if (c->chr) { if (c->stream) (void)hipStreamSynchronize(c->stream); char_free(c); }
     if (c->lvl) { if (c->stream) (void)hipStreamSynchronize(c->stream); level_free(c); }
-    if (c->guide) { if (c->stream) (void)hipStreamSynchronize(c->stream); guide_free(c); }
+    if (c->guide) { if (c->stream) (void)hipStreamSynchronize(c->stream); guide_free(c->guide); }
     if (c->win) { if (c->stream) (void)hipStreamSynchronize(c->stream); window_free(c->win); c->win = nullptr; } // its slot contexts borrow this context's planes
     if (c->owner) batch_forget(c->owner, c); // waits for the batch's stream and retires the batch
     if (c->group) group_forget(c->group, c); // retires the group: its other members are their own again

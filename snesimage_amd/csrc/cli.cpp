@@ -305,6 +305,36 @@ void write_json(snesimage_ctx *ctx, const std::string &target) { // src/lib.rs:1
     fclose(f);
 }
 
+// The flags of guided sweeps, a context's (--guided*) or a set's (--set-guided*): one sweep behind every G, the shortlist, the proxy.
+struct GuidedFlags {
+    uint32_t every = 0, shortlist = 16, proxy = SNES_GUIDE_REDMEAN;
+    bool given = false, short_given = false, proxy_given = false;
+    std::string arg, short_arg, proxy_arg;
+    bool any() const { return given || short_given || proxy_given; }
+    const char *proxy_name() const { return proxy == SNES_GUIDE_CIELAB ? "cielab" : "redmean"; }
+};
+// Checks and parses them: n is "--guided" or "--set-guided", refusal what else rules the sweeps out (its place is behind the
+// proxy's name and before the numbers), or empty.  False: the error has been said.
+bool parse_guided(const char *n, GuidedFlags &f, const std::string &refusal) {
+    if (!f.given && f.short_given) { fprintf(stderr, "error: '%s-shortlist <K>' needs '%s <G>'\n", n, n); return false; }
+    if (!f.given) { fprintf(stderr, "error: '%s-proxy <PROXY>' needs '%s <G>'\n", n, n); return false; }
+    if (f.proxy_given) {
+        if (f.proxy_arg != "redmean" && f.proxy_arg != "cielab") { fprintf(stderr, "error: invalid value '%s' for '%s-proxy <PROXY>': expected redmean or cielab\n", f.proxy_arg.c_str(), n); return false; }
+        f.proxy = f.proxy_arg == "cielab" ? SNES_GUIDE_CIELAB : SNES_GUIDE_REDMEAN;
+    }
+    if (!refusal.empty()) { fprintf(stderr, "error: %s\n", refusal.c_str()); return false; }
+    char *end = nullptr;
+    const unsigned long g = strtoul(f.arg.c_str(), &end, 10);
+    if (f.arg.empty() || f.arg[0] == '-' || *end || g < 1 || g > 1000000) { fprintf(stderr, "error: invalid value '%s' for '%s <G>': expected a number of sweeps, 1 or more\n", f.arg.c_str(), n); return false; }
+    f.every = (uint32_t)g;
+    if (f.short_given) {
+        const unsigned long k = strtoul(f.short_arg.c_str(), &end, 10);
+        if (f.short_arg.empty() || f.short_arg[0] == '-' || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '%s-shortlist <K>': expected 1..64\n", f.short_arg.c_str(), n); return false; }
+        f.shortlist = (uint32_t)k;
+    }
+    return true;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -322,9 +352,7 @@ int main(int argc, char **argv) {
     bool set_backdrop = false, set_backdrop_fixed = false; std::string set_backdrop_arg; // the backdrop colour of a --share set
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
-    uint32_t guided_every = 0, guided_short = 16; bool guided_given = false, guided_short_given = false; std::string guided_arg, guided_short_arg;
-    uint32_t guided_proxy = SNES_GUIDE_REDMEAN, set_guided_proxy = SNES_GUIDE_REDMEAN; bool guided_proxy_given = false, set_guided_proxy_given = false; std::string guided_proxy_arg, set_guided_proxy_arg;
-    uint32_t set_guided_every = 0, set_guided_short = 16; bool set_guided_given = false, set_guided_short_given = false; std::string set_guided_arg, set_guided_short_arg;
+    GuidedFlags gd, sgd; // --guided*, --set-guided*
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -358,12 +386,12 @@ int main(int argc, char **argv) {
         else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
         else if (a == "--tile-moves") tile_every = (uint32_t)strtoul(need("--tile-moves"), nullptr, 10);
         else if (a == "--resume") resume_file = need("--resume");
-        else if (a == "--guided") { guided_given = true; guided_arg = need("--guided"); }
-        else if (a == "--guided-shortlist") { guided_short_given = true; guided_short_arg = need("--guided-shortlist"); }
-        else if (a == "--guided-proxy") { guided_proxy_given = true; guided_proxy_arg = need("--guided-proxy"); }
-        else if (a == "--set-guided-proxy") { set_guided_proxy_given = true; set_guided_proxy_arg = need("--set-guided-proxy"); }
-        else if (a == "--set-guided") { set_guided_given = true; set_guided_arg = need("--set-guided"); }
-        else if (a == "--set-guided-shortlist") { set_guided_short_given = true; set_guided_short_arg = need("--set-guided-shortlist"); }
+        else if (a == "--guided") { gd.given = true; gd.arg = need("--guided"); }
+        else if (a == "--guided-shortlist") { gd.short_given = true; gd.short_arg = need("--guided-shortlist"); }
+        else if (a == "--guided-proxy") { gd.proxy_given = true; gd.proxy_arg = need("--guided-proxy"); }
+        else if (a == "--set-guided-proxy") { sgd.proxy_given = true; sgd.proxy_arg = need("--set-guided-proxy"); }
+        else if (a == "--set-guided") { sgd.given = true; sgd.arg = need("--set-guided"); }
+        else if (a == "--set-guided-shortlist") { sgd.short_given = true; sgd.short_arg = need("--set-guided-shortlist"); }
         else if (a == "--max-tiles") { max_tiles_given = true; max_tiles_arg = need("--max-tiles"); }
         else if (a == "--merge-shortlist") { merge_short_given = true; merge_short_arg = need("--merge-shortlist"); }
         else if (a == "--refit-tiles") { refit_given = true; refit_arg = need("--refit-tiles"); }
@@ -387,44 +415,14 @@ int main(int argc, char **argv) {
         const char *bad = !devices.empty() ? "'--devices'" : (reassign_every ? "'--reassign-tiles'" : nullptr);
         if (bad) { fprintf(stderr, "error: the argument '--tile-moves <K>' cannot be used with %s\n", bad); return 2; }
     }
-    if (guided_given || guided_short_given || guided_proxy_given) { // guided sweeps: said before any file or device is touched
-        if (!guided_given && guided_short_given) { fprintf(stderr, "error: '--guided-shortlist <K>' needs '--guided <G>'\n"); return 2; }
-        if (!guided_given) { fprintf(stderr, "error: '--guided-proxy <PROXY>' needs '--guided <G>'\n"); return 2; }
-        if (guided_proxy_given) {
-            if (guided_proxy_arg != "redmean" && guided_proxy_arg != "cielab") { fprintf(stderr, "error: invalid value '%s' for '--guided-proxy <PROXY>': expected redmean or cielab\n", guided_proxy_arg.c_str()); return 2; }
-            guided_proxy = guided_proxy_arg == "cielab" ? SNES_GUIDE_CIELAB : SNES_GUIDE_REDMEAN;
-        }
+    if (gd.any()) { // guided sweeps: said before any file or device is touched
         const char *bad = !shares.empty() ? "'--share'" : !devices.empty() ? "'--devices'" : (flags & SNES_NES) ? "'--nes'" : nullptr; // one context of its own; the NES call scores its whole table already
-        if (bad) { fprintf(stderr, "error: the argument '--guided <G>' cannot be used with %s\n", bad); return 2; }
-        char *end = nullptr;
-        const unsigned long g = strtoul(guided_arg.c_str(), &end, 10);
-        if (guided_arg.empty() || guided_arg[0] == '-' || *end || g < 1 || g > 1000000) { fprintf(stderr, "error: invalid value '%s' for '--guided <G>': expected a number of sweeps, 1 or more\n", guided_arg.c_str()); return 2; }
-        guided_every = (uint32_t)g;
-        if (guided_short_given) {
-            const unsigned long k = strtoul(guided_short_arg.c_str(), &end, 10);
-            if (guided_short_arg.empty() || guided_short_arg[0] == '-' || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--guided-shortlist <K>': expected 1..64\n", guided_short_arg.c_str()); return 2; }
-            guided_short = (uint32_t)k;
-        }
+        if (!parse_guided("--guided", gd, bad ? std::string("the argument '--guided <G>' cannot be used with ") + bad : "")) return 2;
     }
-    if (set_guided_given || set_guided_short_given || set_guided_proxy_given) { // guided sweeps of a set: said before any file or device is touched
-        if (!set_guided_given && set_guided_short_given) { fprintf(stderr, "error: '--set-guided-shortlist <K>' needs '--set-guided <G>'\n"); return 2; }
-        if (!set_guided_given) { fprintf(stderr, "error: '--set-guided-proxy <PROXY>' needs '--set-guided <G>'\n"); return 2; }
-        if (set_guided_proxy_given) {
-            if (set_guided_proxy_arg != "redmean" && set_guided_proxy_arg != "cielab") { fprintf(stderr, "error: invalid value '%s' for '--set-guided-proxy <PROXY>': expected redmean or cielab\n", set_guided_proxy_arg.c_str()); return 2; }
-            set_guided_proxy = set_guided_proxy_arg == "cielab" ? SNES_GUIDE_CIELAB : SNES_GUIDE_REDMEAN;
-        }
-        if (shares.empty()) { fprintf(stderr, "error: '--set-guided <G>' needs '--share <SOURCE=TARGET>': it runs the guided sweeps of a set (one image: --guided)\n"); return 2; }
+    if (sgd.any()) { // guided sweeps of a set: said before any file or device is touched
         const char *bad = !devices.empty() ? "'--devices'" : (flags & SNES_NES) ? "'--nes'" : nullptr; // a set runs on one device; the NES call scores its whole table already
-        if (bad) { fprintf(stderr, "error: the argument '--set-guided <G>' cannot be used with %s\n", bad); return 2; }
-        char *end = nullptr;
-        const unsigned long g = strtoul(set_guided_arg.c_str(), &end, 10);
-        if (set_guided_arg.empty() || set_guided_arg[0] == '-' || *end || g < 1 || g > 1000000) { fprintf(stderr, "error: invalid value '%s' for '--set-guided <G>': expected a number of sweeps, 1 or more\n", set_guided_arg.c_str()); return 2; }
-        set_guided_every = (uint32_t)g;
-        if (set_guided_short_given) {
-            const unsigned long k = strtoul(set_guided_short_arg.c_str(), &end, 10);
-            if (set_guided_short_arg.empty() || set_guided_short_arg[0] == '-' || *end || k < 1 || k > 64) { fprintf(stderr, "error: invalid value '%s' for '--set-guided-shortlist <K>': expected 1..64\n", set_guided_short_arg.c_str()); return 2; }
-            set_guided_short = (uint32_t)k;
-        }
+        if (!parse_guided("--set-guided", sgd, shares.empty() ? "'--set-guided <G>' needs '--share <SOURCE=TARGET>': it runs the guided sweeps of a set (one image: --guided)"
+                                               : bad ? std::string("the argument '--set-guided <G>' cannot be used with ") + bad : "")) return 2;
     }
     if (max_tiles_given || merge_short_given || refit_given || !tilemap_file.empty()) { // said before any file or device is touched
         char *end = nullptr;
@@ -646,7 +644,7 @@ int main(int argc, char **argv) {
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
-    if (guided_proxy != SNES_GUIDE_REDMEAN && snesimage_set_guided_proxy(ctx, guided_proxy) != 0) die(snesimage_last_error()); // (before the context is lent to anything)
+    if (gd.proxy != SNES_GUIDE_REDMEAN && snesimage_set_guided_proxy(ctx, gd.proxy) != 0) die(snesimage_last_error()); // (before the context is lent to anything)
     if (ordered_n) log_info("Ordered dithering: " + std::to_string(ordered_n) + " x " + std::to_string(ordered_n) + " Bayer pattern, amplitude " + std::to_string(ordered_amp));
     if (!level_amps.empty() && !set_level_opts) {
         std::string m = "Per-tile dither levels: " + std::to_string(level_amps.size()) + " levels, amplitudes";
@@ -708,7 +706,7 @@ int main(int argc, char **argv) {
         }
         if ((set_bd ? snesimage_shared_create_backdrop(frames.data(), (uint32_t)frames.size(), set_b, &set) : snesimage_shared_create(frames.data(), (uint32_t)frames.size(), &set)) != 0) die(snesimage_last_error());
         log_info("Sharing one palette between " + std::to_string(frames.size()) + " images");
-        if (set_guided_proxy != SNES_GUIDE_REDMEAN && snesimage_shared_set_guided_proxy(set, set_guided_proxy) != 0) die(snesimage_last_error());
+        if (sgd.proxy != SNES_GUIDE_REDMEAN && snesimage_shared_set_guided_proxy(set, sgd.proxy) != 0) die(snesimage_last_error());
         if (set_bd) {
             uint8_t b[3];
             if (snesimage_shared_get_backdrop_rgb5(set, b) != 0) die(snesimage_last_error());
@@ -813,12 +811,12 @@ int main(int argc, char **argv) {
             for (uint32_t p = 0; p < count; p++)
                 for (uint32_t ix = 0; ix < size; ix++) {
                     int32_t k = -1;
-                    if (snesimage_guided_step_async(ctx, p, ix, guided_short) != 0 || snesimage_last_step(ctx, nullptr, nullptr, &k) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+                    if (snesimage_guided_step_async(ctx, p, ix, gd.shortlist) != 0 || snesimage_last_step(ctx, nullptr, nullptr, &k) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
                     gs.calls += 1; gs.accepted += k >= 0 ? 1u : 0u;
                 }
-        } else if (snesimage_guided_sweep(ctx, guided_short, nullptr, &gs) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+        } else if (snesimage_guided_sweep(ctx, gd.shortlist, nullptr, &gs) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
         if (snesimage_error(ctx, &e1) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
-        log_info("Guided sweep: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + (guided_proxy == SNES_GUIDE_CIELAB ? "cielab" : "redmean") + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        log_info("Guided sweep: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + gd.proxy_name() + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
         load_before(); // (the colours the next calls' reports compare with)
     };
@@ -831,18 +829,18 @@ int main(int argc, char **argv) {
             for (uint32_t p = 0; p < count; p++)
                 for (uint32_t ix = 0; ix < size; ix++) {
                     snesimage_call_result r{};
-                    if (snesimage_shared_guided_step_async(set, p, ix, set_guided_short) != 0 || snesimage_shared_last_step(set, &r) != 0) die(what + snesimage_last_error());
+                    if (snesimage_shared_guided_step_async(set, p, ix, sgd.shortlist) != 0 || snesimage_shared_last_step(set, &r) != 0) die(what + snesimage_last_error());
                     gs.calls += 1; gs.accepted += r.best_k >= 0 ? 1u : 0u;
                 }
-        } else if (snesimage_shared_guided_sweep(set, set_guided_short, nullptr, &gs) != 0) die(what + snesimage_last_error());
+        } else if (snesimage_shared_guided_sweep(set, sgd.shortlist, nullptr, &gs) != 0) die(what + snesimage_last_error());
         if (snesimage_shared_error(set, &e1) != 0) die(what + snesimage_last_error());
-        log_info("Guided sweep of the set: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + (set_guided_proxy == SNES_GUIDE_CIELAB ? "cielab" : "redmean") + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
+        log_info("Guided sweep of the set: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + sgd.proxy_name() + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }
         load_before(); // (the colours the next calls' reports compare with)
     };
     auto end_of_sweep = [&]() {
-        if (guided_every && step != sweep && step % guided_every == 0) guided_sweep(); // in front of everything that moves tiles: they see the palette it leaves
-        if (set_guided_every && step != sweep && step % set_guided_every == 0) set_guided_sweep(); // (the same place for a set)
+        if (gd.every && step != sweep && step % gd.every == 0) guided_sweep(); // in front of everything that moves tiles: they see the palette it leaves
+        if (sgd.every && step != sweep && step % sgd.every == 0) set_guided_sweep(); // (the same place for a set)
         if (reassign_every && step != sweep && step % reassign_every == 0) { // a sweep over every slot has just ended (src/lib.rs:925-931)
             uint32_t moved = 0;
             if (set) { if (snesimage_shared_reassign_tiles(set, &moved) != 0) die(std::string("Unable to reassign tiles: ") + snesimage_last_error()); }
@@ -873,7 +871,7 @@ int main(int argc, char **argv) {
         for (uint32_t call = 0; call < calls;) {
             uint32_t n = calls - call;
             if (n > 4096) n = 4096;
-            if (reassign_every || tile_every || level_every || set_level_every || guided_every || set_guided_every || bd_fixed) { // calls left in the current sweep
+            if (reassign_every || tile_every || level_every || set_level_every || gd.every || sgd.every || bd_fixed) { // calls left in the current sweep
                 uint32_t p = palette, ix = index, ch = channel, st = step, m = 0, k = 0;
                 while (st == step && k < n) { sched_next(&p, &ix, &ch, &st, &m); k++; }
                 n = k;

@@ -5,15 +5,15 @@
 // d(c, x) = ciede2000(Lab(rgb8(c)), Lab(T(x))) in f32, entry first, as prep_body calls it, made an exact integer by
 // q(d) = min((uint32_t)(d * 65536.0f), 0xFFFFFF).  q is monotone, so min(q(m), q(d)) = q(min(m, d)): the floor travels as
 // the f32 distance and one conversion per pixel and colour serves both.
-//   k_guide_gather_lab    the slot's population as a list of (Lab of T, floor m as f32), 16 bytes a pixel, one block per tile;
-//   ks_guide_gather_lab   the same over the members of a set, one block per global tile;
+//   k_guide_gather_lab    the slot's population over all members as a list of (Lab of T, floor m as f32), 16 bytes a pixel,
+//                         one block per global tile;
 //   k_guide_cost_lab      cost(u) = sum over the list of q(min(m, d(c_u, x))), one lane per colour, one block per 256
 //                         colours and slice of the list; the slices meet in 64-bit integer atomic adds.
-// k_guide_select / ks_guide_select take the table as it is: a cost is below 2^43.
+// k_guide_select takes the table as it is: a cost is below 2^43.
 // Every sum is an integer sum: neither the order of the list, nor the order of the adds, nor the colour a lane holds shows in
 // the result.  All kernels are wave64; stores are plain vector stores.
 #pragma once
-#include "kernels_guide_set.hpp"
+#include "kernels_guide.hpp"
 
 namespace snes {
 
@@ -29,12 +29,19 @@ __device__ __forceinline__ Lab guide_lab_of(uint32_t rgb8, const float *__restri
 // d * 2^16 is exact in f32; clamping before the truncation equals clamping behind it (0xFFFFFF is a float)
 __device__ __forceinline__ uint32_t guide_lab_q(float d) { return (uint32_t)fminf(d * 65536.0f, kGuideLabQMax); }
 
-// One tile's 64 pixels behind the list's next 64 places (k_guide_gather's body in Lab).  s_pal: the Lab of the tile's subpalette.
-__device__ __forceinline__ void guide_gather_lab_tile(const uint8_t *__restrict__ target, const uint8_t *__restrict__ colors, const float *__restrict__ lab_eotf, int t, int p, int W, int sub_size,
-                                                      int si, GuideLabPixel *__restrict__ list, unsigned int *__restrict__ count, Lab *s_pal, unsigned int *s_at) {
-    const int lane = threadIdx.x;
+// The population.  grid = the global tiles g = member * ntile + tile, block = the tile's 64 pixels (one wave); k_guide_gather's
+// discipline and body, in Lab.
+__global__ __launch_bounds__(64) void k_guide_gather_lab(const GuideMember *__restrict__ M, const uint8_t *__restrict__ colors, const float *__restrict__ lab_eotf, int ntile, int W, int sub_size,
+                                                        int sp, int si, GuideLabPixel *__restrict__ list, unsigned int *__restrict__ count) {
+    __shared__ Lab s_pal[256]; // (sub_count * sub_size <= 253)
+    __shared__ unsigned int s_at;
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int f = g / ntile, t = g - f * ntile;
+    const uint8_t *__restrict__ target = M[f].target;
+    const int p = M[f].tile_pal[t];
+    if (sp >= 0 && p != sp) return; // (uniform over the block)
     for (int j = lane; j < sub_size && j < 256; j += 64) { const uint8_t *c = colors + 3 * (p * sub_size + j); s_pal[j] = guide_lab_of(rgb5_to_rgb8(c[0], c[1], c[2]), lab_eotf); }
-    if (lane == 0) *s_at = atomicAdd(count, 1u);
+    if (lane == 0) s_at = atomicAdd(count, 1u);
     __syncthreads();
     const int px = ((t >> 5) * 8 + (lane >> 3)) * W + (t & 31) * 8 + (lane & 7);
     const uint32_t o = reinterpret_cast<const uint32_t *>(target)[px];
@@ -42,31 +49,8 @@ __device__ __forceinline__ void guide_gather_lab_tile(const uint8_t *__restrict_
     float m = __builtin_inff();
     for (int j = 0; j < sub_size; j++)
         if (j != si) { const float d = ciede2000(s_pal[j], tl); m = d < m ? d : m; }
-    GuideLabPixel g; g.l = tl.l; g.a = tl.a; g.b = tl.b; g.m = (o >> 24) == 0 ? 0.0f : m;
-    list[(size_t)(*s_at) * 64 + lane] = g;
-}
-
-// The population.  grid = the tiles of the image, block = the tile's 64 pixels (one wave); k_guide_gather's discipline.
-__global__ __launch_bounds__(64) void k_guide_gather_lab(const uint8_t *__restrict__ target, const uint8_t *__restrict__ tile_pal, const uint8_t *__restrict__ colors, const float *__restrict__ lab_eotf,
-                                                        int W, int sub_size, int sp, int si, GuideLabPixel *__restrict__ list, unsigned int *__restrict__ count) {
-    __shared__ Lab s_pal[256]; // (sub_count * sub_size <= 253)
-    __shared__ unsigned int s_at;
-    const int t = blockIdx.x;
-    const int p = tile_pal[t];
-    if (sp >= 0 && p != sp) return; // (uniform over the block)
-    guide_gather_lab_tile(target, colors, lab_eotf, t, p, W, sub_size, si, list, count, s_pal, &s_at);
-}
-
-// The population of a set.  grid = the G global tiles g = member * ntile + tile; ks_guide_gather's discipline.
-__global__ __launch_bounds__(64) void ks_guide_gather_lab(const GuideMember *__restrict__ M, const uint8_t *__restrict__ colors, const float *__restrict__ lab_eotf, int ntile, int W, int sub_size,
-                                                         int sp, int si, GuideLabPixel *__restrict__ list, unsigned int *__restrict__ count) {
-    __shared__ Lab s_pal[256];
-    __shared__ unsigned int s_at;
-    const int g = blockIdx.x;
-    const int f = g / ntile, t = g - f * ntile;
-    const int p = M[f].tile_pal[t];
-    if (sp >= 0 && p != sp) return; // (uniform over the block)
-    guide_gather_lab_tile(M[f].target, colors, lab_eotf, t, p, W, sub_size, si, list, count, s_pal, &s_at);
+    GuideLabPixel q; q.l = tl.l; q.a = tl.a; q.b = tl.b; q.m = (o >> 24) == 0 ? 0.0f : m;
+    list[(size_t)s_at * 64 + lane] = q;
 }
 
 // cost(u) for 256 colours over slice blockIdx.y of the list.  The slice is staged in LDS and read by all lanes at one address

@@ -7,8 +7,8 @@
 struct snesimage_shared_window; // slot windows of the set (shared_window_host.inc)
 struct snesimage_sharedchar;    // workspace of the set's character budget (shared_char_host.inc)
 struct snesimage_sharedlevel;   // workspace of the set's per-tile dither levels (shared_level_host.inc)
-struct snesimage_sharedguide;   // workspace of the set's guided calls (shared_guide_host.inc)
-namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); void shared_level_free(snesimage_sharedlevel *w); void shared_guide_free(snesimage_sharedguide *w); }
+struct snesimage_guidework;     // workspace and generator of guided calls, a context's and the set's (guide_host.inc)
+namespace { void shared_window_free(snesimage_shared_window *w); void shared_char_free(snesimage_sharedchar *w); void shared_level_free(snesimage_sharedlevel *w); void guide_free(snesimage_guidework *&w); }
 
 struct snesimage_shared {
     snesimage_batch *b = nullptr;
@@ -19,7 +19,7 @@ struct snesimage_shared {
     std::vector<unsigned long long> epoch;    // each member's palette / tile-map generation when the set last touched it
     snesimage_sharedchar *chr = nullptr;      // the character budget of the set, made on first use
     snesimage_sharedlevel *lvl = nullptr;     // the tied level calls of the set, made on first use
-    snesimage_sharedguide *guide = nullptr;   // the guided calls of the set, made on first use
+    snesimage_guidework *guide = nullptr;     // the guided calls of the set, made on first use
     uint32_t guide_proxy = 0;                 // snesimage_shared_set_guided_proxy: the set's own, the members' are neither read nor written
     bool reduced = false;                     // snesimage_shared_reduce_characters left merged maps: stored maps that are no optimize() of the palette
     // a backdrop set (snesimage_shared_create_backdrop; DESIGN §5c''): every member is a SNES_BACKDROP context and holds the set's B
@@ -404,7 +404,7 @@ void snesimage_shared_destroy(snesimage_shared *s) {
     if (s->win) { shared_window_free(s->win); s->win = nullptr; } // (its slot contexts borrow the members' planes: before the members go)
     if (s->chr) { shared_char_free(s->chr); s->chr = nullptr; }
     if (s->lvl) { shared_level_free(s->lvl); s->lvl = nullptr; }
-    if (s->guide) { shared_guide_free(s->guide); s->guide = nullptr; }
+    guide_free(s->guide);
     snesimage_batch_destroy(s->b); // (waits for its stream)
     if (s->d_joint) (void)hipFree(s->d_joint);
     if (s->d_sum) (void)hipFree(s->d_sum);

@@ -379,6 +379,51 @@ def test_refusals_leave_the_context_usable(S):
     twin.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("proxy", ["redmean", "cielab"])
+def test_the_member_table_follows_the_context(S, proxy):
+    """The generator reaches a context's planes through a one-entry member table on the device (kernels_guide.hpp: GuideMember).
+    The target moves when an ordered-dither table is set or cleared, the candidate list when a call needs more room than 64:
+    the calls behind either equal those of a fresh context in the same state, whose table was written once."""
+    img, table = GM.image(16, 14), OM.bayer(4, 64)
+
+    def fresh_twin(g, table):
+        t = S.OptimizedImage(img, 2, 3)
+        t.guided_proxy = proxy
+        if table is not None:
+            t.set_ordered_dither(table)
+        t.tile_palettes, t.palette = g.tile_palettes, g.palette
+        t.optimize()
+        return t
+
+    g = S.OptimizedImage(img, 2, 3)
+    g.guided_proxy = proxy
+    g.initialize_tiles()
+    g.recalculate_palettes()
+    assert sorted(np.unique(g.tile_palettes).tolist()) == [0, 1], "one subpalette is unused: the case shows less"
+    plain = g.guided_costs(0, 1)  # the member table exists
+    g.set_ordered_dither(table)  # the target moves
+    g.optimize()
+    g.step(S.METHOD_RANDOM, 1, 0, 0, 1, 0, 256)  # the candidate list grows
+    twin = fresh_twin(g, table)
+    dithered = g.guided_costs(0, 1)
+    assert (dithered != plain).any(), "the table changes no cost: the case shows nothing"  # (the step touched subpalette 1 only)
+    assert_costs_equal(dithered, twin.guided_costs(0, 1), "slot (0, 1) behind the table and the long call")
+    assert_costs_equal(g.guided_costs(1, 2), twin.guided_costs(1, 2), "slot (1, 2) behind the table and the long call")
+    (ra, ca), (rb, cb) = g.guided_candidates(1, 1, 8), twin.guided_candidates(1, 1, 8)
+    assert np.array_equal(ra, rb) and np.array_equal(ca, cb)
+    la, lb = g.guided_sweep(4)[0], twin.guided_sweep(4)[0]
+    assert [(x[1], x[2].tolist()) for x in la] == [(x[1], x[2].tolist()) for x in lb] and all(close(x[0], y[0]) for x, y in zip(la, lb))
+    assert np.array_equal(g.palette, twin.palette) and np.array_equal(g.palette_map, twin.palette_map)
+    g.set_ordered_dither(None)  # the target moves back
+    g.optimize()
+    twin.close()
+    twin = fresh_twin(g, None)
+    assert_costs_equal(g.guided_costs(0, 1), twin.guided_costs(0, 1), "slot (0, 1) behind the cleared table")
+    g.close()
+    twin.close()
+
+
 def drive(S, g, calls, every, k, seed=1, fixed=False):
     """The CLI's loop call by call: scheduled calls of 64, one guided sweep behind every `every` sweeps of the palette.
     fixed: --backdrop-fixed, whose schedule and guided sweeps pass the backdrop slot by."""
