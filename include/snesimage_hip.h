@@ -745,6 +745,33 @@ int32_t snesimage_guided_candidates(snesimage_ctx *ctx, uint32_t palette, uint32
 int32_t snesimage_guided_step(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k, double *best_error, uint8_t *best_rgb5);
 int32_t snesimage_guided_step_async(snesimage_ctx *ctx, uint32_t palette, uint32_t index, uint32_t k); /* results via snesimage_last_step */
 int32_t snesimage_guided_sweep(snesimage_ctx *ctx, uint32_t k, snesimage_call_result *log /* optional, one per slot */, snesimage_run_stats *stats /* optional */);
+/* GUIDED CALLS THROUGH THE SLOT WINDOWS (DESIGN 5f''').  n_calls guided calls of shortlist k (1..64, 0 = 16) from slot
+ * (*palette, *index) on, in the order of snesimage_guided_sweep: index is the inner loop, palette the outer; on a backdrop
+ * context the tied slot (sub_count, 0) comes last; behind the last slot comes (0, 0) again.  On return *palette, *index name the
+ * slot of the call that would come next.  Equivalent, bit for bit, to snesimage_guided_step_async per call: the palette, the map,
+ * the incumbent, the snesimage_last_step record and every log[j] with its error's bits.
+ *   A guided call's shortlist depends on the palette, tile_palettes and the target image only, none of which a rejected call
+ *   changes, so the calls speculate as the scheduled calls of snesimage_run_slots do: a window is the next calls in slot order,
+ *   scored against the palette as it stands in one set of launches, committed in order (best := incumbent, strict <, ascending
+ *   k); what lies behind the first acceptance is void and runs again in the next window.  The shortlists of a window come from
+ *   one batched run of the generator (one pixel list, count and 32,768-entry table per call; integer sums throughout).
+ *   window: 0 = adaptive, 1 = call by call, otherwise that many calls per launch set, at most SNES_WINDOW_MAX (default 64).  The
+ *   adaptive size of guided windows is kept apart from that of snesimage_run_slots: a guided run between two scheduled runs
+ *   changes neither the launch sets nor the stats of those.
+ *   stats (optional) as snesimage_run_slots fills it: scored = calls taken x k, useful = calls that took effect x k, windows
+ *   = launch sets (a call stepped on its own counts as one), voided = windows enqueued ahead that an acceptance voided.
+ *   log (optional): n_calls records.
+ *   A window ends in front of the tied slot of a backdrop context, which is stepped on its own.  Stepped call by call inside the
+ *   function as well: a context the windows do not cover (snesimage_run_slots), a first call from a palette_map that is not
+ *   optimize() of the palette, window = 1, and a context whose proxy is SNES_GUIDE_CIELAB (no batched CIELAB generator).
+ *   The workspace of the batched generator (lists and tables for SNES_WINDOW_MAX calls: 32 MB + 16 MB at 256 x 256) is allocated
+ *   by the first guided window and freed with the context, all or nothing.
+ *   Refusals: those of the guided calls above and of snesimage_run_slots — SNES_ERR_ARG for a null context or pointer, a slot out
+ *   of range or k > 64; SNES_ERR_UNSUPPORTED on a SNES_NES context; SNES_ERR_STATE between the phases of a split-phase step or
+ *   window and on a context lent to a batch, a set or a group; SNES_ERR_HIP for a failed workspace allocation, which leaves the
+ *   context as it was and usable. */
+int32_t snesimage_guided_run_slots(snesimage_ctx *ctx, uint32_t n_calls, uint32_t k, uint32_t *palette, uint32_t *index, uint32_t window,
+                                   snesimage_call_result *log, snesimage_run_stats *stats);
 /* NOT a reference method: GUIDED CALLS OF A SET (DESIGN 5f').  The proxy above carries over to a shared-palette set without a new
  * definition: the palette and the slot are shared and the floor of a pixel depends on that pixel's own tile only.  Integers only,
  * except the objective.  For a set of F members with geometry (C, S), the shared palette and slot (p, i):
@@ -841,6 +868,15 @@ void snesimage_debug_fail_alloc(int32_t n);
  * float) when it is allocated, so that a read of anything no kernel wrote shows in the results instead of reading the
  * zeros a fresh allocation often holds.  Applies to storage allocated after the call. */
 void snesimage_debug_poison_alloc(int32_t on);
+/* Test hook: the shortlists snesimage_guided_run_slots scored.  While the capture is on (non-zero), every run keeps, for each
+ * call that took effect, the k candidates the call scored, read back from where the scorer read them — the window's candidate
+ * list for a call of a window (the calls voided behind an acceptance are not kept: they run again), the context's for a
+ * call stepped on its own; a run replaces what the run before it kept, and the read-back synchronises, so the capture is for
+ * tests.  snesimage_debug_guided_shortlists copies them out: *n_calls and *k of the last captured run, and, if rgb5 is not
+ * null and holds cap >= n_calls * k * 3 bytes, the raw 5-bit triples, call after call, candidate 0 first (SNES_ERR_ARG for
+ * a null context or a buffer that is too short). */
+int32_t snesimage_debug_guided_capture(snesimage_ctx *ctx, int32_t on);
+int32_t snesimage_debug_guided_shortlists(snesimage_ctx *ctx, uint8_t *rgb5, uint32_t cap, uint32_t *n_calls, uint32_t *k);
 /* Launch timing by the library's own HIP events on the stream each launch group runs on (bench.py's roofline leg).
  * While enabled, every scoring launch group records events; timing_read() returns summed milliseconds:
  *   ms3[0] = the whole launch group (all kernels that score one chunk of candidates);

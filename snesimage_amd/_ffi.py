@@ -168,6 +168,7 @@ SIGNATURES = [
     ("snesimage_guided_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f64p, _u8p]),
     ("snesimage_guided_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("snesimage_guided_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
+    ("snesimage_guided_run_slots", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
     ("snesimage_shared_guided_costs", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u64p]),
     ("snesimage_shared_guided_candidates", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, _u64p]),
     ("snesimage_shared_guided_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f64p, _u8p]),
@@ -187,6 +188,8 @@ SIGNATURES = [
     ("snesimage_debug_math", C.c_int32, [C.c_int32, C.c_int32, _f32p, _f32p, C.c_uint32, _f32p]),
     ("snesimage_debug_fail_alloc", None, [C.c_int32]),
     ("snesimage_debug_poison_alloc", None, [C.c_int32]),
+    ("snesimage_debug_guided_capture", C.c_int32, [C.c_void_p, C.c_int32]),
+    ("snesimage_debug_guided_shortlists", C.c_int32, [C.c_void_p, _u8p, C.c_uint32, _u32p, _u32p]),
     ("snesimage_timing_enable", C.c_int32, [C.c_void_p, C.c_int32]),
     ("snesimage_timing_read", C.c_int32, [C.c_void_p, _f64p, _u64p, _u64p]),
     ("snesimage_last_error", C.c_char_p, []),

@@ -538,6 +538,30 @@ class OptimizedImage:
         out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log]
         return out, {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
+    def guided_run_slots(self, n_calls, k=0, state=(0, 0), window=0, want_log=True):
+        """n_calls guided calls of shortlist k from slot state = (palette, index) on, in the guided sweep's slot order (behind
+        the last slot the first again), several calls per launch set: bit-identical to `guided_step` per call for every
+        `window` (0 = adaptive, 1 = call by call).  Returns (log, state, stats) shaped like `run_slots`."""
+        st = [C.c_uint32(int(v)) for v in state]
+        log = (_ffi.CallResult * n_calls)() if want_log else None
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_guided_run_slots(self._c, int(n_calls), int(k), C.byref(st[0]), C.byref(st[1]), int(window), log, C.byref(stats)))
+        out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log] if want_log else None
+        return out, tuple(v.value for v in st), {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    def debug_guided_capture(self, on=True):
+        """Test hook: keep the shortlists that the calls of `guided_run_slots` score (snesimage_debug_guided_capture)."""
+        self._chk(self._L.snesimage_debug_guided_capture(self._c, 1 if on else 0))
+
+    def debug_guided_shortlists(self):
+        """Test hook: the shortlists of the last captured run -> rgb5[n_calls, k, 3], in call order."""
+        n, k = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.snesimage_debug_guided_shortlists(self._c, None, 0, C.byref(n), C.byref(k)))
+        out = np.zeros((n.value, k.value, 3), np.uint8)
+        if out.size:
+            self._chk(self._L.snesimage_debug_guided_shortlists(self._c, _p(out, _ffi._u8p), out.size, C.byref(n), C.byref(k)))
+        return out
+
     @property
     def guided_proxy(self):
         """The metric of the guided calls' cost table: "redmean" (the default) or "cielab" — the same objective measured in

@@ -14,6 +14,7 @@
 #include "kernels_char_set.hpp"
 #include "kernels_guide.hpp"
 #include "kernels_guide_lab.hpp"
+#include "kernels_guide_window.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -236,6 +237,7 @@ struct snesimage_ctx {
     struct snesimage_charwork *chr = nullptr;  // workspace of the character budget (char_host.inc), created on first use
     struct snesimage_guidework *guide = nullptr; // workspace and generator of the guided calls (guide_host.inc), created on first use
     uint32_t guide_proxy = 0;                    // snesimage_set_guided_proxy: the metric of the guided calls' table (SNES_GUIDE_REDMEAN)
+    bool guide_capture = false; std::vector<uint8_t> guide_captured; uint32_t guide_captured_k = 0; // snesimage_debug_guided_capture: the last run's shortlists (guided_window_host.inc)
 
     // cache keys
     bool tables_valid = false, src_valid = false, inc_valid = false;
@@ -1753,3 +1755,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "shared_level_host.inc"
 #include "guide_host.inc"
 #include "shared_guide_host.inc"
+#include "guided_window_host.inc"

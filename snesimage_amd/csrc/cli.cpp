@@ -37,7 +37,7 @@
 // --set-tilemap FILE writes the set's characters and one tilemap per frame (snesimage_shared_as_tilemap_json).
 // --refit-set-tiles N (with --share) runs up to N refit sweeps over the whole set behind that (snesimage_shared_refit_characters):
 // every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
-// --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_sweep): on every
+// --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_run_slots, --window calls per launch set): on every
 // slot the --guided-shortlist K colours an integer proxy ranks best among all 32,768 are scored, and the error decides.
 // --guided-proxy / --set-guided-proxy redmean|cielab choose the proxy's distance (snesimage_set_guided_proxy; DESIGN 5f'').
 // --set-guided G (with --share) does the same for a set (snesimage_shared_guided_sweep): the proxy runs over the tiles of all
@@ -137,7 +137,8 @@ void usage() {
             "      --guided <G>         behind every G sweeps of the palette, one guided sweep: on every slot, all 32,768 colours are ranked by what\n"
             "                           the slot's pixels would cost in colour distance, and the --guided-shortlist best are scored by the error\n"
             "                           itself; runs in front of --reassign-tiles, --tile-moves and --tile-dither; with --backdrop-fixed the\n"
-            "                           backdrop slot is passed by; not with --share, --devices or --nes\n"
+            "                           backdrop slot is passed by; not with --share, --devices or --nes.  The calls of a guided sweep go\n"
+            "                           through the launch sets of --window like the scheduled ones (same result for every --window)\n"
             "      --guided-shortlist <K>  colours scored per guided call, 1..64 [default: 16: a choice, not a measurement]; needs --guided\n"
             "      --guided-proxy <PROXY>  the distance that ranks the colours: redmean, or cielab (CIEDE2000, the distance the pixels choose\n"
             "                           their entry by under --perceptual-palettes) [default: redmean]; needs --guided\n"
@@ -807,14 +808,9 @@ int main(int argc, char **argv) {
         snesimage_run_stats gs{};
         double e0 = 0.0, e1 = 0.0;
         if (snesimage_error(ctx, &e0) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
-        if (bd_fixed) {
-            for (uint32_t p = 0; p < count; p++)
-                for (uint32_t ix = 0; ix < size; ix++) {
-                    int32_t k = -1;
-                    if (snesimage_guided_step_async(ctx, p, ix, gd.shortlist) != 0 || snesimage_last_step(ctx, nullptr, nullptr, &k) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
-                    gs.calls += 1; gs.accepted += k >= 0 ? 1u : 0u;
-                }
-        } else if (snesimage_guided_sweep(ctx, gd.shortlist, nullptr, &gs) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
+        // through the slot windows, --window calls per launch set (1: call by call; the same result); count * size calls from (0, 0) end in front of the backdrop slot
+        uint32_t gp = 0, gi = 0;
+        if (snesimage_guided_run_slots(ctx, count * size + (bd_sched ? 1u : 0u), gd.shortlist, &gp, &gi, window, nullptr, &gs) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
         if (snesimage_error(ctx, &e1) != 0) die(std::string("Unable to run a guided sweep: ") + snesimage_last_error());
         log_info("Guided sweep: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + gd.proxy_name() + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }

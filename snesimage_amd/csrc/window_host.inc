@@ -70,6 +70,10 @@ struct snesimage_window {
     uint32_t adapt = 8;                 // next window's size when the caller leaves it to the library
     WindowPolicy policy;                // acceptance rate of the recent windows -> size of the next one
     uint32_t clean_streak = 0;          // windows in a row that accepted nothing
+    // guided windows (guided_window_host.inc) size themselves: a guided run between two scheduled runs leaves the launch sets of those as they were
+    uint32_t g_adapt = 8; WindowPolicy g_policy; uint32_t g_clean_streak = 0;
+    // ... and their generator's workspace, for window_max() calls: per call the pixel list, and the counts in front of the cost tables
+    snes::GuidePixel *g_list = nullptr; unsigned long long *g_tab = nullptr;
 };
 
 namespace {
@@ -88,6 +92,15 @@ void ctx_schedule_next(const snesimage_ctx *c, int nes, uint32_t *palette, uint3
     else snesimage_schedule_next(c->sub_count, c->sub_size, nes, palette, index, channel, step, method);
 }
 bool window_capable(const snesimage_ctx *c) { return c->sp.enabled && !c->owner && !(c->dither && c->sub_size == 1); } // (one-entry subpalettes with --dither: dense path, see score_list)
+
+// A window whose calls are not the scheduler's: the caller of window_enqueue names the slot order and writes the candidate
+// lists itself.  next: the slot behind (*palette, *index); generate: n candidates for each of the window's K calls (r.d_slots:
+// their slots) into r.d_cand and the errors preset to +inf, on the context's main stream, where kw_gen_candidates runs.
+struct WindowGen {
+    uint32_t n;
+    void (*next)(const snesimage_ctx *c, uint32_t *palette, uint32_t *index);
+    int32_t (*generate)(snesimage_ctx *c, WindowRec &r, uint32_t K, uint32_t n, double *d_errors);
+};
 
 void window_release_child(snesimage_ctx *k) {
     // borrowed from the parent: not ours to free
@@ -143,7 +156,7 @@ void window_free(snesimage_window *w) {
     if (w->side) { (void)hipStreamSynchronize(w->side); if (!w->side_borrowed) (void)hipStreamDestroy(w->side); }
     if (w->aux) { (void)hipStreamSynchronize(w->aux); (void)hipStreamDestroy(w->aux); }
     for (auto &r : w->rec) { window_rec_free(r); for (auto &e : r.ev) if (e) (void)hipEventDestroy(e); if (r.done) (void)hipEventDestroy(r.done); if (r.args) (void)hipEventDestroy(r.args); }
-    dfree(w->d_dead);
+    dfree(w->d_dead); dfree(w->g_list); dfree(w->g_tab);
     delete w;
 }
 
@@ -194,7 +207,7 @@ int32_t window_reserve(snesimage_ctx *c, uint32_t K, uint32_t own, int set = 0) 
 // n_slots, cut where the method changes (every call of a window has the same number of candidates) — against the palette
 // as it stands when the launches reach the device.  d_errors == nullptr: the record's own vector.
 int32_t window_enqueue(snesimage_ctx *c, WindowRec &r, uint32_t n_slots, uint64_t seed, uint64_t first_step_id, uint32_t palette, uint32_t index, uint32_t channel, uint32_t step, uint32_t n_random,
-                       uint32_t shard_rank, uint32_t shard_count, double *d_errors, int set = 0, bool ahead = false) {
+                       uint32_t shard_rank, uint32_t shard_count, double *d_errors, int set = 0, bool ahead = false, const WindowGen *gen = nullptr) {
     snesimage_window *w = c->win;
     struct Call { uint32_t method, palette, index, channel; } calls[snes::kMaxWindow];
     uint32_t K = 0;
@@ -202,11 +215,12 @@ int32_t window_enqueue(snesimage_ctx *c, WindowRec &r, uint32_t n_slots, uint64_
       while (K < n_slots) {
           const uint32_t cp = p, ci = i, cc = ch;
           if (c->backdrop && cp == c->sub_count) break; // a window ends in front of a backdrop call (snesimage_run_slots steps it on its own)
+          if (gen) { gen->next(c, &p, &i); calls[K++] = Call{SNES_METHOD_RANDOM, cp, ci, 0u}; continue; } // the caller's slot order; committed by the random method's rule
           ctx_schedule_next(c, c->nes ? 1 : 0, &p, &i, &ch, &st, &m);
           if (K == 0) m0 = m; else if (m != m0) break;
           calls[K++] = Call{m, cp, ci, cc};
       } }
-    const uint32_t method = calls[0].method, n = method_count(method, n_random);
+    const uint32_t method = calls[0].method, n = gen ? gen->n : method_count(method, n_random);
     if (n > 64) return fail(SNES_ERR_ARG, "a slot window holds at most 64 candidates per call");
     // The window's calls are dealt to the ranks in runs of `deal` consecutive calls, round robin (neighbouring calls walk the
     // entries of one subpalette — the same tiles, much the same contested pixels: a run shares what it reads — while the
@@ -250,7 +264,8 @@ int32_t window_enqueue(snesimage_ctx *c, WindowRec &r, uint32_t n_slots, uint64_
     hipStream_t as = whole ? w->side : st;
     HIPCHK(hipMemcpyAsync(r.d_blob, r.h_blob, args_off + sizeof(snes::BatchArgs) * members, hipMemcpyHostToDevice, as));
     if (whole) { HIPCHK(hipEventRecord(r.args, as)); HIPCHK(hipStreamWaitEvent(st, r.args, 0)); }
-    hipLaunchKernelGGL(kw_gen_candidates, dim3((n + 63) / 64, K), dim3(64), 0, st, r.d_slots, c->d_colors, r.d_cand, d_errors, (int)n, (const int *)w->d_dead, r.base);
+    if (gen) CHECK(gen->generate(c, r, K, n, d_errors)); // the caller's lists in the random candidates' place
+    else hipLaunchKernelGGL(kw_gen_candidates, dim3((n + 63) / 64, K), dim3(64), 0, st, r.d_slots, c->d_colors, r.d_cand, d_errors, (int)n, (const int *)w->d_dead, r.base);
     if (members) {
         // B's single-image sweeps (latency-bound: a few waves per call) on a side stream beside the candidates' scan and downscale
         BatchSide bs{w->use_side ? w->side : nullptr, r.ev[0], r.ev[1], r.ev[2], r.ev[3], whole};
