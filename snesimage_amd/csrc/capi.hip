@@ -195,6 +195,9 @@ struct snesimage_ctx {
         // Candidates of one list with one colour are one image: the lowest index is scored, the others take its error (kernels.hpp,
         // dedup_*).  Lists without dither of dedup_min candidates and more (SNES_DEDUP=0: never; SNES_DEDUP_MIN): a random
         // list of 1,024 holds 16 repeats, one of 4,096 holds 245 (6 %), and a shorter call has nothing to pay a further launch with.
+        // The candidates' wide V pass forms only the pooling sums whose weight in the score is not zero (kernels.hpp, kSumMasks;
+        // DESIGN 4a).  SNES_WEIGHT_MASK=0: all six of every (channel, scale), on every path — the same errors bit for bit.
+        bool weight_mask = true;
         bool dedup = true; uint32_t dedup_min = 1024; int *holder = nullptr; bool holder_dirty = false; // holder_dirty: a call failed between marking and reset
         bool enabled = false, side = true; uint32_t min_n = 1; uint32_t cap = 0, lanes = 0; // min_n: shortest list that takes the group-sparse path (SNES_SPARSE_MIN; until round 4: 64 — a channel sweep's 32 candidates, or a rank's share of a 64-candidate call, went the dense way: 0.35 ms against 0.27, 1.7 ms with --perceptual-palettes) // cap = candidates per lane the arrays were sized for
         SparseGeom S{};
@@ -623,6 +626,7 @@ SparseParams sparse_params(snesimage_ctx *c, uint32_t lane) {
     P.items = sp.items + (size_t)lane * sp.item_stride * kItemLists; P.item_count = sp.item_count + (size_t)lane * kItemLists; P.item_stride = sp.item_stride; // lane == nlanes: B
     P.ckf = sp.ckf; P.cka = sp.cka; P.part = sp.part; P.first = sp.first; P.ckh = sp.ckh; P.zeros = sp.ckh + sp.zeros_off; P.trash = sp.ckh + sp.zeros_off + 12LL * c->G.W;
     for (P.s_first = 0; P.s_first < c->G.nscales && c->G.sw[P.s_first] >= 64; P.s_first++) {} // first narrow scale
+    P.full_sums = sp.weight_mask ? 0 : 1;
     if (c->dither) {
         const uint32_t l = lane < c->nlanes ? lane : 0;
         P.use_maps = 1; P.sub_size = (int)c->sub_size; P.slot_ci = sp.slot_ci; P.subC4 = c->d_subC4; P.tile_pal = c->d_tile_pal;
@@ -1174,6 +1178,7 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (const char *e = getenv("SNES_HGRID")) { int v = atoi(e); if (v >= 1) c->sp.hgrid = (uint32_t)v; }
     if (const char *e = getenv("SNES_SPARSE_MIN")) { int v = atoi(e); if (v >= 1) c->sp.min_n = (uint32_t)v; }
     if (const char *e = getenv("SNES_DEDUP")) c->sp.dedup = atoi(e) != 0;
+    if (const char *e = getenv("SNES_WEIGHT_MASK")) c->sp.weight_mask = atoi(e) != 0;
     if (const char *e = getenv("SNES_DEDUP_MIN")) { int v = atoi(e); if (v >= 1) c->sp.dedup_min = (uint32_t)v; }
     Geom &G = c->G;
     G.W = (int)w; G.H = (int)h; G.nscales = 0;

@@ -56,6 +56,60 @@ SNES_HD int down_odd_row(const Geom &G, int s, int y) { return 2 * y + 1 < G.th[
 
 __device__ __constant__ double kSsim2Weight[108] = SSIM2_WEIGHTS; // include/ssimulacra2_constants.h
 
+// ---- the pooling sums the score needs -----------------------------------------------------------------------------
+// Msssim::score is ssim = fma(w[i], |term_i|, ssim) over six terms per (channel, scale), and more than half of the weights are
+// exactly 0.0: fma(0.0, |t|, ssim) returns ssim bit for bit for any finite t, so a sum whose weight is zero may hold any finite
+// value, and the candidates' wide V pass (kernels_sparse2.hpp) forms only the others.  The masks are derived from the weight
+// table itself, never written by hand: bit q of m[ns][ch][s] <=> sum q of maps_accumulate ({ssim1, ssim4, art1, art4, det1,
+// det4}) of (channel, scale) has a non-zero weight in a pyramid of ns scales.  The score walks the weights with one running
+// index over channel -> scale -> norm, so the weights of a (channel, scale) depend on how many scales the image has.
+constexpr int kSumAll = 0x3f, kSumSsim = 0x03, kSumEdge = 0x3c; // every sum / those of the SSIM map / those of the edge map
+struct SumMaskTable { unsigned char m[kMaxScales + 1][3][kMaxScales]; };
+constexpr double kSsim2WeightHost[108] = SSIM2_WEIGHTS;
+constexpr SumMaskTable make_sum_masks() {
+    SumMaskTable t{};
+    const int acc_of[6] = {0, 2, 4, 1, 3, 5}; // weight order {ssim1, art1, det1, ssim4, art4, det4} -> index of the sum
+    for (int ns = 1; ns <= kMaxScales; ns++)
+        for (int ch = 0; ch < 3; ch++)
+            for (int s = 0; s < ns; s++) {
+                int m = 0;
+                for (int e = 0; e < 6; e++) if (kSsim2WeightHost[(ch * ns + s) * 6 + e] != 0.0) m |= 1 << acc_of[e];
+                t.m[ns][ch][s] = (unsigned char)m;
+            }
+    return t;
+}
+constexpr SumMaskTable kSumMasksHost = make_sum_masks();
+__device__ __constant__ SumMaskTable kSumMasks = make_sum_masks();
+// The masked body is instantiated for the distinct masks of the three widest scales of a full pyramid (nine at most) and for
+// the full mask; a block takes the smallest instantiated mask that holds every sum it needs (any other pyramid: the same rule,
+// the full mask at worst).
+constexpr int kSumClasses = 10;
+struct SumClassTable { unsigned char m[kSumClasses]; };
+constexpr SumClassTable make_sum_classes() {
+    SumClassTable t{};
+    int n = 0;
+    for (int ch = 0; ch < 3; ch++)
+        for (int s = 0; s < 3 && s < kMaxScales; s++) {
+            const unsigned char m = kSumMasksHost.m[kMaxScales][ch][s];
+            bool seen = false;
+            for (int i = 0; i < n; i++) seen = seen || t.m[i] == m;
+            if (!seen) t.m[n++] = m;
+        }
+    for (; n < kSumClasses; n++) t.m[n] = (unsigned char)kSumAll;
+    return t;
+}
+constexpr SumClassTable kSumClassesHost = make_sum_classes();
+__device__ __constant__ SumClassTable kSumClassTab = make_sum_classes();
+constexpr bool sum_class_is_first(int i) { for (int j = 0; j < i; j++) if (kSumClassesHost.m[j] == kSumClassesHost.m[i]) return false; return true; }
+__device__ __forceinline__ int sum_class(const int need) { // index of the smallest instantiated mask that holds `need`
+    int best = kSumClasses - 1, bits = 7;
+    for (int i = 0; i < kSumClasses; i++) {
+        const int m = kSumClassTab.m[i];
+        if ((m & need) == need && __builtin_popcount(m) < bits) { best = i; bits = __builtin_popcount(m); }
+    }
+    return best;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Palette tables: per colour index the linear RGB and positive-XYB triple of its 8-bit expansion.
 // Entry ncol is reserved for the candidate, entry ncol+1 is the transparent pixel (0,0,0).
@@ -473,26 +527,44 @@ __global__ __launch_bounds__(256) void k_source_scale0(const uint8_t *__restrict
 // sums, ten orders below the 1e-5 the error may move.  It replaces a binary64 division per pixel and channel (a quarter
 // of the V pass's issue slots) by a subtraction and a product.
 // ------------------------------------------------------------------------------------------------
+// MASK: the sums to form (kSumAll: all six).  A sum in MASK takes the same operations on the same values in the same order
+// whatever else MASK holds; the others are left alone, and what only they need (the SSIM quotient without ssim1 and ssim4: m1,
+// sd1, v22 and v12 are then unused; the edge term without the other four: a1, r1 and i2) is not computed.
+template <int MASK = kSumAll>
 __device__ __forceinline__ void maps_accumulate(double (&acc)[6], float m1, float sd1, float a1, double r1, float m2, float v22, float v12, float i2) {
-    const float mu22 = m2 * m2, mu12 = m1 * m2;
-    const float mu_diff = m1 - m2;
-    const float num_m = fmaf(mu_diff, -mu_diff, 1.0f);
-    const float num_s = fmaf(2.0f, v12 - mu12, SSIM2_C2);
-    const float denom_s = sd1 + (v22 - mu22) + SSIM2_C2;
-    double d = 1.0 - (double)((num_m * num_s) / denom_s);
-    d = d > 0.0 ? d : 0.0;
-    acc[0] += d;
-    const double dd = d * d;
-    acc[1] += dd * dd;
-    const double d1 = ((double)fabsf(i2 - m2) - (double)a1) * r1;
-    const double art = d1 > 0.0 ? d1 : 0.0;
-    const double det = (-d1) > 0.0 ? (-d1) : 0.0;
-    acc[2] += art;
-    const double a2 = art * art;
-    acc[3] += a2 * a2;
-    acc[4] += det;
-    const double l2 = det * det;
-    acc[5] += l2 * l2;
+    if (MASK & kSumSsim) {
+        const float mu22 = m2 * m2, mu12 = m1 * m2;
+        const float mu_diff = m1 - m2;
+        const float num_m = fmaf(mu_diff, -mu_diff, 1.0f);
+        const float num_s = fmaf(2.0f, v12 - mu12, SSIM2_C2);
+        const float denom_s = sd1 + (v22 - mu22) + SSIM2_C2;
+        double d = 1.0 - (double)((num_m * num_s) / denom_s);
+        d = d > 0.0 ? d : 0.0;
+        if (MASK & 1) acc[0] += d;
+        if (MASK & 2) {
+            const double dd = d * d;
+            acc[1] += dd * dd;
+        }
+    }
+    if (MASK & kSumEdge) {
+        const double d1 = ((double)fabsf(i2 - m2) - (double)a1) * r1;
+        if (MASK & 0x0c) {
+            const double art = d1 > 0.0 ? d1 : 0.0;
+            if (MASK & 4) acc[2] += art;
+            if (MASK & 8) {
+                const double a2 = art * art;
+                acc[3] += a2 * a2;
+            }
+        }
+        if (MASK & 0x30) {
+            const double det = (-d1) > 0.0 ? (-d1) : 0.0;
+            if (MASK & 0x10) acc[4] += det;
+            if (MASK & 0x20) {
+                const double l2 = det * det;
+                acc[5] += l2 * l2;
+            }
+        }
+    }
 }
 __device__ __forceinline__ float source_sd1(float mu1, float sigma11) { const float mu11 = mu1 * mu1; return sigma11 - mu11; }
 __device__ __forceinline__ float source_a1(float img1, float mu1) { return fabsf(img1 - mu1); }

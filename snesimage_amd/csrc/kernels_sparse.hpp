@@ -78,6 +78,7 @@ struct SparseParams {
     int *first;       // per candidate: first changed group of scale 0 (H/4 if none), written by the scan for k_sparse_order
     const int *order; // k_sparse_v: candidates of the launch, longest column sweeps first (k_sparse_order); nullptr = as listed
     const int *holder; int list0; // duplicate colours (kernels.hpp, dedup_*): the table, or nullptr; list index of the launch's first candidate
+    int full_sums; // 1: the candidates' wide V pass forms all six pooling sums of every (channel, scale) (SNES_WEIGHT_MASK=0); 0: only those with a non-zero weight (kSumMasks)
 };
 
 __device__ __forceinline__ uint32_t sparse_ci(uint32_t lo, uint32_t thr, uint32_t crgb, uint32_t ncol) {

@@ -426,13 +426,30 @@ __device__ __forceinline__ double2 buf_ld2d(rsrc_t r, uint32_t voff, uint32_t so
 
 // BASE: the image B itself — every group is its own, the sweep starts at the top with a zero state and leaves the
 // checkpoint records behind (record g: state before group iteration g and pooling sums of rows < 4g-4; record H/4+1: final sums).
-template <bool BASE>
-__device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int s, const int bx) { // bx: blockIdx.x unless the caller remaps blocks
-    __shared__ short s_slot[4][64]; // per wave: group -> slot in the candidate's storage, -1 = B's group
+//
+// MASK (candidates only; kernels.hpp, kSumMasks): the pooling sums whose weight in the score is not zero.  The body forms those
+// and nothing that only the others need:
+//   * without ssim1 and ssim4 (SS false) there is no SSIM map: no s22 / s12 recurrence, state, checkpoint load, H plane load
+//     or ring slot, and no m1 / sd1 load — the edge map needs mu2 alone;
+//   * without the other four (ED false) there is no a1 / r1 / XYB load;
+//   * only the sums in MASK are loaded from B's record, carried, reduced and stored; the `part` entries of the others are
+//     written as +0.0 (k_final_score* multiplies them by a zero weight: they must be finite, never stale).
+// B's own sweeps and the checkpoint records stay full, so candidates of every class resume from the same records.
+// LDS of one block, shared by the instantiations of the body (declared inside the template each would take its own copy)
+struct V2Shared {
+    short slot[4][64]; // per wave: group -> slot in the candidate's storage, -1 = B's group
     // tails: xy halves two deep, zw halves three deep, [slot][plane][thread]; the pooling reduction reuses the space
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[(2 + 3) * 3 * 256 * sizeof(float2)];
+    __attribute__((aligned(16))) unsigned char raw[(2 + 3) * 3 * 256 * sizeof(float2)];
+};
+template <bool BASE, int MASK>
+__device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int s, const int bx, V2Shared &sh) { // bx: blockIdx.x unless the caller remaps blocks
+    static_assert(!BASE || MASK == kSumAll, "B's sweep leaves full records");
+    constexpr bool SS = (MASK & kSumSsim) != 0, ED = (MASK & kSumEdge) != 0;
+    constexpr int NPL = SS ? 3 : 1; // H planes swept: mu2, s22, s12 | mu2
+    short (*s_slot)[64] = sh.slot;
+    unsigned char *const s_raw = sh.raw;
     double (*red)[6] = reinterpret_cast<double (*)[6]>(s_raw);
-    static_assert(sizeof(s_raw) >= 256 * 6 * sizeof(double), "reduction scratch must fit the tail ring");
+    static_assert(sizeof(sh.raw) >= 256 * 6 * sizeof(double), "reduction scratch must fit the tail ring");
     const Geom &G = P.G;
     // (the geometry arrays are indexed dynamically: without the readfirstlanes their values count as divergent)
     const int W = uni(G.sw[s]), H = uni(G.sh[s]), H4 = H >> 2;
@@ -493,15 +510,18 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
             for (int q = 0; q < 3; q++) { sa[p][q] = 0.0f; sb[p][q] = 0.0f; }
 #pragma unroll
         for (int q = 0; q < 6; q++) acc[q] = 0.0;
-    } else { // checkpoint record gs: ckf[s][ch][g][18][W], cka[s][ch][g][6][W]
+    } else { // checkpoint record gs: ckf[s][ch][g][18][W], cka[s][ch][g][6][W] — the planes and the sums this class carries
         const float *cf = P.ckf + P.S.off_ckf[s] + ((size_t)ch * (H4 + 2) + gs) * 18 * W + xw;
         const double *ca = P.cka + P.S.off_cka[s] + ((size_t)ch * (H4 + 2) + gs) * 6 * W + xw;
 #pragma unroll
         for (int p = 0; p < 3; p++)
 #pragma unroll
-            for (int q = 0; q < 3; q++) { sa[p][q] = ld_at<float>(cf + (size_t)(p * 6 + q) * W, l4); sb[p][q] = ld_at<float>(cf + (size_t)(p * 6 + 3 + q) * W, l4); }
+            for (int q = 0; q < 3; q++) {
+                sa[p][q] = p < NPL ? ld_at<float>(cf + (size_t)(p * 6 + q) * W, l4) : 0.0f;
+                sb[p][q] = p < NPL ? ld_at<float>(cf + (size_t)(p * 6 + 3 + q) * W, l4) : 0.0f;
+            }
 #pragma unroll
-        for (int q = 0; q < 6; q++) acc[q] = ld_at<double>(ca + (size_t)q * W, l8);
+        for (int q = 0; q < 6; q++) acc[q] = ((MASK >> q) & 1) ? ld_at<double>(ca + (size_t)q * W, l8) : 0.0;
     }
     // the three planes of group g for this wave: the candidate's if it wrote these columns, else B's; zeros below the image
     // (the prefetch stays unconditional: no per-iteration zeroing of its registers)
@@ -512,7 +532,8 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         const int sl_ = uni((int)s_slot[wv][below_ ? 0 : gg_]);                                                               \
         const rsrc_t r_ = below_ ? h_zero : (sl_ >= 0 ? h_own : h_b);                                                         \
         const uint32_t so_ = below_ ? 0u : (uint32_t)(sl_ >= 0 ? sl_ : gg_) * 9u * W16;                                       \
-        DST[0] = buf_ld4(r_, l16, so_); DST[1] = buf_ld4(r_, l16, so_ + W16); DST[2] = buf_ld4(r_, l16, so_ + 2u * W16);      \
+        DST[0] = buf_ld4(r_, l16, so_);                                                                                       \
+        if (SS) { DST[1] = buf_ld4(r_, l16, so_ + W16); DST[2] = buf_ld4(r_, l16, so_ + 2u * W16); }                          \
     }
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     // Tail ring slots are relative to gs: group gs+r keeps its xy half in slot r mod 2 and its zw half in slot r mod 3.
@@ -529,7 +550,7 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         if (gs - 3 >= 0) SNES_HLOAD(gs - 3, t3)
     }
 #pragma unroll
-    for (int p = 0; p < 3; p++) {
+    for (int p = 0; p < NPL; p++) {
         const float4 g1 = t1[p], g2 = t2[p], g3 = t3[p];
         ring_xy[(1 * 3 + p) * 256] = make_float2(g1.x, g1.y); ring_zw[(2 * 3 + p) * 256] = make_float2(g1.z, g1.w); // r = -1
         ring_xy[(0 * 3 + p) * 256] = make_float2(g2.x, g2.y); ring_zw[(1 * 3 + p) * 256] = make_float2(g2.z, g2.w); // r = -2
@@ -546,18 +567,21 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         }                                                                                                                     \
         SNES_HLOAD(g + 1, NXT)                                                                                                \
         /* inputs of the maps of row group g-1, consumed after the recurrence steps below (g = 0: group 0's, unused) */        \
-        float4 c_m1, c_sd1, c_a1, c_x;                                                                                        \
-        double2 c_ra, c_rb;                                                                                                   \
+        float4 c_m1 = zero4, c_sd1 = zero4, c_a1 = zero4, c_x = zero4;                                                        \
+        double2 c_ra = make_double2(0.0, 0.0), c_rb = c_ra;                                                                   \
         {                                                                                                                     \
             const int gm = g >= 1 ? g - 1 : 0;                                                                                \
             const uint32_t go = (uint32_t)gm * W16;                                                                           \
-            c_m1 = buf_ld4(m1_b, l16, go); c_sd1 = buf_ld4(sd1_b, l16, go); c_a1 = buf_ld4(a1_b, l16, go);                    \
-            c_ra = buf_ld2d(r1_b, l32, 2u * go); c_rb = buf_ld2d(r1_b, l32 + 16u, 2u * go);                                   \
-            const int sl = uni((int)s_slot[wv][gm]);                                                                          \
-            c_x = buf_ld4(sl >= 0 ? x_own : x_b, l16, (uint32_t)(sl >= 0 ? sl : gm) * 3u * W16);                              \
+            if (SS) { c_m1 = buf_ld4(m1_b, l16, go); c_sd1 = buf_ld4(sd1_b, l16, go); }                                       \
+            if (ED) {                                                                                                         \
+                c_a1 = buf_ld4(a1_b, l16, go);                                                                                \
+                c_ra = buf_ld2d(r1_b, l32, 2u * go); c_rb = buf_ld2d(r1_b, l32 + 16u, 2u * go);                               \
+                const int sl = uni((int)s_slot[wv][gm]);                                                                      \
+                c_x = buf_ld4(sl >= 0 ? x_own : x_b, l16, (uint32_t)(sl >= 0 ? sl : gm) * 3u * W16);                          \
+            }                                                                                                                 \
         }                                                                                                                     \
-        float outp[3][4];                                                                                                     \
-        _Pragma("unroll") for (int p = 0; p < 3; p++) {                                                                       \
+        float outp[3][4] = {};                                                                                                \
+        _Pragma("unroll") for (int p = 0; p < NPL; p++) {                                                                     \
             float2 *pz = ring_zw + (r3 * 3 + p) * 256, *px = ring_xy + (r2 * 3 + p) * 256;                                    \
             const float2 tz = *pz, tx = *px; /* group g-3 second half, g-2 first half */                                      \
             *pz = make_float2(CUR[p].z, CUR[p].w);                                                                            \
@@ -568,13 +592,13 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
             SNES_VSTEP(tx.y + CUR[p].w, sb[p], sa[p], outp[p][3])                                                             \
         }                                                                                                                     \
         /* a1 stays binary32 until the maps: converted where it is loaded, the iteration would open with a wait on memory */  \
-        asm volatile("" : "+v"(c_a1.x), "+v"(c_a1.y), "+v"(c_a1.z), "+v"(c_a1.w));                                            \
+        if (ED) asm volatile("" : "+v"(c_a1.x), "+v"(c_a1.y), "+v"(c_a1.z), "+v"(c_a1.w));                                    \
         if (g >= 1) {                                                                                                         \
             const float m1v[4] = {c_m1.x, c_m1.y, c_m1.z, c_m1.w}, sd1v[4] = {c_sd1.x, c_sd1.y, c_sd1.z, c_sd1.w};              \
             const float a1v[4] = {c_a1.x, c_a1.y, c_a1.z, c_a1.w}, i2v[4] = {c_x.x, c_x.y, c_x.z, c_x.w};                     \
             const double r1v[4] = {c_ra.x, c_ra.y, c_rb.x, c_rb.y};                                                           \
             _Pragma("unroll") for (int q = 0; q < 4; q++)                                                                     \
-                maps_accumulate(acc, m1v[q], sd1v[q], a1v[q], r1v[q], outp[0][q], outp[1][q], outp[2][q], i2v[q]);            \
+                maps_accumulate<MASK>(acc, m1v[q], sd1v[q], a1v[q], r1v[q], outp[0][q], outp[1][q], outp[2][q], i2v[q]);      \
         }                                                                                                                     \
         r2 ^= 1; r3 = r3 == 2 ? 0 : r3 + 1;                                                                                   \
     }
@@ -592,21 +616,47 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
     }
     __syncthreads(); // the tail ring is dead: its space becomes the reduction scratch
 #pragma unroll
-    for (int q = 0; q < 6; q++) red[t][q] = active ? acc[q] : 0.0;
+    for (int q = 0; q < 6; q++) if ((MASK >> q) & 1) red[t][q] = active ? acc[q] : 0.0;
     __syncthreads();
     const int xp = t & (W - 1); // column inside the pair
     for (int stride = W >> 1; stride > 0; stride >>= 1) {
         if (xp < stride) {
 #pragma unroll
-            for (int q = 0; q < 6; q++) red[t][q] += red[t + stride][q];
+            for (int q = 0; q < 6; q++) if ((MASK >> q) & 1) red[t][q] += red[t + stride][q];
         }
         __syncthreads();
     }
     if (xp == 0 && active) {
         double *o = P.part + (((size_t)k * G.nscales + s) * 3 + ch) * 6;
 #pragma unroll
-        for (int q = 0; q < 6; q++) o[q] = red[t][q];
+        for (int q = 0; q < 6; q++) o[q] = ((MASK >> q) & 1) ? red[t][q] : 0.0; // a sum not formed: +0.0, never what the storage held
     }
+}
+// B's sweep: every sum
+__device__ __forceinline__ void sparse_v2_base(const SparseParams &P, const int s, const int bx) {
+    __shared__ V2Shared sh;
+    sparse_v2_body<true, kSumAll>(P, s, bx, sh);
+}
+// The candidates' sweep.  The class is chosen per block, ahead of the body and its barriers: the sums needed by the channels of
+// the block's pairs (one channel but for the two blocks of a scale that straddle a channel boundary when a block holds several
+// pairs), and the smallest instantiated mask that holds them.
+template <int I>
+__device__ __forceinline__ void sparse_v2_class(const SparseParams &P, const int s, const int bx, V2Shared &sh, const int cls) {
+    constexpr bool first = sum_class_is_first(I); // (the table is padded with the full mask: sum_class() returns the first of equals)
+    if (first && cls == I) sparse_v2_body<false, kSumClassesHost.m[I]>(P, s, bx, sh);
+    else if constexpr (I + 1 < kSumClasses) sparse_v2_class<I + 1>(P, s, bx, sh, cls);
+}
+__device__ __forceinline__ void sparse_v2_cand(const SparseParams &P, const int s, const int bx) {
+    __shared__ V2Shared sh;
+    const int ppw = 4 / (P.G.sw[s] >> 6), npairs = P.ncand * 3; // pairs per block
+    if (bx * ppw >= npairs) return;
+    int need = kSumAll;
+    if (!P.full_sums) {
+        const int c0 = (bx * ppw) / P.ncand, c1 = min(bx * ppw + ppw - 1, npairs - 1) / P.ncand;
+        need = 0;
+        for (int c = c0; c <= c1; c++) need |= kSumMasks.m[P.G.nscales][c][s];
+    }
+    sparse_v2_class<0>(P, s, bx, sh, uni(sum_class(need)));
 }
 // ---- B's V sweep with the work of a column split over two waves (round 4) ---------------------------------------------------
 // sparse_v2_body<true> sweeps a single image: 21 waves in all, each alone on its SIMD, 65 dependent group iterations of ~245
@@ -732,14 +782,19 @@ __global__ __launch_bounds__(64) void k_sparse_h2_from(SparseParams P, int list0
 __global__ __launch_bounds__(64) void k_sparse_h2q(SparseParams P) { sparse_h2q_dispatch<false>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); } // short lists
 __global__ __launch_bounds__(64) void k_sparse_h2q_base(SparseParams P) { sparse_h2q_dispatch<true>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); } // B: a single image is a short list
 __global__ __launch_bounds__(64) void k_sparse_h2_base(SparseParams P) { sparse_h2_dispatch<true>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
-__global__ __launch_bounds__(256, 5) void k_sparse_v2(SparseParams P) { if ((int)blockIdx.y < P.G.nscales && P.G.sw[blockIdx.y] >= 64) sparse_v2_body<false>(P, (int)blockIdx.y, (int)blockIdx.x); }
+// The candidates' V kernels read their parameter block in place.  A by-value struct reaches a kernel as a copy in private
+// memory that the optimiser then has to prove away; with the body instantiated per class it no longer does (pointers into the
+// copy meet at the joins of the dispatch), and the kernels took 1 KB of scratch per lane and spilled.  The first argument of a
+// kernel lies at offset 0 of its argument segment, which is constant, wave-uniform memory: scalar loads, as before.
+__device__ __forceinline__ const SparseParams &kernarg_params() { return *(const SparseParams *)__builtin_amdgcn_kernarg_segment_ptr(); }
+__global__ __launch_bounds__(256, 5) void k_sparse_v2(SparseParams) { const SparseParams &P = kernarg_params(); if ((int)blockIdx.y < P.G.nscales && P.G.sw[blockIdx.y] >= 64) sparse_v2_cand(P, (int)blockIdx.y, (int)blockIdx.x); }
 // the wide scales from s0 on (the launch that follows the other scales' H pass when scale 0, whose H pass went ahead, runs beside it)
-__global__ __launch_bounds__(256, 5) void k_sparse_v2_from(SparseParams P, int s0) { const int s = s0 + (int)blockIdx.y; if (s < P.G.nscales && P.G.sw[s] >= 64) sparse_v2_body<false>(P, s, (int)blockIdx.x); }
+__global__ __launch_bounds__(256, 5) void k_sparse_v2_from(SparseParams, int s0) { const SparseParams &P = kernarg_params(); const int s = s0 + (int)blockIdx.y; if (s < P.G.nscales && P.G.sw[s] >= 64) sparse_v2_cand(P, s, (int)blockIdx.x); }
 // B: the wide scales in this body (grid.y = scale), the narrow ones in the general one (grid.y = scale - s_first), two launches:
 // one kernel holding both bodies would take the larger register allocation for every block
 // B, split: grid.x = 64-column block (W / 64 of the widest scale), grid.y = channel, grid.z = scale; 128 threads
 __global__ __launch_bounds__(128) void k_sparse_v2_base_split(SparseParams P) { const int s = (int)blockIdx.z; if (s < P.G.nscales && P.G.sw[s] >= 64 && (int)blockIdx.x < (P.G.sw[s] >> 6)) sparse_v2_base_split_body(P, s, (int)blockIdx.y, (int)blockIdx.x); }
-__global__ __launch_bounds__(256) void k_sparse_v2_base(SparseParams P) { if ((int)blockIdx.y < P.G.nscales && P.G.sw[blockIdx.y] >= 64) sparse_v2_body<true>(P, (int)blockIdx.y, (int)blockIdx.x); }
+__global__ __launch_bounds__(256) void k_sparse_v2_base(SparseParams P) { if ((int)blockIdx.y < P.G.nscales && P.G.sw[blockIdx.y] >= 64) sparse_v2_base(P, (int)blockIdx.y, (int)blockIdx.x); }
 __device__ __forceinline__ void sparse_v_base_narrow_dispatch(const SparseParams &P) { const int s = (int)blockIdx.y + P.s_first; if (s < P.G.nscales) sparse_v_body<false, 0, 1>(P, s); }
 __global__ __launch_bounds__(256, 1) void k_sparse_v_base_narrow(SparseParams P) { sparse_v_base_narrow_dispatch(P); }
 
