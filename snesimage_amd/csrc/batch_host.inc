@@ -106,6 +106,7 @@ int32_t enqueue_batched_scoring(hipStream_t st, const snes::BatchArgs *A, uint32
     if (s_first < G.nscales) hipLaunchKernelGGL(kb_sparse_h, dim3((unsigned)((G.sh[s_first] / 4 * 3 + 15) / 16), (unsigned)((G.nscales - s_first) * kColBuckets), K), dim3(64), 0, bs, A, 1, bdead);
     if (s_first < G.nscales) hipLaunchKernelGGL(kb_sparse_v_base_narrow, dim3(3, (unsigned)(G.nscales - s_first), K), dim3(256), 0, bs, A, bdead);
     if (split) HIPCHK(hipEventRecord(side->narrow, bs));
+    if (c0->sp.debug_poison) hipLaunchKernelGGL(kb_poison_store, dim3(256, 1, K), dim3(256), 0, st, A, dead); // SNES_DEBUG_POISON: ahead of everything the call's candidates write
     hipLaunchKernelGGL(kb_candidate_tables, dim3((n + 63) / 64, 1, K), dim3(64), 0, st, A, dead);
     if (dith && c0->perceptual) { // --dither --perceptual-palettes: as below with the CIEDE2000 kernels
         hipLaunchKernelGGL(kb_candidate_lab, dim3((n + 63) / 64, 1, K), dim3(64), 0, st, A, dead);

@@ -198,6 +198,13 @@ struct snesimage_ctx {
         // The candidates' wide V pass forms only the pooling sums whose weight in the score is not zero (kernels.hpp, kSumMasks;
         // DESIGN 4a).  SNES_WEIGHT_MASK=0: all six of every (channel, scale), on every path — the same errors bit for bit.
         bool weight_mask = true;
+        // At scale 0 the candidates' long H pass leaves out the s22 / s12 planes of the channels whose V class forms no SSIM map
+        // (kernels_sparse2.hpp, sparse_h2_dispatch).  SNES_H_PLANES=0: three planes everywhere, the masked V pass as it is.
+        bool h_planes = true;
+        // SNES_DEBUG_POISON=1 (a debug aid, off by default): every call fills its candidates' storage with 0xFF bytes (binary32
+        // NaNs) before anything of the call writes it, so that a read of a plane the H pass left out shows as a NaN error instead of
+        // hiding behind a stale finite value with a zero weight.
+        bool debug_poison = false;
         bool dedup = true; uint32_t dedup_min = 1024; int *holder = nullptr; bool holder_dirty = false; // holder_dirty: a call failed between marking and reset
         bool enabled = false, side = true; uint32_t min_n = 1; uint32_t cap = 0, lanes = 0; // min_n: shortest list that takes the group-sparse path (SNES_SPARSE_MIN; until round 4: 64 — a channel sweep's 32 candidates, or a rank's share of a 64-candidate call, went the dense way: 0.35 ms against 0.27, 1.7 ms with --perceptual-palettes) // cap = candidates per lane the arrays were sized for
         SparseGeom S{};
@@ -627,6 +634,7 @@ SparseParams sparse_params(snesimage_ctx *c, uint32_t lane) {
     P.ckf = sp.ckf; P.cka = sp.cka; P.part = sp.part; P.first = sp.first; P.ckh = sp.ckh; P.zeros = sp.ckh + sp.zeros_off; P.trash = sp.ckh + sp.zeros_off + 12LL * c->G.W;
     for (P.s_first = 0; P.s_first < c->G.nscales && c->G.sw[P.s_first] >= 64; P.s_first++) {} // first narrow scale
     P.full_sums = sp.weight_mask ? 0 : 1;
+    P.h_planes = (sp.weight_mask && sp.h_planes) ? 1 : 0;
     if (c->dither) {
         const uint32_t l = lane < c->nlanes ? lane : 0;
         P.use_maps = 1; P.sub_size = (int)c->sub_size; P.slot_ci = sp.slot_ci; P.subC4 = c->d_subC4; P.tile_pal = c->d_tile_pal;
@@ -751,6 +759,7 @@ int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, 
     SparseParams P = sparse_params(c, lane);
     P.is_base = 0; P.ncand = (int)nc; P.k0 = (int)(lane * sp.cap);
     if (list0 >= 0) { P.holder = sp.holder; P.list0 = list0; }
+    if (sp.debug_poison) HIPCHK(hipMemsetAsync(sp.store + (size_t)P.k0 * sp.S.cand_stride, 0xff, sizeof(float) * (size_t)sp.S.cand_stride * nc, stream)); // SNES_DEBUG_POISON: ahead of everything the call writes there
     snesimage_ctx::TimingRec tr{}; tr.n = nc;
     if (c->timing) { for (int i = 0; i < 6; i++) HIPCHK(hipEventCreate(&tr.ev[i])); if (c->timing == 1) HIPCHK(hipEventRecord(tr.ev[0], stream)); }
     // (the marking rides on the launch that has a thread per candidate anyway: nothing is added in front of the scan)
@@ -1179,6 +1188,8 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (const char *e = getenv("SNES_SPARSE_MIN")) { int v = atoi(e); if (v >= 1) c->sp.min_n = (uint32_t)v; }
     if (const char *e = getenv("SNES_DEDUP")) c->sp.dedup = atoi(e) != 0;
     if (const char *e = getenv("SNES_WEIGHT_MASK")) c->sp.weight_mask = atoi(e) != 0;
+    if (const char *e = getenv("SNES_H_PLANES")) c->sp.h_planes = atoi(e) != 0;
+    if (const char *e = getenv("SNES_DEBUG_POISON")) c->sp.debug_poison = atoi(e) != 0;
     if (const char *e = getenv("SNES_DEDUP_MIN")) { int v = atoi(e); if (v >= 1) c->sp.dedup_min = (uint32_t)v; }
     Geom &G = c->G;
     G.W = (int)w; G.H = (int)h; G.nscales = 0;

@@ -109,6 +109,13 @@ __device__ __forceinline__ int sum_class(const int need) { // index of the small
     }
     return best;
 }
+// The class of a block of the candidates' wide V pass whose pairs are all of channel ch, and whether that class forms the SSIM
+// map.  Asked of the instantiation the block RUNS, not of the raw mask: a mask without an instantiation of its own is served by
+// a larger one, which may read the s22 / s12 planes although the mask itself has no SSIM sum.  sparse_v2_cand picks its class
+// here and the candidates' H pass decides here which planes of a scale-0 item anything will read (sparse_h2_dispatch): one
+// rule, so the two cannot disagree.
+__device__ __forceinline__ int sum_class_of(const int ns, const int ch, const int s) { return sum_class(kSumMasks.m[ns][ch][s]); }
+__device__ __forceinline__ bool sum_class_has_ssim(const int ns, const int ch, const int s) { return (kSumClassTab.m[sum_class_of(ns, ch, s)] & kSumSsim) != 0; }
 
 // ------------------------------------------------------------------------------------------------
 // Palette tables: per colour index the linear RGB and positive-XYB triple of its 8-bit expansion.

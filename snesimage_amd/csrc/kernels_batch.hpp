@@ -79,6 +79,13 @@ __global__ __launch_bounds__(256) void kb_clear_bitmaps(const BatchArgs *__restr
     const size_t words = (size_t)a.n * (a.npx / 32);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) a.Pc.bitmap[i] = 0u;
 }
+// SNES_DEBUG_POISON (a debug aid): the storage of the call's candidates as binary32 NaNs before the call writes any of it
+__global__ __launch_bounds__(256) void kb_poison_store(const BatchArgs *__restrict__ A, const int *__restrict__ dead) {
+    SNES_BATCH_IMG;
+    uint32_t *w = reinterpret_cast<uint32_t *>(a.Pc.store + (size_t)a.Pc.k0 * a.Pc.S.cand_stride);
+    const size_t words = (size_t)a.Pc.ncand * (size_t)a.Pc.S.cand_stride;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) w[i] = 0xffffffffu;
+}
 __global__ __launch_bounds__(256) void kb_sparse_scan_lab(const BatchArgs *__restrict__ A, const int *__restrict__ dead) { SNES_BATCH_IMG; sparse_scan_lab_body(a.Pc); }
 __global__ __launch_bounds__(64) void kb_sparse_h(const BatchArgs *__restrict__ A, int base, const int *__restrict__ dead) { SNES_BATCH_IMG; sparse_h_body(base ? a.Pb : a.Pc); }
 __global__ __launch_bounds__(64) void kb_sparse_h2(const BatchArgs *__restrict__ A, const int *__restrict__ dead) { SNES_BATCH_XCD; sparse_h2_dispatch<false>(a.Pc, bb.y, bb.x, (int)gridDim.x); }

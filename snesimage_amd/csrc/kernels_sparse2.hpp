@@ -90,12 +90,35 @@ __device__ __forceinline__ void h2_resolve(const SparseParams &P, const uint4 pa
     }
 }
 // BASE: the launch is B's own H pass (every item is B's: no win test, and the block checkpoints are written) / the candidates'
-template <bool S0, bool BASE>
-__device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int list, const int bx, const int gx, H2Shared &sh) {
+//
+// ONE (scale 0 of the candidates only): the one-plane form.  The V class of an item's channel forms no SSIM map
+// (sum_class_has_ssim), so nothing reads the item's s22 and s12 planes: the body runs the mu2 recurrence alone — no img1 fetch,
+// no squares and products, plane 0's checkpoint state only — and stages and stores mu2 and the XYB plane, both bit for bit what
+// the full form writes (the same operations on the same values in the same order).  The storage layout does not change: the
+// other two planes of the item are simply not written.  The flush is re-cut for two planes: a quarter-wave = item, so a store
+// instruction carries the two 128-byte lines of FOUR items (four instructions per 8-column run instead of eight) and no lane
+// of an existing item aims at the scratch line.  The memory pipeline is the full form's.
+// nfree / ord (candidates at scale 0; nfree == 0 elsewhere: the list as written, every wave in this body): the list is read
+// channel-major — with n = count / 3 triples, virtual index q stands for item 3 (q % n) + channel ord[q / n], ord = the nfree
+// SSIM-free channels first (two bits each) — so that the 16 items of a wave are of one class in all but at most two waves of
+// a list.  A wave whose items are all SSIM-free belongs to the ONE instantiation, every other wave to the full one; the
+// dispatch runs both over the list and each skips the other's waves (wave-uniform, decided before any of the body).
+// scale 0's colour table: XYB of the ncol + 2 colour indices, three planes, into the dynamic LDS of the H kernels
+__device__ __forceinline__ void sparse_h2_load_lut(const SparseParams &P, float *s_lut) {
+    const int lstr = P.ncol + 2;
+    for (int i = threadIdx.x; i < 3 * lstr; i += 64) { const int c = i / lstr, j = i - c * lstr; s_lut[i] = P.pal_xyb[3 * j + c]; }
+    lds_order();
+}
+// lut_ready: the caller has loaded the colour table for this wave (the dispatch, which runs two forms over one list)
+template <bool S0, bool BASE, bool ONE = false>
+__device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int list, const int bx, const int gx, H2Shared &sh, const int nfree = 0, const int ord = 0, const bool lut_ready = false) {
+    static_assert(!ONE || (S0 && !BASE), "the one-plane form is the candidates' at scale 0");
     // staged planes: the three H outputs + the XYB input, which the V pass reads in the R4 layout (at scale 0 it is looked up
     // here; at the other scales it is the downscale's output in the C4 layout, and rewriting it from here — whole lines,
     // only from the row's first block on — is cheaper than a second scattered copy from the downscale; B's are written there)
-    constexpr int NP = (S0 || !BASE) ? 4 : 3;
+    constexpr int NP = ONE ? 2 : ((S0 || !BASE) ? 4 : 3);
+    constexpr int NH = ONE ? 1 : 3;       // H planes computed: mu2 | mu2, s22, s12
+    const int nf = (S0 && !BASE) ? nfree : 0;
     constexpr int PW = 32;                // staged floats per plane: 8 columns x 4 rows = one 128-byte line of the XT4 / R4 layouts
     constexpr int ISTR = NP * PW + 4;     // staging words per item; the pad spreads the quads' rows over the LDS banks
     extern __shared__ float s_lut[]; // scale 0: XYB of the ncol + 2 colour indices, three planes (dynamic: 12 (ncol + 2) bytes — the waves a CU holds are what this kernel lives on)
@@ -108,21 +131,23 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
     const int lane = threadIdx.x;
     const int count = P.item_count[list];
     if (bx * 16 >= count) return;
-    if (S0) {
-        for (int i = lane; i < 3 * lstr; i += 64) { const int c = i / lstr, j = i - c * lstr; s_lut[i] = P.pal_xyb[3 * j + c]; }
-        lds_order();
-    }
+    if (S0 && !lut_ready) sparse_h2_load_lut(P, s_lut);
     const float n2_0 = P.K.n2[0], n2_1 = P.K.n2[1], n2_2 = P.K.n2[2];
     const float mp_0 = -P.K.d1[0], mp_1 = -P.K.d1[1], mp_2 = -P.K.d1[2];
     const int G4 = W >> 2, gs = cb << 4; // first quad of the block: a multiple of 16
     const int r = lane & 3;
     const int half = lane >> 5, fl = lane & 31, fp = fl >> 3, fc = fl & 7; // the flush: half-wave = item, lane = (plane, column) of the staged 8-column run
+    const int qtr = lane >> 4, ql = lane & 15;                             // ONE: quarter-wave = item, lane = (mu2 | XYB, column)
+    const int ntri = count / 3;                                            // triples of the list (the scan writes whole triples)
     float *const trash = P.trash + (lane << 2);
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i0 = bx * 16; i0 < count; i0 += gx * 16) { // grid-stride over item quads
+        if (nf > 0 && (((min(i0 + 16, count) - 1) / ntri < nf) != ONE)) continue; // the other form's wave
         const int qi = i0 + (lane >> 2);
         const bool valid = qi < count;
-        const unsigned int it = P.items[(size_t)list * P.item_stride + (valid ? qi : i0)];
+        int ii = valid ? qi : i0;
+        if (nf > 0) { const int c = ii / ntri; ii = 3 * (ii - c * ntri) + ((ord >> (2 * c)) & 3); }
+        const unsigned int it = P.items[(size_t)list * P.item_stride + ii];
         const int k = item_k(it), j = item_j(it), ch = item_ch(it);
         const int y = 4 * item_g(it) + r;
         const size_t ns = (size_t)W * H;
@@ -146,7 +171,7 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
         // B's state on entering the block: ckh[s][ch][block-1][18][row]
         const float *ck = P.ckh + P.S.off_ckh[s] + ((size_t)(ch * 3 + (cb > 0 ? cb - 1 : 0)) * 18) * H + y;
 #pragma unroll
-        for (int p = 0; p < 3; p++)
+        for (int p = 0; p < NH; p++)
 #pragma unroll
             for (int q = 0; q < 3; q++) {
                 sa[p][q] = gs > 0 ? ck[(size_t)(p * 6 + q) * H] : 0.0f;
@@ -161,7 +186,7 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
 #pragma unroll
         for (int a = 0; a < 3; a++) { pa[a] = make_uint4(0, 0, 0, 0); pb[a] = pa[a]; bw[a] = 0u; }
         auto fetch = [&](const int q, float4 &d1, float4 &d2, uint4 &wa, uint4 &wb, uint32_t &wbm) { // every load on every path (0 <= q < G4)
-            d1 = in1[(size_t)q * H];
+            if (!ONE) d1 = in1[(size_t)q * H]; // (img1 feeds s12 alone)
             if (S0) {
                 if (um) { wa.x = mw[(size_t)q * H]; wa.y = sw[(size_t)q * H]; } else { wa = pk[(size_t)q * H * 2]; wb = pk[(size_t)q * H * 2 + 1]; }
                 wbm = bmrow[q >> 3];
@@ -203,17 +228,36 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
             float outp[3][4];                                                                                                 \
             _Pragma("unroll") for (int q = 0; q < 4; q++) {                                                                   \
                 const float s0 = l2[q] + v2[q];                                                                               \
+                if (ONE) {                                                                                                    \
+                    if ((q & 1) == 0) { SNES_HSTEP(s0, sa[0], sb[0], outp[0][q]) } else { SNES_HSTEP(s0, sb[0], sa[0], outp[0][q]) } \
+                } else {                                                                                                      \
                 const float s1 = (l2[q] * l2[q]) + (v2[q] * v2[q]);                                                           \
                 const float s2 = (l1[q] * l2[q]) + (v1[q] * v2[q]);                                                           \
                 if ((q & 1) == 0) { SNES_HSTEP(s0, sa[0], sb[0], outp[0][q]) SNES_HSTEP(s1, sa[1], sb[1], outp[1][q]) SNES_HSTEP(s2, sa[2], sb[2], outp[2][q]) } \
                 else { SNES_HSTEP(s0, sb[0], sa[0], outp[0][q]) SNES_HSTEP(s1, sb[1], sa[1], outp[1][q]) SNES_HSTEP(s2, sb[2], sa[2], outp[2][q]) }             \
+                }                                                                                                             \
             }                                                                                                                 \
             if (STAGE) { /* outputs of quad g-1 (those of quad gs-1 are B's and stay unwritten): stage [plane][column % 8][row] */ \
                 float *so = s_out + (lane >> 2) * ISTR + ((((T) + 1) & 1) << 4) + r; /* (g - 1) & 1: gs is even */            \
-                _Pragma("unroll") for (int p = 0; p < 3; p++) { so[p * PW + 0] = outp[p][0]; so[p * PW + 4] = outp[p][1]; so[p * PW + 8] = outp[p][2]; so[p * PW + 12] = outp[p][3]; } \
-                if (NP == 4) { so[3 * PW + 0] = r2[ul_].x; so[3 * PW + 4] = r2[ul_].y; so[3 * PW + 8] = r2[ul_].z; so[3 * PW + 12] = r2[ul_].w; } \
+                _Pragma("unroll") for (int p = 0; p < NH; p++) { so[p * PW + 0] = outp[p][0]; so[p * PW + 4] = outp[p][1]; so[p * PW + 8] = outp[p][2]; so[p * PW + 12] = outp[p][3]; } \
+                if (NP == NH + 1) { so[NH * PW + 0] = r2[ul_].x; so[NH * PW + 4] = r2[ul_].y; so[NH * PW + 8] = r2[ul_].z; so[NH * PW + 12] = r2[ul_].w; } \
             }                                                                                                                 \
-            if (FLUSH) { /* 8 columns complete: one store instruction per two items = their NP planes as 128-byte lines */    \
+            if ((FLUSH) && ONE) { /* 8 columns complete: one store instruction per FOUR items = mu2's and the XYB plane's 128-byte lines */ \
+                lds_order();                                                                                                  \
+                const uint32_t o_l = (uint32_t)((g - 2) << 4) + (uint32_t)((ql & 7) << 2); /* both planes start at their base */ \
+                float4 fv[4]; long long fb[4];                                                                                \
+                _Pragma("unroll") for (int m = 0; m < 4; m++) {                                                               \
+                    const int im_ = 4 * m + qtr;                                                                              \
+                    fv[m] = *reinterpret_cast<const float4 *>(s_out + im_ * ISTR + ql * 4);                                   \
+                    fb[m] = (ql & 8) ? s_xbase[im_] : s_hbase[im_];                                                           \
+                }                                                                                                             \
+                _Pragma("unroll") for (int m = 0; m < 4; m++) {                                                               \
+                    float *dst = fb[m] >= 0 ? P.store + fb[m] + o_l : trash;                                                  \
+                    *reinterpret_cast<float4 *>(dst) = fv[m];                                                                 \
+                }                                                                                                             \
+                asm volatile("" ::: "memory");                                                                               \
+            }                                                                                                                 \
+            if ((FLUSH) && !ONE) { /* 8 columns complete: one store instruction per two items = their NP planes as 128-byte lines */    \
                 lds_order();                                                                                                  \
                 /* float offset of this lane's 16 bytes behind the item's base: plane fp of the H output (XT4: [x/64][x%64][row] = 4 x */ \
                 /* floats into the plane), or the XYB plane (R4: 4 x as well) */                                              \
@@ -557,6 +601,23 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         ring_zw[(0 * 3 + p) * 256] = make_float2(g3.z, g3.w);                                                       // r = -3
     }
     int r2 = 0, r3 = 0; // (g - gs) mod 2, mod 3: wave-uniform ring slots
+    // The classes without an SSIM map: a group iteration is one short recurrence, and map inputs loaded at its top were awaited
+    // ~40 instructions later.  They fetch the map inputs of row group g during iteration g, one iteration before the maps of
+    // that group (iteration g + 1), into registers these classes have free (no state, tails or buffers of s22 / s12) — as wave M
+    // of sparse_v2_base_split_body does.  Unconditional, the group clamped to the image (SNES_HLOAD); same values, same use.
+    constexpr bool PRE = !BASE && !SS && ED;
+    float4 n_a1 = zero4, n_x = zero4;
+    double2 n_ra = make_double2(0.0, 0.0), n_rb = n_ra;
+#define SNES_V2MLOAD(GM)                                                                                                      \
+    {                                                                                                                         \
+        const int gm_ = (GM);                                                                                                 \
+        const uint32_t go_ = (uint32_t)gm_ * W16;                                                                             \
+        n_a1 = buf_ld4(a1_b, l16, go_);                                                                                       \
+        n_ra = buf_ld2d(r1_b, l32, 2u * go_); n_rb = buf_ld2d(r1_b, l32 + 16u, 2u * go_);                                     \
+        const int sl_ = uni((int)s_slot[wv][gm_]);                                                                            \
+        n_x = buf_ld4(sl_ >= 0 ? x_own : x_b, l16, (uint32_t)(sl_ >= 0 ? sl_ : gm_) * 3u * W16);                              \
+    }
+    if (PRE && gs <= H4) SNES_V2MLOAD(min(max(gs - 1, 0), H4 - 1)) // what iteration gs consumes (g = 0: group 0's, unused)
 #define SNES_V2GROUP(CUR, NXT)                                                                                                \
     {                                                                                                                         \
         if (BASE && active) { /* record g */                                                                                  \
@@ -569,7 +630,8 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         /* inputs of the maps of row group g-1, consumed after the recurrence steps below (g = 0: group 0's, unused) */        \
         float4 c_m1 = zero4, c_sd1 = zero4, c_a1 = zero4, c_x = zero4;                                                        \
         double2 c_ra = make_double2(0.0, 0.0), c_rb = c_ra;                                                                   \
-        {                                                                                                                     \
+        if (PRE) { c_a1 = n_a1; c_ra = n_ra; c_rb = n_rb; c_x = n_x; SNES_V2MLOAD(min(g, H4 - 1)) } /* fetched last iteration; group g's for the next */ \
+        else {                                                                                                                \
             const int gm = g >= 1 ? g - 1 : 0;                                                                                \
             const uint32_t go = (uint32_t)gm * W16;                                                                           \
             if (SS) { c_m1 = buf_ld4(m1_b, l16, go); c_sd1 = buf_ld4(sd1_b, l16, go); }                                       \
@@ -609,6 +671,7 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         SNES_V2GROUP(bufB, bufA)
     }
 #undef SNES_V2GROUP
+#undef SNES_V2MLOAD
 #undef SNES_HLOAD
     if (BASE && active) { // final record (H4 + 1): the pooling sums of the whole column
 #pragma unroll
@@ -650,13 +713,18 @@ __device__ __forceinline__ void sparse_v2_cand(const SparseParams &P, const int 
     __shared__ V2Shared sh;
     const int ppw = 4 / (P.G.sw[s] >> 6), npairs = P.ncand * 3; // pairs per block
     if (bx * ppw >= npairs) return;
-    int need = kSumAll;
-    if (!P.full_sums) {
+    int cls;
+    if (P.full_sums) cls = sum_class(kSumAll);
+    else {
         const int c0 = (bx * ppw) / P.ncand, c1 = min(bx * ppw + ppw - 1, npairs - 1) / P.ncand;
-        need = 0;
-        for (int c = c0; c <= c1; c++) need |= kSumMasks.m[P.G.nscales][c][s];
+        if (c0 == c1) cls = sum_class_of(P.G.nscales, c0, s); // one channel (every block of scale 0): the rule the H pass writes its planes by
+        else {
+            int need = 0;
+            for (int c = c0; c <= c1; c++) need |= kSumMasks.m[P.G.nscales][c][s];
+            cls = sum_class(need);
+        }
     }
-    sparse_v2_class<0>(P, s, bx, sh, uni(sum_class(need)));
+    sparse_v2_class<0>(P, s, bx, sh, uni(cls));
 }
 // ---- B's V sweep with the work of a column split over two waves (round 4) ---------------------------------------------------
 // sparse_v2_body<true> sweeps a single image: 21 waves in all, each alone on its SIMD, 65 dependent group iterations of ~245
@@ -774,7 +842,33 @@ __device__ __forceinline__ void sparse_h2_dispatch(const SparseParams &P, const 
     const int s = list / kColBuckets;
     if (s >= P.G.nscales || P.G.sw[s] < 64 || (list % kColBuckets) >= (P.G.sw[s] >> 6)) return;
     __shared__ H2Shared sh;
-    if (s == 0) sparse_h2_body<true, BASE>(P, list, bx, gx, sh); else sparse_h2_body<false, BASE>(P, list, bx, gx, sh);
+    if (s != 0) { sparse_h2_body<false, BASE>(P, list, bx, gx, sh); return; }
+    // Scale 0 of the candidates: the channels whose V class forms no SSIM map get the one-plane form (sparse_h2_body, ONE).
+    // Scale 0 only: there a V block is exactly one (candidate, channel) (W = 256: four waves, one pair), so the class that
+    // reads an item's planes is its own channel's.  From scale 1 on a block holds several pairs and the two blocks that
+    // straddle a channel boundary run the union of two channels' sums: a union with an SSIM sum would read s22 / s12 of an
+    // SSIM-free channel's items (B at scales 1 and 2 of a 256x128 image), so those scales write every plane.
+    if constexpr (!BASE) {
+        const int count = P.item_count[list];
+        // count % 3: the channel-major read takes the list for whole triples (v, v + 1, v + 2 = channels 0, 1, 2 of one (candidate,
+        // group)).  scan_publish is the only writer of the candidates' lists and writes nothing else; a second writer has to
+        // keep that: this test is a consistency guard, not a proof, and a list of another make with a count that happens to
+        // be a multiple of three would go through the remap unnoticed.
+        if (P.h_planes && !P.full_sums && (P.G.sw[0] >> 6) == 4 && count % 3 == 0) {
+            int nfree = 0, ord = 0, pos = 0;
+            for (int c = 0; c < 3; c++) if (!sum_class_has_ssim(P.G.nscales, c, 0)) { ord |= c << (2 * pos++); nfree++; }
+            for (int c = 0; c < 3; c++) if (sum_class_has_ssim(P.G.nscales, c, 0)) ord |= c << (2 * pos++);
+            if (nfree > 0) {
+                if (bx * 16 >= count) return;
+                extern __shared__ float s_lut[];
+                sparse_h2_load_lut(P, s_lut); // once, for both forms
+                sparse_h2_body<true, false, true>(P, list, bx, gx, sh, nfree, ord, true);
+                sparse_h2_body<true, false, false>(P, list, bx, gx, sh, nfree, ord, true);
+                return;
+            }
+        }
+    }
+    sparse_h2_body<true, BASE>(P, list, bx, gx, sh);
 }
 __global__ __launch_bounds__(64) void k_sparse_h2(SparseParams P) { sparse_h2_dispatch<false>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
 // the lists from list0 on (the launch that follows the downscale when scale 0's lists, which do not read it, went ahead beside it)
