@@ -829,6 +829,34 @@ int32_t snesimage_set_guided_proxy(snesimage_ctx *ctx, uint32_t proxy);
 int32_t snesimage_get_guided_proxy(snesimage_ctx *ctx, uint32_t *proxy);
 int32_t snesimage_shared_set_guided_proxy(snesimage_shared *set, uint32_t proxy);
 int32_t snesimage_shared_get_guided_proxy(snesimage_shared *set, uint32_t *proxy);
+/* GUIDED CALLS OF A SET THROUGH THE SLOT WINDOWS (DESIGN 5f'''').  n_calls guided set calls of shortlist k (1..64, 0 = 16) from
+ * slot (*palette, *index) on, in the order of snesimage_shared_guided_sweep: index is the inner loop, palette the outer; on a
+ * backdrop set the tied slot (sub_count, 0) comes last; behind the last slot comes (0, 0) again.  On return *palette, *index name
+ * the slot behind the last call that took effect.  Equivalent, bit for bit and for every `window`, to
+ * snesimage_shared_guided_step_async per call: every member's palette, map and incumbent, the set's record
+ * (snesimage_shared_last_step) and every log[j] with its error's bits.
+ *   A rejected guided set call changes nothing that a shortlist or a score reads, so a guided window is a window of
+ *   snesimage_shared_run_slots whose candidate lists are shortlists: the next calls in slot order, scored by every member against
+ *   the palette as it stands in one set of launches, committed once on the joint error in order (best := E, strict <, ascending
+ *   k); what lies behind the first acceptance runs again in the next window.  One window is in flight at a time: voided stays 0.
+ *   THE WINDOW'S GENERATOR does not repeat a subpalette's work for each of its entries.  For a pixel x of subpalette p, over the
+ *   entries of the (expanded) subpalette: a(x) = the lowest key, j*(x) = the first entry that reaches it, b(x) = the lowest key
+ *   over j != j*(x) (0xFFFFFFFF with one entry).  The floor of slot (p, i) is b(x) where j*(x) == i, else a(x), so
+ *     A_p(u) = sum over p's population of min(a, key(x, u)),
+ *     D_{p,i}(u) = sum over the pixels with j* == i of min(b, key(x, u)) - min(a, key(x, u)),    cost_{p,i}(u) = A_p(u) + D_{p,i}(u)
+ *   in integers and exactly: A once per subpalette and window, D once per call over the pixels whose nearest entry is the call's.
+ *   The tables and the shortlists equal those of snesimage_shared_guided_costs / _candidates bit for bit.
+ *   window: 0 = adaptive, 1 = call by call, otherwise that many calls per launch set, at most SNES_WINDOW_MAX / F.  The adaptive
+ *   size is kept apart from that of snesimage_shared_run_slots: a guided run between two scheduled runs changes neither the launch
+ *   sets nor the stats of those.  stats and log (both optional) as snesimage_guided_run_slots fills them.
+ *   Stepped call by call inside the function: the tied slot (a window ends in front of it), window = 1, a set of more than
+ *   SNES_WINDOW_MAX / 2 members, members whose maps are not optimize() of the palette, and a set whose proxy is SNES_GUIDE_CIELAB.
+ *   The generator's workspace (per call of SNES_WINDOW_MAX / F: 16 bytes x 64 per tile of the set and a table; per subpalette of a
+ *   window: 8 bytes x 64 per tile and a table) is allocated by the first guided window and freed with the set, all or nothing.
+ *   Refusals: those of snesimage_shared_guided_step and of snesimage_shared_run_slots; SNES_ERR_HIP for a failed workspace
+ *   allocation.  A refusal leaves the set as it was and usable. */
+int32_t snesimage_shared_guided_run_slots(snesimage_shared *set, uint32_t n_calls, uint32_t k, uint32_t *palette, uint32_t *index, uint32_t window,
+                                          snesimage_call_result *log, snesimage_run_stats *stats);
 int32_t snesimage_get_palette_map(snesimage_ctx *ctx, uint8_t *out /*w*h*/);
 int32_t snesimage_set_palette_map(snesimage_ctx *ctx, const uint8_t *in);
 int32_t snesimage_as_rgba(snesimage_ctx *ctx, uint8_t *out /*w*h*4; lib.rs:550-577*/);
@@ -877,6 +905,14 @@ void snesimage_debug_poison_alloc(int32_t on);
  * a null context or a buffer that is too short). */
 int32_t snesimage_debug_guided_capture(snesimage_ctx *ctx, int32_t on);
 int32_t snesimage_debug_guided_shortlists(snesimage_ctx *ctx, uint8_t *rgb5, uint32_t cap, uint32_t *n_calls, uint32_t *k);
+/* The same two hooks for snesimage_shared_guided_run_slots: the lists the members' scorers read, for every call that took effect. */
+int32_t snesimage_shared_debug_guided_capture(snesimage_shared *set, int32_t on);
+int32_t snesimage_shared_debug_guided_shortlists(snesimage_shared *set, uint8_t *rgb5, uint32_t cap, uint32_t *n_calls, uint32_t *k);
+/* Test hook: the tables of the guided windows' generator.  Runs the generator of one window whose calls are the n given slots
+ * (1 <= n <= SNES_WINDOW_MAX / F; regular slots; a slot may repeat) without scoring or committing anything and returns each
+ * call's final table, costs[j * 32768 + u] = A + D of call j.  The state is left unchanged.  SNES_ERR_ARG for a null pointer, a
+ * slot out of range, the tied slot or a bad n; SNES_ERR_UNSUPPORTED under SNES_GUIDE_CIELAB and where the guided set calls are. */
+int32_t snesimage_shared_debug_guided_window_costs(snesimage_shared *set, const uint32_t *palettes, const uint32_t *indices, uint32_t n, uint64_t *costs /* n*32768 */);
 /* Launch timing by the library's own HIP events on the stream each launch group runs on (bench.py's roofline leg).
  * While enabled, every scoring launch group records events; timing_read() returns summed milliseconds:
  *   ms3[0] = the whole launch group (all kernels that score one chunk of candidates);

@@ -174,6 +174,7 @@ SIGNATURES = [
     ("snesimage_shared_guided_step", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _f64p, _u8p]),
     ("snesimage_shared_guided_step_async", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("snesimage_shared_guided_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
+    ("snesimage_shared_guided_run_slots", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p, _u32p, C.c_uint32, C.POINTER(CallResult), C.POINTER(RunStats)]),
     ("snesimage_set_guided_proxy", C.c_int32, [C.c_void_p, C.c_uint32]),
     ("snesimage_get_guided_proxy", C.c_int32, [C.c_void_p, _u32p]),
     ("snesimage_shared_set_guided_proxy", C.c_int32, [C.c_void_p, C.c_uint32]),
@@ -190,6 +191,9 @@ SIGNATURES = [
     ("snesimage_debug_poison_alloc", None, [C.c_int32]),
     ("snesimage_debug_guided_capture", C.c_int32, [C.c_void_p, C.c_int32]),
     ("snesimage_debug_guided_shortlists", C.c_int32, [C.c_void_p, _u8p, C.c_uint32, _u32p, _u32p]),
+    ("snesimage_shared_debug_guided_capture", C.c_int32, [C.c_void_p, C.c_int32]),
+    ("snesimage_shared_debug_guided_shortlists", C.c_int32, [C.c_void_p, _u8p, C.c_uint32, _u32p, _u32p]),
+    ("snesimage_shared_debug_guided_window_costs", C.c_int32, [C.c_void_p, _u32p, _u32p, C.c_uint32, _u64p]),
     ("snesimage_timing_enable", C.c_int32, [C.c_void_p, C.c_int32]),
     ("snesimage_timing_read", C.c_int32, [C.c_void_p, _f64p, _u64p, _u64p]),
     ("snesimage_last_error", C.c_char_p, []),

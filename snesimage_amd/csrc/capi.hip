@@ -15,6 +15,7 @@
 #include "kernels_guide.hpp"
 #include "kernels_guide_lab.hpp"
 #include "kernels_guide_window.hpp"
+#include "kernels_guide_set_window.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1772,3 +1773,4 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "guide_host.inc"
 #include "shared_guide_host.inc"
 #include "guided_window_host.inc"
+#include "shared_guided_window_host.inc"

@@ -40,7 +40,7 @@
 // --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_run_slots, --window calls per launch set): on every
 // slot the --guided-shortlist K colours an integer proxy ranks best among all 32,768 are scored, and the error decides.
 // --guided-proxy / --set-guided-proxy redmean|cielab choose the proxy's distance (snesimage_set_guided_proxy; DESIGN 5f'').
-// --set-guided G (with --share) does the same for a set (snesimage_shared_guided_sweep): the proxy runs over the tiles of all
+// --set-guided G (with --share) does the same for a set (snesimage_shared_guided_run_slots): the proxy runs over the tiles of all
 // frames, every frame scores the --set-guided-shortlist K colours, and the set's error decides.
 // The host language the north star asks for is Rust; no Rust toolchain exists in this image, so the
 // driver is C++ over the same extern "C" surface a Rust crate would bind.
@@ -145,7 +145,8 @@ void usage() {
             "      --set-guided <G>     with --share: behind every G sweeps of the palette, one guided sweep of the set: the colours are ranked\n"
             "                           over the tiles of all frames, every frame scores the --set-guided-shortlist best, and the set's error\n"
             "                           decides; runs in front of --reassign-tiles, --tile-moves and --set-tile-dither; with\n"
-            "                           --set-backdrop-fixed the backdrop slot is passed by; not with --devices or --nes\n"
+            "                           --set-backdrop-fixed the backdrop slot is passed by; not with --devices or --nes.  The calls of a guided\n"
+            "                           sweep of the set go through the launch sets of --window (same result for every --window)\n"
             "      --set-guided-shortlist <K>  colours scored per guided call of the set, 1..64 [default: 16: a choice, not a measurement];\n"
             "                           needs --set-guided\n"
             "      --set-guided-proxy <PROXY>  the same choice for the guided sweeps of the set: redmean or cielab [default: redmean];\n"
@@ -170,7 +171,8 @@ void usage() {
             "                           with --devices\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
-            "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only\n"
+            "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only;\n"
+            "                           with --set-guided any --window: at most that many calls per launch set\n"
             "      --decode-only        write the decoded source as raw RGBA8 to <TARGET_FILENAME> and stop (no GPU)\n  -h, --help\n  -V, --version\n");
 }
 // the flat integer array stored under `"key":[...]` in one of this driver's (or the reference's) JSON outputs
@@ -487,7 +489,7 @@ int main(int argc, char **argv) {
         flags |= SNES_BACKDROP;
     }
     if (!shares.empty()) { // a set runs on one device, from the k-means initialisers (a backdrop set also from --resume); its windows are sized by the library (--window 0) or off (--window 1)
-        const char *bad = (!resume_file.empty() && !set_bd) ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 ? "'--window' other than 0 or 1" : nullptr);
+        const char *bad = (!resume_file.empty() && !set_bd) ? "'--resume'" : !devices.empty() ? "'--devices'" : !tile_file.empty() ? "'--tile-palettes'" : (window > 1 && !sgd.given ? "'--window' other than 0 or 1" : nullptr); // (with --set-guided the launch sets take at most --window calls)
         if (bad) { fprintf(stderr, "error: the argument '--share <SOURCE=TARGET>' cannot be used with %s\n", bad); return 2; }
     }
     if (ordered_given || amp_given) { // said before any device is touched
@@ -821,14 +823,9 @@ int main(int argc, char **argv) {
         snesimage_run_stats gs{};
         double e0 = 0.0, e1 = 0.0;
         if (snesimage_shared_error(set, &e0) != 0) die(what + snesimage_last_error());
-        if (bd_fixed) {
-            for (uint32_t p = 0; p < count; p++)
-                for (uint32_t ix = 0; ix < size; ix++) {
-                    snesimage_call_result r{};
-                    if (snesimage_shared_guided_step_async(set, p, ix, sgd.shortlist) != 0 || snesimage_shared_last_step(set, &r) != 0) die(what + snesimage_last_error());
-                    gs.calls += 1; gs.accepted += r.best_k >= 0 ? 1u : 0u;
-                }
-        } else if (snesimage_shared_guided_sweep(set, sgd.shortlist, nullptr, &gs) != 0) die(what + snesimage_last_error());
+        // through the set's slot windows, --window calls per launch set (1: call by call; the same result); count * size calls from (0, 0) end in front of the backdrop slot
+        uint32_t gp = 0, gi = 0;
+        if (snesimage_shared_guided_run_slots(set, count * size + (set_bd && !bd_fixed ? 1u : 0u), sgd.shortlist, &gp, &gi, window, nullptr, &gs) != 0) die(what + snesimage_last_error());
         if (snesimage_shared_error(set, &e1) != 0) die(what + snesimage_last_error());
         log_info("Guided sweep of the set: " + std::to_string(gs.calls) + " calls, " + std::to_string(gs.accepted) + " accepted (" + sgd.proxy_name() + "); error " + fmt_f64(e0) + " -> " + fmt_f64(e1));
         if (std::abs(e1 - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e1)); last_error = e1; }

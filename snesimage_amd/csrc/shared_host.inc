@@ -21,6 +21,7 @@ struct snesimage_shared {
     snesimage_sharedlevel *lvl = nullptr;     // the tied level calls of the set, made on first use
     snesimage_guidework *guide = nullptr;     // the guided calls of the set, made on first use
     uint32_t guide_proxy = 0;                 // snesimage_shared_set_guided_proxy: the set's own, the members' are neither read nor written
+    bool guide_capture = false; std::vector<uint8_t> guide_captured; uint32_t guide_captured_k = 0; // snesimage_shared_debug_guided_capture: the last run's shortlists (shared_guided_window_host.inc)
     bool reduced = false;                     // snesimage_shared_reduce_characters left merged maps: stored maps that are no optimize() of the palette
     // a backdrop set (snesimage_shared_create_backdrop; DESIGN §5c''): every member is a SNES_BACKDROP context and holds the set's B
     bool backdrop = false;

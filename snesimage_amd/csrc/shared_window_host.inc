@@ -21,12 +21,28 @@ struct snesimage_shared_window {
     hipStream_t side = nullptr; bool use_side = true;
     uint32_t adapt = 0;                // next window's size when the caller leaves it to the library (0: not yet chosen)
     WindowPolicy policy;
+    // guided windows (shared_guided_window_host.inc) size themselves: a guided run between two scheduled runs leaves the launch sets of those as they were
+    uint32_t g_adapt = 0; WindowPolicy g_policy;
+    struct snesimage_sharedguidewin *g_work = nullptr; // ... and their generator's workspace, made by the first guided window
+};
+
+// A window whose calls are not the scheduler's (WindowGen for a set): the caller of shared_window_run names the slot order and
+// writes the candidate lists itself.  next: the slot behind (*palette, *index); generate: n candidates for each of the window's K
+// calls (r.h_slots / r.d_slots: their slots) into r.d_cand and the first K * n errors preset to +inf, on the set's stream, where
+// kw_gen_candidates runs.
+struct SharedWindowGen {
+    uint32_t n;
+    void (*next)(const snesimage_ctx *c0, uint32_t *palette, uint32_t *index);
+    int32_t (*generate)(snesimage_shared *s, WindowRec &r, uint32_t K, uint32_t n);
 };
 
 namespace {
 
+void shared_guided_window_free(snesimage_sharedguidewin *g);
+
 void shared_window_free(snesimage_shared_window *w) {
     if (!w) return;
+    shared_guided_window_free(w->g_work);
     for (auto &m : w->child) for (auto *k : m) window_release_child(k);
     if (w->side) { (void)hipStreamSynchronize(w->side); (void)hipStreamDestroy(w->side); }
     window_rec_free(w->rec);
@@ -99,8 +115,10 @@ int32_t shared_window_prepare(snesimage_shared *s) {
 
 // One window: at most n_slots calls from the scheduler state on, cut where the method changes; scored, committed, its
 // result awaited.  *taken calls were scored, *used of them took effect, the last of them changed the palette if *acc.
+// gen: the calls are the next n_slots slots of the caller's order instead, each of gen->n candidates that gen->generate writes;
+// they are committed by the random method's rule.
 int32_t shared_window_run(snesimage_shared *s, uint32_t n_slots, uint64_t seed, uint64_t first_step_id, uint32_t palette, uint32_t index, uint32_t channel, uint32_t step, uint32_t n_random,
-                          snesimage_call_result *log, uint32_t *taken, uint32_t *stride, uint32_t *used, uint32_t *acc) {
+                          snesimage_call_result *log, uint32_t *taken, uint32_t *stride, uint32_t *used, uint32_t *acc, const SharedWindowGen *gen = nullptr) {
     auto &M = members(s);
     snesimage_ctx *c0 = M[0];
     const uint32_t F = (uint32_t)M.size();
@@ -110,11 +128,12 @@ int32_t shared_window_run(snesimage_shared *s, uint32_t n_slots, uint64_t seed, 
       while (K < n_slots) {
           const uint32_t cp = p, ci = i, cc = ch;
           if (s->backdrop && cp == c0->sub_count) break; // a window ends in front of a backdrop call (snesimage_shared_run_slots steps it on its own)
+          if (gen) { gen->next(c0, &p, &i); calls[K++] = Call{SNES_METHOD_RANDOM, cp, ci, 0u}; continue; } // the caller's slot order
           ctx_schedule_next(c0, c0->nes ? 1 : 0, &p, &i, &ch, &st, &m); // (a backdrop set: snesimage_schedule_next_backdrop)
           if (K == 0) m0 = m; else if (m != m0) break;
           calls[K++] = Call{m, cp, ci, cc};
       } }
-    const uint32_t method = calls[0].method, n = method_count(method, n_random);
+    const uint32_t method = calls[0].method, n = gen ? gen->n : method_count(method, n_random);
     if (n > 64) return fail(SNES_ERR_ARG, "a slot window holds at most 64 candidates per call");
     // groups: a call, or the consecutive channel calls of one entry behind one base image (window_enqueue's merge rule)
     struct Group { uint32_t j0, len; } groups[snes::kMaxWindow];
@@ -153,7 +172,8 @@ int32_t shared_window_run(snesimage_shared *s, uint32_t n_slots, uint64_t seed, 
         }
     }
     HIPCHK(hipMemcpyAsync(r.d_blob, r.h_blob, args_off + sizeof(snes::BatchArgs) * (size_t)F * G, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kw_gen_candidates, dim3((n + 63) / 64, K), dim3(64), 0, st, r.d_slots, c0->d_colors, r.d_cand, r.d_errs, (int)n, (const int *)w->d_dead, 1);
+    if (gen) CHECK(gen->generate(s, r, K, n)); // the caller's lists in the random candidates' place
+    else hipLaunchKernelGGL(kw_gen_candidates, dim3((n + 63) / 64, K), dim3(64), 0, st, r.d_slots, c0->d_colors, r.d_cand, r.d_errs, (int)n, (const int *)w->d_dead, 1);
     BatchSide bs{w->use_side ? w->side : nullptr, r.ev[0], r.ev[1], r.ev[2], r.ev[3], false};
     CHECK(enqueue_batched_scoring(st, r.d_args, F * G, n_max, w->child[0][0], &bs, nullptr));
     hipLaunchKernelGGL(ksw_commit, dim3(1), dim3(1024), 0, st, r.d_slots, (int)K, (int)n, (int)F, (int)G, r.d_args, r.d_errs, r.d_cand, s->d_joint, r.d_res, r.d_log);

@@ -199,6 +199,40 @@ class SharedPalette:
         out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log]
         return out, {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
+    def guided_run_slots(self, n_calls, k=0, state=(0, 0), window=0, want_log=True):
+        """n_calls guided set calls of shortlist k from slot state = (palette, index) on, in the guided sweep's slot order (behind
+        the last slot the first again), several calls per launch set (snesimage_shared_guided_run_slots): bit-identical to
+        `guided_step` per call for every `window` (0 = adaptive, 1 = call by call, K = at most K calls per launch set).
+        Returns (log, state, stats) shaped like `run_slots`."""
+        st = [C.c_uint32(int(v)) for v in state]
+        log = (_ffi.CallResult * n_calls)() if want_log else None
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_shared_guided_run_slots(self._s, int(n_calls), int(k), C.byref(st[0]), C.byref(st[1]), int(window), log, C.byref(stats)))
+        out = [(r.error, r.best_k, np.array(r.rgb5[:], np.uint8), int(r.changed)) for r in log] if want_log else None
+        return out, tuple(v.value for v in st), {k_: getattr(stats, k_) for k_ in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
+    def debug_guided_capture(self, on=True):
+        """Test hook: keep the shortlists that the calls of `guided_run_slots` score (snesimage_shared_debug_guided_capture)."""
+        self._chk(self._L.snesimage_shared_debug_guided_capture(self._s, 1 if on else 0))
+
+    def debug_guided_shortlists(self):
+        """Test hook: the shortlists of the last captured run -> rgb5[n_calls, k, 3], in call order."""
+        n, k = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.snesimage_shared_debug_guided_shortlists(self._s, None, 0, C.byref(n), C.byref(k)))
+        out = np.zeros((n.value, k.value, 3), np.uint8)
+        if out.size:
+            self._chk(self._L.snesimage_shared_debug_guided_shortlists(self._s, _p(out, _ffi._u8p), out.size, C.byref(n), C.byref(k)))
+        return out
+
+    def debug_guided_window_costs(self, slots):
+        """Test hook: the tables of the guided windows' generator for one window whose calls are `slots`, a list of (palette,
+        index), nothing scored or committed -> uint64[n, 32768], row j the final table of call j."""
+        sl = np.ascontiguousarray(slots, np.uint32).reshape(-1, 2)
+        p, i = np.ascontiguousarray(sl[:, 0]), np.ascontiguousarray(sl[:, 1])
+        out = np.zeros((max(len(sl), 1), 32768), np.uint64)
+        self._chk(self._L.snesimage_shared_debug_guided_window_costs(self._s, _p(p, _ffi._u32p), _p(i, _ffi._u32p), len(sl), _p(out, _ffi._u64p)))
+        return out[:len(sl)]
+
     @property
     def guided_proxy(self):
         """The metric of the set's guided cost table: "redmean" (the default) or "cielab".  The set's own setting: the
