@@ -518,6 +518,52 @@ int32_t snesimage_shared_reduce_characters(snesimage_shared *set, uint32_t max_u
  * lists of F lists, in member order. */
 int64_t snesimage_shared_as_tilemap_json(snesimage_shared *set, char *out, int64_t cap);
 
+/* Native export — NOT a reference method.  The result as the console loads it: a CGRAM image, bitplane character data (CHR) and
+ * tilemap words (MAP), and a renderer that reads such bytes back as the PPU's background fetch does.  Off unless called; no other
+ * entry point changes.  Terms are those of the character budget above: CHARACTER, FLIP, rep, flip_of, U, classes ordered by
+ * representative.  S is the user's sub_size (in a backdrop context the user's size, not the expanded one), C is sub_count.
+ *   DEPTH: bpp = 0 picks the smallest of 2 (S <= 3), 4 (S <= 15) and 8.  An explicit depth must hold S, S <= (1 << bpp) - 1, else
+ *     SNES_ERR_ARG.  8bpp requires C == 1 and palette_base == 0 — the 8bpp tilemap word's palette bits do not select among
+ *     256-colour palettes — else SNES_ERR_UNSUPPORTED, the message names the geometry.  2bpp and 4bpp require
+ *     palette_base + C <= 8, else SNES_ERR_ARG.
+ *   CGRAM: 512 bytes, 256 little-endian words r | g << 5 | b << 10, the words snesimage_get_palette_u16 returns.  Row p starts at
+ *     word (palette_base + p) << bpp for 2bpp and 4bpp and at word 0 for 8bpp; entry i of row p sits at the row's start + 1 + i.
+ *     The word at each row's start, and word 0 of CGRAM, hold B in a backdrop context and 0 otherwise — what snesimage_as_json
+ *     writes into slot 0 of every row.  Every other word is 0.  At 4bpp with palette_base 0 CGRAM is therefore the JSON's
+ *     `palette` rows concatenated and zero-padded.
+ *   CHR: U characters in class order — the order of "characters" in the tilemap JSON — each in its representative's orientation,
+ *     8 * bpp bytes.  For plane pair k (planes 2k and 2k + 1) and row y, byte 16k + 2y is plane 2k of row y and byte 16k + 2y + 1
+ *     plane 2k + 1; bit 7 - x of a plane byte is that plane's bit of the character value at (x, y).  The values are the
+ *     CHARACTER values (0 for a transparent or backdrop pixel, map + 1 otherwise); the depth condition makes them fit.
+ *   MAP: ntile little-endian words in tile order t = ty * 32 + tx — the picture is 32 tiles wide, so this is the top h/8 rows
+ *     of one 32 x 32 screen.  word = (char_base + pos(rep(t))) | (palette_base + tile_palettes[t]) << 10 | priority << 13 |
+ *     hflip << 14 | vflip << 15, pos(r) the position of r's class in CHR, hflip and vflip bits 0 and 1 of flip_of(t); the
+ *     palette field is 0 at 8bpp.  char_base + U <= 1024 is required, else SNES_ERR_ARG with a message that states U and names
+ *     the character budget calls.
+ * snesimage_export_native produces all three pieces from one state; every output is optional, a call with none only fills
+ * `info`.  chr_cap < chr_bytes with chr given is SNES_ERR_ARG.  It works as snesimage_characters does (an optimize() still owed
+ * is run first) and leaves the state unchanged bit for bit: map, error, epoch.  Refusals are those of snesimage_characters plus
+ * the ones above; a refusal leaves the context usable.
+ * snesimage_shared_export_native counts classes over all members (global representative order: ONE CHR for the set) and writes
+ * one map per member, member-major.  A backdrop set answers SNES_ERR_UNSUPPORTED as snesimage_shared_as_tilemap_json does, more
+ * than 8,192 tiles in all as the set's character calls do.
+ * snesimage_render_native decodes cgram, chr and map under the same layout into w*h RGBA: per pixel the tilemap word, the flips,
+ * the plane bytes, the index; index 0 reads CGRAM word 0, any other the row's start + index (8bpp: the index itself); 5 -> 8 bits
+ * as v * 8 + v / 4; alpha 255.  It reads the context's width, height, device and stream and nothing of its palette or map (bpp = 0
+ * resolves from the context's S), so it judges bytes from anywhere, on a lent context too.  Inputs are checked before any
+ * launch: a null pointer, chr_bytes that is not 1..1024 whole characters, or a map word whose character number lies below
+ * char_base or beyond chr_bytes is SNES_ERR_ARG.
+ * Out of scope: backdrop sets, 8bpp with several subpalettes, widths other than 256, more than one 32 x 32 screen, compression,
+ * and a reader of native files. */
+typedef struct { uint8_t bpp /*0 = auto, 2, 4, 8*/, palette_base /*0..7*/, priority /*0, 1*/, pad; uint16_t char_base /*0..1023*/, pad2; } snesimage_native_layout; /* 8 bytes; NULL = all zero */
+typedef struct { uint32_t bpp, unique, chr_bytes, map_words; } snesimage_native_info;
+int32_t snesimage_export_native(snesimage_ctx *ctx, const snesimage_native_layout *layout, uint8_t *cgram /*512, opt*/, uint8_t *chr /*opt*/, uint64_t chr_cap,
+                                uint16_t *map /*ntile, opt*/, snesimage_native_info *info /*opt*/);
+int32_t snesimage_shared_export_native(snesimage_shared *set, const snesimage_native_layout *layout, uint8_t *cgram, uint8_t *chr, uint64_t chr_cap,
+                                       uint16_t *maps /*F * ntile, member-major, opt*/, snesimage_native_info *info);
+int32_t snesimage_render_native(snesimage_ctx *ctx, const snesimage_native_layout *layout, const uint8_t *cgram /*512*/, const uint8_t *chr, uint64_t chr_bytes,
+                                const uint16_t *map /*ntile*/, uint8_t *rgba /*w*h*4*/);
+
 /* The refit of shared characters across the members of a shared-palette set — NOT a reference method.  After a set merge a
  * character that serves tiles of several frames still carries the indices chosen for one donor tile of one frame.  This is the
  * refit above over the whole set: each shared character fitted to ALL the tiles of ALL members that use it, decided on the joint

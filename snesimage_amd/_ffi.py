@@ -60,6 +60,16 @@ class SharedRefitResult(C.Structure):
                 ("scored", C.c_uint8)]
 
 
+class NativeLayout(C.Structure):
+    """snesimage_native_layout: depth and bases of a native export (all zero: auto depth, bases 0)."""
+    _fields_ = [("bpp", C.c_uint8), ("palette_base", C.c_uint8), ("priority", C.c_uint8), ("pad", C.c_uint8), ("char_base", C.c_uint16), ("pad2", C.c_uint16)]
+
+
+class NativeInfo(C.Structure):
+    """snesimage_native_info: what a native export produced."""
+    _fields_ = [("bpp", C.c_uint32), ("unique", C.c_uint32), ("chr_bytes", C.c_uint32), ("map_words", C.c_uint32)]
+
+
 # every symbol include/snesimage_hip.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("snesimage_create", C.c_int32, [_u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
@@ -90,6 +100,9 @@ SIGNATURES = [
     ("snesimage_shared_score_merges", C.c_int32, [C.c_void_p, _u16p, _u16p, _u16p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
     ("snesimage_shared_reduce_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(SharedMergeResult), C.c_uint32, _u32p, _u32p]),
     ("snesimage_shared_as_tilemap_json", C.c_int64, [C.c_void_p, C.c_char_p, C.c_int64]),
+    ("snesimage_export_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, C.POINTER(NativeInfo)]),
+    ("snesimage_shared_export_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, C.POINTER(NativeInfo)]),
+    ("snesimage_render_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, _u8p]),
     ("snesimage_shared_character_fits", C.c_int32, [C.c_void_p, _u16p, _u16p, _u64p, _u8p, _u32p]),
     ("snesimage_shared_score_refits", C.c_int32, [C.c_void_p, _u16p, C.c_uint32, _f64p, _f64p, _u8p]),
     ("snesimage_shared_refit_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(SharedRefitResult), C.c_uint32, _u32p, _u32p, _u32p, C.POINTER(RunStats)]),

@@ -79,6 +79,25 @@ def schedule(sub_count, sub_size, n_calls, nes=False, backdrop=False):
     return out
 
 
+def _native_layout(bpp, char_base, palette_base, priority):
+    """snesimage_native_layout of the keyword arguments; the library judges the values, this only keeps them from wrapping."""
+    bpp, char_base, palette_base, priority = int(bpp), int(char_base), int(palette_base), int(priority)
+    if not (0 <= bpp <= 255 and 0 <= palette_base <= 255 and 0 <= priority <= 255 and 0 <= char_base <= 65535):
+        raise ValueError("native layout: bpp, palette_base and priority are bytes, char_base a 16-bit word")
+    return _ffi.NativeLayout(bpp, palette_base, priority, 0, char_base, 0)
+
+
+def _export_native(owner, call, handle, ntile, frames, bpp, char_base, palette_base, priority):
+    """export_native of an image (frames None) or a set (frames = F): sizes first, then the three pieces in one call."""
+    layout = _native_layout(bpp, char_base, palette_base, priority)
+    info = _ffi.NativeInfo()
+    owner._chk(call(handle, C.byref(layout), None, None, 0, None, C.byref(info)))
+    cgram, chr_ = np.zeros(512, np.uint8), np.zeros(max(int(info.chr_bytes), 1), np.uint8)
+    words = np.zeros(ntile if frames is None else (frames, ntile), np.uint16)
+    owner._chk(call(handle, C.byref(layout), _p(cgram, _ffi._u8p), _p(chr_, _ffi._u8p), chr_.size, _p(words, _ffi._u16p), C.byref(info)))
+    return {"cgram": cgram.tobytes(), "chr": chr_[:info.chr_bytes].tobytes(), "map": words, "bpp": int(info.bpp), "unique": int(info.unique)}
+
+
 class OptimizedImage:
     """`OptimizedImage::new(source, palette_count, palette_size, dither, perceptual_palettes, nes)`.
 
@@ -288,6 +307,28 @@ class OptimizedImage:
         buf = C.create_string_buffer(int(need))
         self._L.snesimage_as_tilemap_json(self._c, buf, need)
         return buf.value.decode()
+
+    # -- the native export (not in the reference; include/snesimage_hip.h) ------------------------------------------
+    def export_native(self, bpp=0, char_base=0, palette_base=0, priority=0):
+        """The image as the console loads it (include/snesimage_hip.h, "Native export"): a dict of `cgram` (512 bytes), `chr`
+        (unique * 8 * bpp bytes of bitplane characters, class order), `map` (uint16[ntile] tilemap words), `bpp` (the depth,
+        resolved if 0 was given) and `unique`.  The state is left unchanged."""
+        return _export_native(self, self._L.snesimage_export_native, self._c, (self.w // 8) * (self.h // 8), None, bpp, char_base, palette_base, priority)
+
+    def render_native(self, cgram, chr, map, bpp=0, char_base=0, palette_base=0, priority=0):
+        """Decode native bytes as the PPU's background fetch does -> uint8[h, w, 4], alpha 255.  Reads nothing of this
+        image's palette or map: only its size, device and stream."""
+        ntile = (self.w // 8) * (self.h // 8)
+        cg = np.frombuffer(bytes(cgram), np.uint8)
+        ch = np.frombuffer(bytes(chr), np.uint8)
+        mp = np.ascontiguousarray(map, np.uint16).reshape(-1)
+        if cg.size != 512 or mp.size != ntile:
+            raise ValueError("render_native: cgram is 512 bytes and map holds one word per tile")
+        layout = _native_layout(bpp, char_base, palette_base, priority)
+        out = np.zeros((self.h, self.w, 4), np.uint8)
+        self._chk(self._L.snesimage_render_native(self._c, C.byref(layout), _p(cg, _ffi._u8p), _p(ch, _ffi._u8p) if ch.size else None, ch.size, _p(mp, _ffi._u16p),
+                                                  _p(out, _ffi._u8p)))
+        return out
 
     def score_candidates(self, palette, index, rgb5):
         """Loop body of lib.rs:205-220 for an explicit candidate list -> errors (float64)."""

@@ -35,6 +35,10 @@
 // --max-set-tiles N (with --share) is the budget of the whole set: the frames share one VRAM character area, so their characters
 // are counted together and a tile may take its indices from a tile of another frame (snesimage_shared_reduce_characters);
 // --set-tilemap FILE writes the set's characters and one tilemap per frame (snesimage_shared_as_tilemap_json).
+// --export-cgram / --export-chr / --export-map FILE write the result as the console loads it (snesimage_export_native), the
+// --set-export- trio that of a --share set (snesimage_shared_export_native); --export-bpp, --export-char-base,
+// --export-palette-base and --export-priority lay it out.  The bytes are rendered back (snesimage_render_native) and compared
+// with as_rgba() before a file is written.
 // --refit-set-tiles N (with --share) runs up to N refit sweeps over the whole set behind that (snesimage_shared_refit_characters):
 // every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
 // --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_run_slots, --window calls per launch set): on every
@@ -169,6 +173,18 @@ void usage() {
             "                           every character shared across the frames to all the tiles using it and keep a refit where the\n"
             "                           set's error falls (one frame's error may rise); stops after a sweep that accepts nothing; not\n"
             "                           with --devices\n"
+            "      --export-cgram <F>, --export-chr <F>, --export-map <F>\n"
+            "                           write the result as the console loads it (any subset): the 512-byte CGRAM image, the distinct\n"
+            "                           characters as bitplane data and the tilemap words of one 32-tile-wide screen; the bytes are\n"
+            "                           rendered back and compared with the result before anything is written; not with --share or --devices\n"
+            "      --set-export-cgram <F>, --set-export-chr <F>, --set-export-map <F>\n"
+            "                           with --share: the same for the set: one CGRAM, one character area for all frames, and the frames'\n"
+            "                           tilemaps one after another in member order; not with --devices or --set-backdrop(-fixed)\n"
+            "      --export-bpp <2|4|8> depth of the exported characters [default: the smallest that holds the subpalette size]; 8 needs one\n"
+            "                           subpalette; needs an export file\n"
+            "      --export-char-base <N>  number of the first exported character in the tilemap words, 0..1023 [default: 0]\n"
+            "      --export-palette-base <N>  CGRAM palette of subpalette 0, 0..7 [default: 0]\n"
+            "      --export-priority <0|1>  priority bit of every tilemap word [default: 0]\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
             "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only;\n"
@@ -356,6 +372,11 @@ int main(int argc, char **argv) {
     uint32_t level_every = 0, dither_levels = 4; bool level_given = false, dither_levels_given = false; std::string level_arg, dither_levels_arg, levels_out_file, levels_in_file;
     uint32_t set_level_every = 0; bool set_level_given = false, set_mode_given = false, set_tied = true; std::string set_level_arg, set_mode_arg, set_levels_out_file, set_levels_in_file;
     GuidedFlags gd, sgd; // --guided*, --set-guided*
+    std::string export_file[3], set_export_file[3]; // --export-cgram / -chr / -map and their --set- kin
+    struct { const char *name, *shown; bool given; std::string arg; unsigned long lo, hi, value; } export_opt[4] = { // the layout of whichever family is present
+        {"--export-bpp", "--export-bpp <2|4|8>", false, "", 2, 8, 0}, {"--export-char-base", "--export-char-base <N>", false, "", 0, 1023, 0},
+        {"--export-palette-base", "--export-palette-base <N>", false, "", 0, 7, 0}, {"--export-priority", "--export-priority <0|1>", false, "", 0, 1, 0}};
+    static const char *const kExportName[3] = {"--export-cgram", "--export-chr", "--export-map"}, *const kSetExportName[3] = {"--set-export-cgram", "--set-export-chr", "--set-export-map"};
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](const char *name) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "error: a value is required for '%s'\n", name); exit(2); } return argv[++i]; };
@@ -402,6 +423,11 @@ int main(int argc, char **argv) {
         else if (a == "--max-set-tiles") { max_set_given = true; max_set_arg = need("--max-set-tiles"); }
         else if (a == "--set-tilemap") set_tilemap_file = need("--set-tilemap");
         else if (a == "--refit-set-tiles") { refit_set_given = true; refit_set_arg = need("--refit-set-tiles"); }
+        else if (a == "--export-cgram" || a == "--export-chr" || a == "--export-map") { for (int k = 0; k < 3; k++) if (a == kExportName[k]) export_file[k] = need(kExportName[k]); }
+        else if (a == "--set-export-cgram" || a == "--set-export-chr" || a == "--set-export-map") { for (int k = 0; k < 3; k++) if (a == kSetExportName[k]) set_export_file[k] = need(kSetExportName[k]); }
+        else if (a == "--export-bpp" || a == "--export-char-base" || a == "--export-palette-base" || a == "--export-priority") {
+            for (auto &o : export_opt) if (a == o.name) { o.given = true; o.arg = need(o.name); }
+        }
         else if (a == "--share") {
             const std::string v = need("--share");
             const size_t eq = v.find('=');
@@ -467,6 +493,32 @@ int main(int argc, char **argv) {
         const unsigned long n = strtoul(refit_set_arg.c_str(), &end, 10);
         if (refit_set_arg.empty() || refit_set_arg[0] == '-' || *end || n < 1 || n > 16) { fprintf(stderr, "error: invalid value '%s' for '--refit-set-tiles <N>': expected 1..16\n", refit_set_arg.c_str()); return 2; }
         refit_set_sweeps = (uint32_t)n;
+    }
+    int export_first = -1, set_export_first = -1; // the first export file of each family that was given
+    for (int k = 2; k >= 0; k--) { if (!export_file[k].empty()) export_first = k; if (!set_export_file[k].empty()) set_export_first = k; }
+    { // the native export: said before any file or device is touched
+        if (export_first >= 0) {
+            const char *bad = !shares.empty() ? "'--share'" : (!devices.empty() ? "'--devices'" : nullptr); // characters are counted in one image on one device
+            if (bad) { fprintf(stderr, "error: the argument '%s <F>' cannot be used with %s\n", kExportName[export_first], bad); return 2; }
+        }
+        if (set_export_first >= 0) {
+            const char *opt = kSetExportName[set_export_first];
+            if (shares.empty()) { fprintf(stderr, "error: '%s <F>' needs '--share <SOURCE=TARGET>': it exports the characters of a set (one image: --export-cgram, --export-chr, --export-map)\n", opt); return 2; }
+            const char *bad = !devices.empty() ? "'--devices'" : set_backdrop ? "'--set-backdrop'" : set_backdrop_fixed ? "'--set-backdrop-fixed'" : nullptr; // a backdrop set has no character calls yet
+            if (bad) { fprintf(stderr, "error: the argument '%s <F>' cannot be used with %s\n", opt, bad); return 2; }
+        }
+        for (auto &o : export_opt) {
+            if (!o.given) continue;
+            if (export_first < 0 && set_export_first < 0) { fprintf(stderr, "error: '%s' needs an export file: '--export-cgram', '--export-chr', '--export-map' or, with --share, their '--set-export-' kin\n", o.shown); return 2; }
+            char *end = nullptr;
+            o.value = strtoul(o.arg.c_str(), &end, 10);
+            const bool is_bpp = std::string(o.name) == "--export-bpp";
+            if (o.arg.empty() || o.arg[0] == '-' || *end || o.value < o.lo || o.value > o.hi || (is_bpp && o.value != 2 && o.value != 4 && o.value != 8)) {
+                if (is_bpp) fprintf(stderr, "error: invalid value '%s' for '%s': expected 2, 4 or 8\n", o.arg.c_str(), o.shown);
+                else fprintf(stderr, "error: invalid value '%s' for '%s': expected %lu..%lu\n", o.arg.c_str(), o.shown, o.lo, o.hi);
+                return 2;
+            }
+        }
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
@@ -1008,6 +1060,47 @@ int main(int argc, char **argv) {
         fwrite(json.data(), 1, (size_t)need - 1, f);
         fclose(f);
         log_info("Wrote the set's tilemap to " + set_tilemap_file);
+    }
+    // The native export, where the tilemap is written.  The bytes are first rendered as the PPU's background fetch reads them
+    // (snesimage_render_native) and compared with as_rgba(): equal RGB wherever the source is opaque, CGRAM word 0 elsewhere.
+    // A difference is an internal error, and no export file is written.
+    if (export_first >= 0 || set_export_first >= 0) {
+        const bool of_set = set_export_first >= 0;
+        snesimage_native_layout lay{};
+        lay.bpp = (uint8_t)export_opt[0].value; lay.char_base = (uint16_t)export_opt[1].value; lay.palette_base = (uint8_t)export_opt[2].value; lay.priority = (uint8_t)export_opt[3].value;
+        snesimage_native_info ni{};
+        if ((of_set ? snesimage_shared_export_native(set, &lay, nullptr, nullptr, 0, nullptr, &ni) : snesimage_export_native(ctx, &lay, nullptr, nullptr, 0, nullptr, &ni)) != 0)
+            die(std::string("Unable to export native data: ") + snesimage_last_error());
+        std::vector<uint8_t> cgram(512), chr(ni.chr_bytes);
+        std::vector<uint16_t> words(ni.map_words);
+        if ((of_set ? snesimage_shared_export_native(set, &lay, cgram.data(), chr.data(), chr.size(), words.data(), &ni)
+                    : snesimage_export_native(ctx, &lay, cgram.data(), chr.data(), chr.size(), words.data(), &ni)) != 0 || ni.chr_bytes != chr.size() || ni.map_words != words.size())
+            die(std::string("Unable to export native data: ") + snesimage_last_error());
+        lay.bpp = (uint8_t)ni.bpp; // the depth the export chose
+        const uint32_t ntile = 32 * (h / 8), c0 = (uint32_t)cgram[0] | ((uint32_t)cgram[1] << 8);
+        const uint8_t zero[3] = {(uint8_t)((c0 & 31) * 8 + (c0 & 31) / 4), (uint8_t)(((c0 >> 5) & 31) * 8 + ((c0 >> 5) & 31) / 4), (uint8_t)(((c0 >> 10) & 31) * 8 + ((c0 >> 10) & 31) / 4)};
+        std::vector<uint8_t> drawn((size_t)w * h * 4), want((size_t)w * h * 4);
+        for (size_t m = 0; m < (of_set ? frames.size() : (size_t)1); m++) {
+            if (snesimage_render_native(frames[m], &lay, cgram.data(), chr.data(), chr.size(), words.data() + m * ntile, drawn.data()) != 0 || snesimage_as_rgba(frames[m], want.data()) != 0)
+                die(std::string("Unable to check the native export: ") + snesimage_last_error());
+            for (size_t px = 0; px < (size_t)w * h; px++) {
+                const uint8_t *d = &drawn[4 * px], *e = want[4 * px + 3] ? &want[4 * px] : zero; // (as_rgba leaves alpha 0 exactly where the source does)
+                if (d[0] != e[0] || d[1] != e[1] || d[2] != e[2] || d[3] != 255)
+                    die("internal error: the native export of frame " + std::to_string(m) + " does not render as the result at pixel (" + std::to_string(px % w) + ", " + std::to_string(px / w) + "); nothing was exported");
+            }
+        }
+        const std::string *files = of_set ? set_export_file : export_file;
+        const void *data[3] = {cgram.data(), chr.data(), words.data()};
+        const size_t bytes[3] = {cgram.size(), chr.size(), words.size() * sizeof(uint16_t)}; // (the words are little-endian as the host is)
+        for (int k = 0; k < 3; k++) {
+            if (files[k].empty()) continue;
+            FILE *f = fopen(files[k].c_str(), "wb");
+            if (!f) die("cannot create " + files[k]);
+            fwrite(data[k], 1, bytes[k], f);
+            fclose(f);
+        }
+        log_info(std::string("Wrote native data") + (of_set ? " of the set: " : ": ") + std::to_string(ni.bpp) + "bpp, " + std::to_string(ni.unique) + " characters at " + std::to_string(lay.char_base) + ", " +
+                 std::to_string(ni.map_words) + " tilemap words");
     }
     if (!preview_file.empty()) { // left: source, right: as_rgba() of the result (src/lib.rs:940-957)
         std::vector<uint8_t> result((size_t)w * h * 4), both((size_t)2 * w * h * 4), png;

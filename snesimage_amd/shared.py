@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .api import GUIDED_PROXIES, METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _p
+from .api import GUIDED_PROXIES, METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _export_native, _p
 
 
 SHARED_MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("member_error", np.float64), ("cost", np.uint64), ("member", np.uint16), ("tile", np.uint16),
@@ -397,6 +397,11 @@ class SharedPalette:
         buf = C.create_string_buffer(int(need))
         self._L.snesimage_shared_as_tilemap_json(self._s, buf, need)
         return buf.value.decode()
+
+    def export_native(self, bpp=0, char_base=0, palette_base=0, priority=0):
+        """The set as the console loads it (include/snesimage_hip.h, "Native export"): as OptimizedImage.export_native, with
+        ONE `chr` for all members (classes counted over the whole set) and `map` of shape [F, ntile], member order."""
+        return _export_native(self, self._L.snesimage_shared_export_native, self._s, self._ntile(), len(self.images), bpp, char_base, palette_base, priority)
 
     # -- state ------------------------------------------------------------------------------------
     @property
