@@ -553,8 +553,8 @@ int64_t snesimage_shared_as_tilemap_json(snesimage_shared *set, char *out, int64
  * resolves from the context's S), so it judges bytes from anywhere, on a lent context too.  Inputs are checked before any
  * launch: a null pointer, chr_bytes that is not 1..1024 whole characters, or a map word whose character number lies below
  * char_base or beyond chr_bytes is SNES_ERR_ARG.
- * Out of scope: backdrop sets, 8bpp with several subpalettes, widths other than 256, more than one 32 x 32 screen, compression,
- * and a reader of native files. */
+ * Out of scope: backdrop sets, 8bpp with several subpalettes, widths other than 256, more than one 32 x 32 screen and compression.
+ * Native files are read back by the native import below. */
 typedef struct { uint8_t bpp /*0 = auto, 2, 4, 8*/, palette_base /*0..7*/, priority /*0, 1*/, pad; uint16_t char_base /*0..1023*/, pad2; } snesimage_native_layout; /* 8 bytes; NULL = all zero */
 typedef struct { uint32_t bpp, unique, chr_bytes, map_words; } snesimage_native_info;
 int32_t snesimage_export_native(snesimage_ctx *ctx, const snesimage_native_layout *layout, uint8_t *cgram /*512, opt*/, uint8_t *chr /*opt*/, uint64_t chr_cap,
@@ -563,6 +563,59 @@ int32_t snesimage_shared_export_native(snesimage_shared *set, const snesimage_na
                                        uint16_t *maps /*F * ntile, member-major, opt*/, snesimage_native_info *info);
 int32_t snesimage_render_native(snesimage_ctx *ctx, const snesimage_native_layout *layout, const uint8_t *cgram /*512*/, const uint8_t *chr, uint64_t chr_bytes,
                                 const uint16_t *map /*ntile*/, uint8_t *rgba /*w*h*4*/);
+
+/* Native import — NOT a reference method.  The inverse of the native export: CGRAM, CHR and MAP bytes — the export's own, or
+ * bytes ripped from a ROM or drawn in a tile editor — decoded into the STATE of a context of the same picture: palette, backdrop
+ * colour, tile_palettes and a stored palette_map.  Off unless called; no other entry point changes.  The terms are the export's:
+ * S is the user's sub_size, C is sub_count, and `layout` is resolved and refused exactly as the export resolves and refuses it
+ * for (S, C): the depth (0 = the smallest that holds S), S <= (1 << bpp) - 1, 8bpp only with C == 1 and palette_base 0,
+ * palette_base + C <= 8.  `priority` is not read.  chr_bytes must be 1..1024 whole cells of 8 * bpp bytes, else SNES_ERR_ARG.
+ *   PER TILE t, with the word w = map[t]:
+ *     the character number n = w & 1023 must satisfy char_base <= n < char_base + chr_bytes / (8 * bpp);
+ *     the palette field p = (w >> 10) & 7: at 2bpp and 4bpp tile_palettes[t] = p - palette_base, which must lie in 0..C-1; at 8bpp
+ *     the field is ignored and the subpalette is 0;
+ *     the priority bit (13) is ignored; bits 14 and 15 are the horizontal and the vertical flip.
+ *   PER PIXEL (x, y) of tile t the value v is decoded exactly as snesimage_render_native decodes it: the flips first (cell column
+ *     7 - x under hflip, cell row 7 - y under vflip), then the plane bytes of cell n - char_base in the export's CHR layout.
+ *       v >= 1: the map value is v - 1, which must be < S;
+ *       v == 0 where the source alpha is 0: accepted; the stored map value there is 0, and nothing observable reads it (as_json,
+ *         as_rgba, the characters and error() treat such a pixel as transparent);
+ *       v == 0 where the source alpha is not 0: in a SNES_BACKDROP context the map value S (the tied entry: the backdrop colour
+ *         shows); in any other context refused — the message says to create the context with SNES_BACKDROP;
+ *       v != 0 where the source alpha is 0: refused; the library has no way to draw it.
+ *   CGRAM: entry i of row p is word ((palette_base + p) << bpp) + 1 + i (8bpp: word 1 + i) as raw 5-bit r, g, b; bit 15 is
+ *     dropped.  A backdrop context takes B from word 0 and only from word 0: the rows' first words are not read, as the hardware
+ *     does not read them for a background.  Words the geometry does not name are not read either: foreign files need not be zero
+ *     there.  On a SNES_NES context the colours are taken as they are, not snapped to the NES table; the setters do the same.
+ *   DUPLICATES: duplicate, unused and differently ordered cells are all fine.  The import is per tile.
+ *   ALL OR NOTHING: everything is decoded into staging buffers on the context's stream and a verdict read back after one
+ *     synchronisation; only then are palette, tile_palettes (entries [0, ntile); the rest of the 1,024 stay) and map copied into
+ *     the context.  A refusal under PER TILE or PER PIXEL is SNES_ERR_ARG; its message names the LOWEST offending tile and that
+ *     tile's reason (of several reasons in one tile the first in the order: number below char_base, number past the cells,
+ *     palette field, value above S, 0 on an opaque pixel, colour on a transparent pixel; a tile whose number is refused is not
+ *     decoded further).  A refusal leaves palette, tile_palettes, map, incumbent error, epoch and a pending optimize() exactly as
+ *     they were.
+ *   STATE AFTERWARDS: as after snesimage_set_palette_rgb5, snesimage_set_backdrop_rgb5, snesimage_set_tile_palettes and
+ *     snesimage_set_palette_map with the decoded values, in one step: a stored map whose error is unknown; a pending optimize()
+ *     is dropped, as snesimage_set_palette_map drops it; tables, packs and the incumbent are invalid and the epoch has advanced.
+ *     Whatever re-runs optimize() replaces the map, as with any stored map; the character budget, the refit, the tilemap, the
+ *     export and snesimage_error read it as it stands.  An ordered-dither table or level bank stays set.
+ * Refusals beyond those above are those of snesimage_characters (a null context, between the phases of a split-phase step or
+ * window, a context lent to a batch, a set or a group) and null pointers.  info (optional): bpp, unique = the number of cells in
+ * chr, chr_bytes and map_words.
+ * snesimage_shared_import_native does the same for a set: ONE palette, written to every member; each member's tile_palettes and
+ * stored map come from its slice of `maps` (member-major, as snesimage_shared_export_native writes them); the lowest offending
+ * tile is the lowest GLOBAL tile and the message names its member.  All or nothing over the whole set: one verdict for all
+ * members before any member is touched.  Afterwards the set is as an accepted snesimage_shared_reduce_characters leaves it: the
+ * members carry stored maps, the set has recorded their epochs and stays intact, and it remembers that it holds merged maps, so
+ * every set call that optimizes re-runs optimize() first; E is unknown until snesimage_shared_error.  A backdrop set answers
+ * SNES_ERR_UNSUPPORTED as snesimage_shared_export_native does, a retired set or a member changed outside SNES_ERR_STATE, more than
+ * 8,192 tiles in all SNES_ERR_UNSUPPORTED as the set's character calls do.
+ * Out of scope: backdrop sets, widths other than 256, more than one 32 x 32 screen, compression. */
+int32_t snesimage_import_native(snesimage_ctx *ctx, const snesimage_native_layout *layout, const uint8_t *cgram /*512*/, const uint8_t *chr, uint64_t chr_bytes,
+                                const uint16_t *map /*ntile*/, snesimage_native_info *info /*opt*/);
+int32_t snesimage_shared_import_native(snesimage_shared *set, const snesimage_native_layout *layout, const uint8_t *cgram /*512*/, const uint8_t *chr, uint64_t chr_bytes,
+                                       const uint16_t *maps /*F * ntile, member-major*/, snesimage_native_info *info /*opt*/);
 
 /* The refit of shared characters across the members of a shared-palette set — NOT a reference method.  After a set merge a
  * character that serves tiles of several frames still carries the indices chosen for one donor tile of one frame.  This is the

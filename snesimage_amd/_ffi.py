@@ -103,6 +103,8 @@ SIGNATURES = [
     ("snesimage_export_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, C.POINTER(NativeInfo)]),
     ("snesimage_shared_export_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, C.POINTER(NativeInfo)]),
     ("snesimage_render_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, _u8p]),
+    ("snesimage_import_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, C.POINTER(NativeInfo)]),
+    ("snesimage_shared_import_native", C.c_int32, [C.c_void_p, C.POINTER(NativeLayout), _u8p, _u8p, C.c_uint64, _u16p, C.POINTER(NativeInfo)]),
     ("snesimage_shared_character_fits", C.c_int32, [C.c_void_p, _u16p, _u16p, _u64p, _u8p, _u32p]),
     ("snesimage_shared_score_refits", C.c_int32, [C.c_void_p, _u16p, C.c_uint32, _f64p, _f64p, _u8p]),
     ("snesimage_shared_refit_characters", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(SharedRefitResult), C.c_uint32, _u32p, _u32p, _u32p, C.POINTER(RunStats)]),

@@ -98,6 +98,19 @@ def _export_native(owner, call, handle, ntile, frames, bpp, char_base, palette_b
     return {"cgram": cgram.tobytes(), "chr": chr_[:info.chr_bytes].tobytes(), "map": words, "bpp": int(info.bpp), "unique": int(info.unique)}
 
 
+def _import_native(owner, call, handle, ntile, frames, cgram, chr, map, bpp, char_base, palette_base):
+    """import_native of an image (frames None) or a set (frames = F): what export_native returned, in one call."""
+    cg = np.frombuffer(bytes(cgram), np.uint8) if isinstance(cgram, (bytes, bytearray, memoryview)) else np.ascontiguousarray(cgram, np.uint8).reshape(-1)
+    ch = np.frombuffer(bytes(chr), np.uint8) if isinstance(chr, (bytes, bytearray, memoryview)) else np.ascontiguousarray(chr, np.uint8).reshape(-1)
+    mp = np.ascontiguousarray(map, np.uint16).reshape(-1)
+    if cg.size != 512 or mp.size != ntile * (1 if frames is None else frames):
+        raise ValueError("import_native: cgram is 512 bytes and map holds one word per tile" + ("" if frames is None else " of every member"))
+    layout = _native_layout(bpp, char_base, palette_base, 0)
+    info = _ffi.NativeInfo()
+    owner._chk(call(handle, C.byref(layout), _p(cg, _ffi._u8p), _p(ch, _ffi._u8p) if ch.size else None, ch.size, _p(mp, _ffi._u16p), C.byref(info)))
+    return {"bpp": int(info.bpp), "unique": int(info.unique), "chr_bytes": int(info.chr_bytes), "map_words": int(info.map_words)}
+
+
 class OptimizedImage:
     """`OptimizedImage::new(source, palette_count, palette_size, dither, perceptual_palettes, nes)`.
 
@@ -329,6 +342,12 @@ class OptimizedImage:
         self._chk(self._L.snesimage_render_native(self._c, C.byref(layout), _p(cg, _ffi._u8p), _p(ch, _ffi._u8p) if ch.size else None, ch.size, _p(mp, _ffi._u16p),
                                                   _p(out, _ffi._u8p)))
         return out
+
+    def import_native(self, cgram, chr, map, bpp=0, char_base=0, palette_base=0):
+        """Load native bytes as this image's state (include/snesimage_hip.h, "Native import"): palette, backdrop, tile_palettes
+        and a stored palette_map, all or nothing.  Takes what `export_native()` returns (bytes or uint8 arrays; `map` as
+        uint16[ntile]) or bytes from anywhere.  Returns a dict of `bpp`, `unique` (the cells in chr), `chr_bytes`, `map_words`."""
+        return _import_native(self, self._L.snesimage_import_native, self._c, (self.w // 8) * (self.h // 8), None, cgram, chr, map, bpp, char_base, palette_base)
 
     def score_candidates(self, palette, index, rgb5):
         """Loop body of lib.rs:205-220 for an explicit candidate list -> errors (float64)."""

@@ -13,6 +13,7 @@
 #include "kernels_char.hpp"
 #include "kernels_char_set.hpp"
 #include "kernels_export.hpp"
+#include "kernels_import.hpp"
 #include "kernels_guide.hpp"
 #include "kernels_guide_lab.hpp"
 #include "kernels_guide_window.hpp"
@@ -1768,6 +1769,7 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "char_host.inc"
 #include "shared_char_host.inc"
 #include "export_host.inc"
+#include "import_host.inc"
 #include "shared_refit_host.inc"
 #include "ordered_host.inc"
 #include "level_host.inc"

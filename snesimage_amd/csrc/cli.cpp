@@ -39,6 +39,11 @@
 // --set-export- trio that of a --share set (snesimage_shared_export_native); --export-bpp, --export-char-base,
 // --export-palette-base and --export-priority lay it out.  The bytes are rendered back (snesimage_render_native) and compared
 // with as_rgba() before a file is written.
+// --import-cgram / --import-chr / --import-map FILE (all three) start the run from native data instead of the k-means initialisers
+// (snesimage_import_native): the export's own files, or bytes from a ROM or a tile editor; --import-bpp, --import-char-base and
+// --import-palette-base describe them, apart from the --export- options, so a run can read one layout and write another.  The
+// --set-import- trio does the same for a --share set (snesimage_shared_import_native).  With --calls 0 the imported state is what is
+// written, after --max-tiles / --refit-tiles (--max-set-tiles / --refit-set-tiles) if they are given.
 // --refit-set-tiles N (with --share) runs up to N refit sweeps over the whole set behind that (snesimage_shared_refit_characters):
 // every character shared by tiles of whichever frames is refitted to all of them, and kept where the set's error falls.
 // --guided G runs, behind every G sweeps of the palette, one guided sweep (include/snesimage_hip.h: snesimage_guided_run_slots, --window calls per launch set): on every
@@ -185,6 +190,23 @@ void usage() {
             "      --export-char-base <N>  number of the first exported character in the tilemap words, 0..1023 [default: 0]\n"
             "      --export-palette-base <N>  CGRAM palette of subpalette 0, 0..7 [default: 0]\n"
             "      --export-priority <0|1>  priority bit of every tilemap word [default: 0]\n"
+            "      --import-cgram <F>, --import-chr <F>, --import-map <F>\n"
+            "                           start from native data instead of the k-means initialisers (all three are required): a 512-byte\n"
+            "                           CGRAM image, bitplane characters and one tilemap word per tile, as the --export- options write\n"
+            "                           them or as ripped from a ROM; the library refuses data the picture cannot hold and names the\n"
+            "                           first such tile.  With --calls 0 the imported state itself is written (JSON, --preview, --tilemap,\n"
+            "                           the --export- files), after --max-tiles and --refit-tiles if given: a reduced result can be\n"
+            "                           reduced further.  With --calls N > 0 the first call's optimize() replaces the imported map, as it\n"
+            "                           replaces every stored map: palette and tile palettes are what such a run continues from.  With\n"
+            "                           --backdrop the backdrop colour is CGRAM word 0.  Not with --resume, --tile-palettes, --devices,\n"
+            "                           --share or --backdrop-fixed\n"
+            "      --set-import-cgram <F>, --set-import-chr <F>, --set-import-map <F>\n"
+            "                           with --share: the same for the set: one CGRAM, one character area, and the frames' tilemaps one\n"
+            "                           after another as --set-export-map writes them; not with --devices, --set-backdrop(-fixed) or --resume\n"
+            "      --import-bpp <2|4|8> depth of the imported characters [default: the smallest that holds the subpalette size]; needs the\n"
+            "                           import files\n"
+            "      --import-char-base <N>  number of the first imported character in the tilemap words, 0..1023 [default: 0]\n"
+            "      --import-palette-base <N>  CGRAM palette of subpalette 0 in the imported data, 0..7 [default: 0]\n"
             "      --share <S=T>        optimize one palette for the source and image S together (repeatable); S is decoded like the\n"
             "                           source and must have its size; its JSON goes to T, with the same palette as <TARGET_FILENAME>;\n"
             "                           --window 0 (several calls per launch set, sized by the library) or 1 (call by call) only;\n"
@@ -376,6 +398,11 @@ int main(int argc, char **argv) {
     struct { const char *name, *shown; bool given; std::string arg; unsigned long lo, hi, value; } export_opt[4] = { // the layout of whichever family is present
         {"--export-bpp", "--export-bpp <2|4|8>", false, "", 2, 8, 0}, {"--export-char-base", "--export-char-base <N>", false, "", 0, 1023, 0},
         {"--export-palette-base", "--export-palette-base <N>", false, "", 0, 7, 0}, {"--export-priority", "--export-priority <0|1>", false, "", 0, 1, 0}};
+    std::string import_file[3], set_import_file[3]; // --import-cgram / -chr / -map and their --set- kin
+    struct { const char *name, *shown; bool given; std::string arg; unsigned long lo, hi, value; } import_opt[3] = { // what the imported files are laid out as
+        {"--import-bpp", "--import-bpp <2|4|8>", false, "", 2, 8, 0}, {"--import-char-base", "--import-char-base <N>", false, "", 0, 1023, 0},
+        {"--import-palette-base", "--import-palette-base <N>", false, "", 0, 7, 0}};
+    static const char *const kImportName[3] = {"--import-cgram", "--import-chr", "--import-map"}, *const kSetImportName[3] = {"--set-import-cgram", "--set-import-chr", "--set-import-map"};
     static const char *const kExportName[3] = {"--export-cgram", "--export-chr", "--export-map"}, *const kSetExportName[3] = {"--set-export-cgram", "--set-export-chr", "--set-export-map"};
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -427,6 +454,11 @@ int main(int argc, char **argv) {
         else if (a == "--set-export-cgram" || a == "--set-export-chr" || a == "--set-export-map") { for (int k = 0; k < 3; k++) if (a == kSetExportName[k]) set_export_file[k] = need(kSetExportName[k]); }
         else if (a == "--export-bpp" || a == "--export-char-base" || a == "--export-palette-base" || a == "--export-priority") {
             for (auto &o : export_opt) if (a == o.name) { o.given = true; o.arg = need(o.name); }
+        }
+        else if (a == "--import-cgram" || a == "--import-chr" || a == "--import-map") { for (int k = 0; k < 3; k++) if (a == kImportName[k]) import_file[k] = need(kImportName[k]); }
+        else if (a == "--set-import-cgram" || a == "--set-import-chr" || a == "--set-import-map") { for (int k = 0; k < 3; k++) if (a == kSetImportName[k]) set_import_file[k] = need(kSetImportName[k]); }
+        else if (a == "--import-bpp" || a == "--import-char-base" || a == "--import-palette-base") {
+            for (auto &o : import_opt) if (a == o.name) { o.given = true; o.arg = need(o.name); }
         }
         else if (a == "--share") {
             const std::string v = need("--share");
@@ -513,6 +545,36 @@ int main(int argc, char **argv) {
             char *end = nullptr;
             o.value = strtoul(o.arg.c_str(), &end, 10);
             const bool is_bpp = std::string(o.name) == "--export-bpp";
+            if (o.arg.empty() || o.arg[0] == '-' || *end || o.value < o.lo || o.value > o.hi || (is_bpp && o.value != 2 && o.value != 4 && o.value != 8)) {
+                if (is_bpp) fprintf(stderr, "error: invalid value '%s' for '%s': expected 2, 4 or 8\n", o.arg.c_str(), o.shown);
+                else fprintf(stderr, "error: invalid value '%s' for '%s': expected %lu..%lu\n", o.arg.c_str(), o.shown, o.lo, o.hi);
+                return 2;
+            }
+        }
+    }
+    int import_first = -1, set_import_first = -1; // the first import file of each family that was given
+    for (int k = 2; k >= 0; k--) { if (!import_file[k].empty()) import_first = k; if (!set_import_file[k].empty()) set_import_first = k; }
+    { // the native import: said before any file or device is touched
+        if (import_first >= 0) {
+            const char *opt = kImportName[import_first];
+            for (int k = 0; k < 3; k++) if (import_file[k].empty()) { fprintf(stderr, "error: '%s <F>' needs '%s <F>': a state is CGRAM, characters and tilemap words together\n", opt, kImportName[k]); return 2; }
+            const char *bad = !resume_file.empty() ? "'--resume'" : !tile_file.empty() ? "'--tile-palettes'" : !devices.empty() ? "'--devices'" : !shares.empty() ? "'--share'"
+                            : backdrop_fixed ? "'--backdrop-fixed'" : nullptr; // one state for one image on one device; the backdrop colour is the file's
+            if (bad) { fprintf(stderr, "error: the argument '%s <F>' cannot be used with %s\n", opt, bad); return 2; }
+        }
+        if (set_import_first >= 0) {
+            const char *opt = kSetImportName[set_import_first];
+            if (shares.empty()) { fprintf(stderr, "error: '%s <F>' needs '--share <SOURCE=TARGET>': it imports the state of a set (one image: --import-cgram, --import-chr, --import-map)\n", opt); return 2; }
+            for (int k = 0; k < 3; k++) if (set_import_file[k].empty()) { fprintf(stderr, "error: '%s <F>' needs '%s <F>': a state is CGRAM, characters and tilemap words together\n", opt, kSetImportName[k]); return 2; }
+            const char *bad = !devices.empty() ? "'--devices'" : set_backdrop ? "'--set-backdrop'" : set_backdrop_fixed ? "'--set-backdrop-fixed'" : !resume_file.empty() ? "'--resume'" : nullptr; // a backdrop set has no character calls yet
+            if (bad) { fprintf(stderr, "error: the argument '%s <F>' cannot be used with %s\n", opt, bad); return 2; }
+        }
+        for (auto &o : import_opt) {
+            if (!o.given) continue;
+            if (import_first < 0 && set_import_first < 0) { fprintf(stderr, "error: '%s' needs the import files: '--import-cgram', '--import-chr' and '--import-map' or, with --share, their '--set-import-' kin\n", o.shown); return 2; }
+            char *end = nullptr;
+            o.value = strtoul(o.arg.c_str(), &end, 10);
+            const bool is_bpp = std::string(o.name) == "--import-bpp";
             if (o.arg.empty() || o.arg[0] == '-' || *end || o.value < o.lo || o.value > o.hi || (is_bpp && o.value != 2 && o.value != 4 && o.value != 8)) {
                 if (is_bpp) fprintf(stderr, "error: invalid value '%s' for '%s': expected 2, 4 or 8\n", o.arg.c_str(), o.shown);
                 else fprintf(stderr, "error: invalid value '%s' for '%s': expected %lu..%lu\n", o.arg.c_str(), o.shown, o.lo, o.hi);
@@ -696,6 +758,34 @@ int main(int argc, char **argv) {
     if ((max_set_given || !set_tilemap_file.empty()) && (uint64_t)(shares.size() + 1) * (w / 8) * (h / 8) > 8192) // known once the images are decoded: said before the run, not after it
         die(std::string(max_set_given ? "--max-set-tiles" : "--set-tilemap") + ": the set has " + std::to_string((uint64_t)(shares.size() + 1) * (w / 8) * (h / 8)) +
             " tiles in all; the character budget of a set takes at most 8192 (eight frames of 256 x 256, nine of 256 x 224)");
+    // the native files of an import, read and sized before a device is touched: CGRAM 512 bytes, one tilemap word per tile (of every
+    // frame), whole characters of the depth named or implied
+    std::vector<uint8_t> in_cgram, in_chr, in_map;
+    const bool importing = import_first >= 0 || set_import_first >= 0;
+    if (importing) {
+        const bool of_set = set_import_first >= 0;
+        const std::string *files = of_set ? set_import_file : import_file;
+        std::vector<uint8_t> *into[3] = {&in_cgram, &in_chr, &in_map};
+        for (int k = 0; k < 3; k++) {
+            FILE *f = fopen(files[k].c_str(), "rb");
+            if (!f) { fprintf(stderr, "error: cannot read '%s'\n", files[k].c_str()); return 2; }
+            uint8_t buf[65536]; size_t n;
+            while ((n = fread(buf, 1, sizeof buf, f)) > 0 && into[k]->size() <= (1u << 20)) into[k]->insert(into[k]->end(), buf, buf + n);
+            fclose(f);
+        }
+        const size_t words = 32 * (size_t)(h / 8) * (of_set ? shares.size() + 1 : 1);
+        const unsigned long bpp = import_opt[0].value ? import_opt[0].value : (size <= 3 ? 2 : (size <= 15 ? 4 : 8));
+        if (in_cgram.size() != 512) { fprintf(stderr, "error: '%s' holds %zu bytes: a CGRAM image is 512\n", files[0].c_str(), in_cgram.size()); return 2; }
+        if (in_map.size() != 2 * words) { fprintf(stderr, "error: '%s' holds %zu bytes: %zu tilemap words of 2 bytes are expected\n", files[2].c_str(), in_map.size(), words); return 2; }
+        if (in_chr.empty() || in_chr.size() % (8 * bpp) || in_chr.size() / (8 * bpp) > 1024) {
+            fprintf(stderr, "error: '%s' holds %zu bytes: 1 to 1024 whole characters of %lu bytes (%lubpp) are expected\n", files[1].c_str(), in_chr.size(), 8 * bpp, bpp); return 2; }
+    }
+    snesimage_native_layout in_lay{};
+    in_lay.bpp = (uint8_t)import_opt[0].value; in_lay.char_base = (uint16_t)import_opt[1].value; in_lay.palette_base = (uint8_t)import_opt[2].value;
+    auto log_import = [&](const snesimage_native_info &ni, const char *of) {
+        log_info(std::string("Imported native data") + of + ": " + std::to_string(ni.bpp) + "bpp, " + std::to_string(ni.unique) + " characters at " + std::to_string(in_lay.char_base) + ", " +
+                 std::to_string(ni.map_words) + " tilemap words");
+    };
     if (!devices.empty()) device = devices[0];
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
@@ -795,6 +885,12 @@ int main(int argc, char **argv) {
             if (snesimage_set_tile_palettes(ctx, tp8.data()) != 0 || snesimage_set_palette_rgb5(ctx, rgb5.data()) != 0 || snesimage_optimize(ctx) != 0) die(snesimage_last_error());
             log_info("Resumed from " + resume_file);
         }
+    } else if (importing) { // the state is the files': no initialiser runs, and the map is a stored map until an optimizer call replaces it
+        snesimage_native_info ni{};
+        const uint16_t *words = reinterpret_cast<const uint16_t *>(in_map.data()); // (the words are little-endian as the host is)
+        if ((set ? snesimage_shared_import_native(set, &in_lay, in_cgram.data(), in_chr.data(), in_chr.size(), words, &ni)
+                 : snesimage_import_native(ctx, &in_lay, in_cgram.data(), in_chr.data(), in_chr.size(), words, &ni)) != 0) die(std::string("Unable to import native data: ") + snesimage_last_error());
+        log_import(ni, set ? " of the set" : "");
     } else if (set) { // the reference's initialisers on the images stacked top to bottom
         if (snesimage_shared_initialize_tiles(set) != 0) die(std::string("Unable to initialize tiles: ") + snesimage_last_error());
         log_info("Finished assigning initial tiles");

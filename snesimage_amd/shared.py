@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from .api import GUIDED_PROXIES, METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _export_native, _p
+from .api import GUIDED_PROXIES, METHOD_RANDOM, TILE_LOG_DTYPE, SnesImageError, _export_native, _import_native, _p
 
 
 SHARED_MERGE_LOG_DTYPE = np.dtype([("error", np.float64), ("member_error", np.float64), ("cost", np.uint64), ("member", np.uint16), ("tile", np.uint16),
@@ -402,6 +402,11 @@ class SharedPalette:
         """The set as the console loads it (include/snesimage_hip.h, "Native export"): as OptimizedImage.export_native, with
         ONE `chr` for all members (classes counted over the whole set) and `map` of shape [F, ntile], member order."""
         return _export_native(self, self._L.snesimage_shared_export_native, self._s, self._ntile(), len(self.images), bpp, char_base, palette_base, priority)
+
+    def import_native(self, cgram, chr, maps, bpp=0, char_base=0, palette_base=0):
+        """Load native bytes as the state of the set (include/snesimage_hip.h, "Native import"): one palette for all members,
+        each member's tile_palettes and stored map from its row of `maps` ([F, ntile]); all or nothing over the whole set."""
+        return _import_native(self, self._L.snesimage_shared_import_native, self._s, self._ntile(), len(self.images), cgram, chr, maps, bpp, char_base, palette_base)
 
     # -- state ------------------------------------------------------------------------------------
     @property
