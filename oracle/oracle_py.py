@@ -81,6 +81,9 @@ def lib():
         L.oracle_closest_color_index.argtypes = [_u8p, C.c_uint32, _f64p, C.c_int]
         L.oracle_kmeans.argtypes = [_f64p, C.c_uint32, C.c_uint32, _f64p, _u32p, _u32p]
         L.oracle_ssimulacra2_rgba.argtypes = [_u8p, _u8p, C.c_uint32, C.c_uint32, C.c_int, _f64p]
+        L.oracle_xyb_scale.argtypes = [_u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _u32p, _u32p, _f32p]
+        L.oracle_scale_stats.argtypes = [_u8p, _u8p, C.c_uint32, C.c_uint32, C.c_int, _f64p]
+        L.oracle_msssim_score.argtypes = [_f64p, C.c_uint32, _f64p]
         L.oracle_blur_plane.argtypes = [_f32p, _f32p, C.c_uint32, C.c_uint32, C.c_int]
         L.oracle_blur_constants.argtypes = [_f32p, _f32p, _f32p]
         L.oracle_det_math.argtypes = [C.c_int, _f32p, _f32p, C.c_uint32, _f32p]
@@ -193,6 +196,42 @@ def ssimulacra2_rgba(src, dst, blur_mode=0):
     out = C.c_double(0)
     rc = lib().oracle_ssimulacra2_rgba(_p(a, _u8p), _p(b, _u8p), w, h, blur_mode, C.byref(out))
     if rc != 0:
+        raise RuntimeError(lib().oracle_last_error().decode())
+    return out.value
+
+
+def xyb_pyramid(rgba, blur_mode=0):
+    """The positive XYB planes of every scale of one picture, as error() forms them: [float32 (3, h_s, w_s)]."""
+    a = _u8(rgba)
+    h, w = a.shape[0], a.shape[1]
+    sw, sh = C.c_uint32(0), C.c_uint32(0)
+    buf = np.zeros(3 * h * w, np.float32)  # no scale is larger than the picture
+    out, s, n = [], 0, 1
+    while s < n:
+        n = lib().oracle_xyb_scale(_p(a, _u8p), w, h, blur_mode, s, C.byref(sw), C.byref(sh), _p(buf, _f32p))
+        if n < 0:
+            raise RuntimeError(lib().oracle_last_error().decode())
+        out.append(buf[:3 * sh.value * sw.value].reshape(3, sh.value, sw.value).copy())
+        s += 1
+    return out
+
+
+def scale_stats(src, dst, blur_mode=0):
+    """The pooled statistics of a pair of pictures: float64 (scales, 18), per scale avg_ssim[6] then avg_edgediff[12]."""
+    a, b = _u8(src), _u8(dst)
+    h, w = a.shape[0], a.shape[1]
+    out = np.zeros((6, 18), np.float64)
+    n = lib().oracle_scale_stats(_p(a, _u8p), _p(b, _u8p), w, h, blur_mode, _p(out, _f64p))
+    if n < 0:
+        raise RuntimeError(lib().oracle_last_error().decode())
+    return out[:n].copy()
+
+
+def msssim_score(stats):
+    """Msssim::score of a (scales, 18) array of statistics."""
+    a = np.ascontiguousarray(stats, np.float64).reshape(-1, 18)
+    out = C.c_double(0)
+    if lib().oracle_msssim_score(_p(a, _f64p), a.shape[0], C.byref(out)) != 0:
         raise RuntimeError(lib().oracle_last_error().decode())
     return out.value
 

@@ -611,9 +611,9 @@ double msssim_score(const std::vector<ScaleStats> &scales) {
     return ssim;
 }
 
-// compute_frame_ssimulacra2 with the source side supplied (identical arithmetic to recomputing it)
-double ssimulacra2_against(const SrcPyramid &P, const Img3 &dst_lin0, int blur_mode) {
-    std::vector<ScaleStats> stats;
+// compute_frame_ssimulacra2 with the source side supplied (identical arithmetic to recomputing it): the per-scale statistics
+void ssimulacra2_stats(const SrcPyramid &P, const Img3 &dst_lin0, int blur_mode, std::vector<ScaleStats> &stats) {
+    stats.clear();
     Img3 lin = dst_lin0;
     Img3 img2, mu2, s22, s12;
     std::vector<float> mul;
@@ -634,6 +634,11 @@ double ssimulacra2_against(const SrcPyramid &P, const Img3 &dst_lin0, int blur_m
         ScaleStats st; scale_maps(S, img2, mu2, s22, s12, st);
         stats.push_back(st);
     }
+}
+// ... and the score of those statistics
+double ssimulacra2_against(const SrcPyramid &P, const Img3 &dst_lin0, int blur_mode) {
+    std::vector<ScaleStats> stats;
+    ssimulacra2_stats(P, dst_lin0, blur_mode, stats);
     return msssim_score(stats);
 }
 
@@ -1034,6 +1039,40 @@ int oracle_ssimulacra2_rgba(const uint8_t *src, const uint8_t *dst, uint32_t w, 
     Img3 a, b; rgba_to_linear(src, (int)w, (int)h, a, blur_mode); rgba_to_linear(dst, (int)w, (int)h, b, blur_mode);
     SrcPyramid P; build_src_pyramid(a, blur_mode, P);
     *score = ssimulacra2_against(P, b, blur_mode);
+    return 0;
+}
+// ---- stage outputs of error()'s arithmetic (tests/test_ssim2_model.py): the functions oracle_error runs, stopped early ----
+int oracle_xyb_scale(const uint8_t *rgba, uint32_t w, uint32_t h, int blur_mode, uint32_t scale, uint32_t *sw, uint32_t *sh, float *planes) {
+    if (w < 8 || h < 8) return fail("image smaller than 8x8");
+    Img3 lin; rgba_to_linear(rgba, (int)w, (int)h, lin, blur_mode);
+    SrcPyramid P; build_src_pyramid(lin, blur_mode, P);
+    if (scale < P.scales.size()) {
+        const SrcScale &S = P.scales[scale];
+        if (sw) *sw = (uint32_t)S.w;
+        if (sh) *sh = (uint32_t)S.h;
+        if (planes) for (int c = 0; c < 3; c++) std::memcpy(planes + (size_t)c * S.w * S.h, S.img1.p[c].data(), sizeof(float) * (size_t)S.w * S.h);
+    }
+    return (int)P.scales.size();
+}
+int oracle_scale_stats(const uint8_t *src, const uint8_t *dst, uint32_t w, uint32_t h, int blur_mode, double *stats18) {
+    if (w < 8 || h < 8) return fail("image smaller than 8x8");
+    Img3 a, b; rgba_to_linear(src, (int)w, (int)h, a, blur_mode); rgba_to_linear(dst, (int)w, (int)h, b, blur_mode);
+    SrcPyramid P; build_src_pyramid(a, blur_mode, P);
+    std::vector<ScaleStats> stats; ssimulacra2_stats(P, b, blur_mode, stats);
+    for (size_t s = 0; s < stats.size(); s++) {
+        std::memcpy(stats18 + 18 * s, stats[s].avg_ssim, sizeof(double) * 6);
+        std::memcpy(stats18 + 18 * s + 6, stats[s].avg_edgediff, sizeof(double) * 12);
+    }
+    return (int)stats.size();
+}
+int oracle_msssim_score(const double *stats18, uint32_t nscales, double *score) {
+    if (nscales > SSIM2_NUM_SCALES) return fail("more than six scales");
+    std::vector<ScaleStats> stats(nscales);
+    for (uint32_t s = 0; s < nscales; s++) {
+        std::memcpy(stats[s].avg_ssim, stats18 + 18 * s, sizeof(double) * 6);
+        std::memcpy(stats[s].avg_edgediff, stats18 + 18 * s + 6, sizeof(double) * 12);
+    }
+    *score = msssim_score(stats);
     return 0;
 }
 void oracle_blur_plane(const float *in, float *out, uint32_t w, uint32_t h, int mode) { blur_plane(in, out, (int)w, (int)h, mode); }

@@ -99,6 +99,16 @@ int oracle_kmeans(const double *points, uint32_t n, uint32_t k, double *centres_
 /* ssimulacra2 0.5.1 compute_frame_ssimulacra2 on two RGBA8 images (alpha ignored): returns score. */
 int oracle_ssimulacra2_rgba(const uint8_t *src, const uint8_t *dst, uint32_t w, uint32_t h,
                             int blur_mode, double *score);
+/* Stage outputs of the same arithmetic, for tests/test_ssim2_model.py.  All return the number of scales (negative on error).
+ * oracle_xyb_scale: the positive XYB planes of scale `scale` of one RGBA8 picture, as error() forms them for the source:
+ * *sw x *sh and, where `planes` is not NULL, 3 planes of *sw * *sh floats (X, Y, B); nothing is written for a scale the
+ * picture does not have.  oracle_scale_stats: per scale, avg_ssim[6] (channel, {1-norm, 4-norm}) then avg_edgediff[12]
+ * (channel, {artifact 1, artifact 4, detail_lost 1, detail_lost 4}); stats18 holds 6 * 18 doubles.
+ * oracle_msssim_score: Msssim::score of a caller's statistics in that layout (returns 0). */
+int oracle_xyb_scale(const uint8_t *rgba, uint32_t w, uint32_t h, int blur_mode, uint32_t scale, uint32_t *sw,
+                     uint32_t *sh, float *planes);
+int oracle_scale_stats(const uint8_t *src, const uint8_t *dst, uint32_t w, uint32_t h, int blur_mode, double *stats18);
+int oracle_msssim_score(const double *stats18, uint32_t nscales, double *score);
 /* Blur one plane (mode as oracle_set_blur_mode). */
 void oracle_blur_plane(const float *in, float *out, uint32_t w, uint32_t h, int mode);
 /* Recursive-Gaussian constants (n2[3], d1[3] as f32) and the equivalent FIR taps h[-4..4]. */
