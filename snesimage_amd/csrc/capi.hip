@@ -204,6 +204,10 @@ struct snesimage_ctx {
         // At scale 0 the candidates' long H pass leaves out the s22 / s12 planes of the channels whose V class forms no SSIM map
         // (kernels_sparse2.hpp, sparse_h2_dispatch).  SNES_H_PLANES=0: three planes everywhere, the masked V pass as it is.
         bool h_planes = true;
+        // At scale 0 a wave of k_sparse_v2 sweeps two candidates in the channels whose V class forms no SSIM map: the source's a1
+        // and r1 are fetched once for both (kernels_sparse2.hpp, sparse_v2_pair_body).  SNES_V2_PAIR=0: one candidate
+        // per wave, the launch and the grid as they were.
+        bool v2_pair = true;
         // SNES_DEBUG_POISON=1 (a debug aid, off by default): every call fills its candidates' storage with 0xFF bytes (binary32
         // NaNs) before anything of the call writes it, so that a read of a plane the H pass left out shows as a NaN error instead of
         // hiding behind a stale finite value with a zero weight.
@@ -638,6 +642,7 @@ SparseParams sparse_params(snesimage_ctx *c, uint32_t lane) {
     for (P.s_first = 0; P.s_first < c->G.nscales && c->G.sw[P.s_first] >= 64; P.s_first++) {} // first narrow scale
     P.full_sums = sp.weight_mask ? 0 : 1;
     P.h_planes = (sp.weight_mask && sp.h_planes) ? 1 : 0;
+    P.v2_pair = (sp.weight_mask && sp.v2_pair) ? v2_pair_channels(c->G) : 0;
     if (c->dither) {
         const uint32_t l = lane < c->nlanes ? lane : 0;
         P.use_maps = 1; P.sub_size = (int)c->sub_size; P.slot_ci = sp.slot_ci; P.subC4 = c->d_subC4; P.tile_pal = c->d_tile_pal;
@@ -828,7 +833,7 @@ int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, 
         if (v0_aside) { // scale 0's V pass needs scale 0's H pass, B's sweeps and the order: nothing of the main stream's
             HIPCHK(hipStreamWaitEvent(hs, sp.ev_base_done, 0)); // checkpoints and H output of B
             if (c->timing) HIPCHK(hipEventRecord(tr.ev[3], hs));
-            hipLaunchKernelGGL(k_sparse_v2, dim3(nc * 3, 1), dim3(256), 0, hs, P); // grid.y = scale 0 only
+            hipLaunchKernelGGL(k_sparse_v2, dim3(v2_pair_grid(nc, P.v2_pair), 1), dim3(256), 0, hs, P); // grid.y = scale 0 only; nc * 3 blocks unless channels pair
             if (c->timing) HIPCHK(hipEventRecord(tr.ev[4], hs)); // ev[3]..ev[4]: k_sparse_v2 (scale 0: three quarters of the V pass) alone
             HIPCHK(hipEventRecord(sp.ev_v0[lane], hs));
         }
@@ -875,7 +880,7 @@ int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, 
         if (P.s_first > 1) hipLaunchKernelGGL(k_sparse_v2_from, dim3(nc * 3, (unsigned)(P.s_first - 1)), dim3(256), 0, stream, P, 1);
     } else {
     if (c->timing) HIPCHK(hipEventRecord(tr.ev[3], stream));
-    hipLaunchKernelGGL(k_sparse_v2, dim3(nc * 3, (unsigned)P.s_first), dim3(256), 0, stream, P);
+    hipLaunchKernelGGL(k_sparse_v2, dim3(P.s_first == 1 ? v2_pair_grid(nc, P.v2_pair) : nc * 3, (unsigned)P.s_first), dim3(256), 0, stream, P); // (with further scales in the grid, scale 0's blocks beyond its pairs return at once)
     if (c->timing) HIPCHK(hipEventRecord(tr.ev[4], stream)); // ev[3]..ev[4]: k_sparse_v2 alone
     }
     if (vn_aside) HIPCHK(hipStreamWaitEvent(stream, sp.ev_vn[lane], 0));
@@ -1192,6 +1197,7 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (const char *e = getenv("SNES_DEDUP")) c->sp.dedup = atoi(e) != 0;
     if (const char *e = getenv("SNES_WEIGHT_MASK")) c->sp.weight_mask = atoi(e) != 0;
     if (const char *e = getenv("SNES_H_PLANES")) c->sp.h_planes = atoi(e) != 0;
+    if (const char *e = getenv("SNES_V2_PAIR")) c->sp.v2_pair = atoi(e) != 0;
     if (const char *e = getenv("SNES_DEBUG_POISON")) c->sp.debug_poison = atoi(e) != 0;
     if (const char *e = getenv("SNES_DEDUP_MIN")) { int v = atoi(e); if (v >= 1) c->sp.dedup_min = (uint32_t)v; }
     Geom &G = c->G;

@@ -80,6 +80,7 @@ struct SparseParams {
     const int *holder; int list0; // duplicate colours (kernels.hpp, dedup_*): the table, or nullptr; list index of the launch's first candidate
     int full_sums; // 1: the candidates' wide V pass forms all six pooling sums of every (channel, scale) (SNES_WEIGHT_MASK=0); 0: only those with a non-zero weight (kSumMasks)
     int h_planes;  // 1: the candidates' long H pass writes, at scale 0, only mu2 and the XYB plane of the channels whose V class forms no SSIM map (sum_class_has_ssim); 0: three H planes everywhere (SNES_H_PLANES=0; implied by full_sums)
+    int v2_pair;   // k_sparse_v2, scale 0: bit ch = the blocks of channel ch sweep two candidates per wave (kernels_sparse2.hpp, v2_pair_channels); 0: one everywhere (SNES_V2_PAIR=0; implied by full_sums)
 };
 
 __device__ __forceinline__ uint32_t sparse_ci(uint32_t lo, uint32_t thr, uint32_t crgb, uint32_t ncol) {

@@ -695,6 +695,220 @@ __device__ __forceinline__ void sparse_v2_body(const SparseParams &P, const int 
         for (int q = 0; q < 6; q++) o[q] = ((MASK >> q) & 1) ? red[t][q] : 0.0; // a sum not formed: +0.0, never what the storage held
     }
 }
+// ---- two candidates per wave (scale 0, the classes without an SSIM map) --------------------------------------------------------
+// Such a block waits on what its CU's vector-memory path delivers out of L2, and 48 of the 80 bytes a lane fetches
+// per group iteration are the source's a1 and r1: the same for every candidate.  Here a wave sweeps its 64 columns of the
+// channel for TWO candidates, partners in the launch's order, and fetches a1 and r1 once for both.  Per candidate the wave keeps
+// what sparse_v2_body<false, MASK> keeps for its one — the mu2 state, the H-plane buffers, the XYB quad, the sums of the mask,
+// the ring tails (the second candidate's in the plane-1 slots of V2Shared::raw, which these classes leave unused; its group ->
+// slot table in the plane-2 slot) — and each candidate's operations, operands and order are that body's exactly: only the
+// registers that hold a1 and r1 are shared.
+//
+// Where the sweep starts.  Per wave: a candidate without an own group on these columns takes B's final sums, as in the single
+// body; if only one has an own group the sweep runs for that one alone (NC = 1); if both have, both resume from B's record
+// min(gsA, gsB).  The last rests on an invariant the single body already lives by without saying so:
+//     a sweep whose inputs on its columns are B's up to group g reproduces B's record g bit for bit
+// (the state before iteration g and the sums of the rows above it: the same operations on the same values in the same order as
+// B's own sweep, which every V-pass flavour shares — SNES_VSTEP, maps_accumulate — and -ffp-contract=off leaves alone).  The
+// later candidate's slots are -1 up to its own first group, so it reads B's planes there and arrives at its own record.
+// tests/test_v2_pairs.py pins it: lists in no order, whose partners start the whole picture apart, against the single body.
+// B's H plane and XYB quad are still fetched per candidate where both partners' slot is -1: issuing them once (a wave-uniform
+// skip of the second load) measured slower, and both skips together spill at 96 VGPRs.
+template <int MASK, int NC>
+__device__ __forceinline__ void sparse_v2_sweep(const SparseParams &P, const int s, const int W, const int H, const int ch, const int xw, const int gs,
+                                                const int (&kk)[NC], const short *const (&slot)[NC], const int (&rp)[NC], unsigned char *const s_raw, double (&acc)[NC][6]) {
+    static_assert(!(MASK & kSumSsim) && (MASK & kSumEdge), "the classes without an SSIM map");
+    const Geom &G = P.G;
+    const int H4 = H >> 2, t = threadIdx.x, lane = t & 63;
+    const size_t ns = (size_t)W * H;
+    const float *store_b = P.store + (size_t)P.base * P.S.cand_stride;
+    const size_t h_off = P.S.off_hout[s] + (size_t)(ch * 3) * 4 * W + ((size_t)(xw >> 6) << 8), x_off = P.S.off_xybR[s] + (size_t)ch * 4 * W + (size_t)xw * 4;
+    rsrc_t h_own[NC], x_own[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        const float *store_k = P.store + (size_t)kk[c] * P.S.cand_stride;
+        h_own[c] = make_rsrc(store_k + h_off); x_own[c] = make_rsrc(store_k + x_off);
+    }
+    const rsrc_t h_b = make_rsrc(store_b + h_off), x_b = make_rsrc(store_b + x_off), h_zero = make_rsrc(P.zeros);
+    const rsrc_t a1_b = make_rsrc(P.a1R4 + G.src_off[s] + (size_t)ch * ns + (size_t)xw * 4);
+    const rsrc_t r1_b = make_rsrc(P.r1R4 + G.src_off[s] + (size_t)ch * ns + (size_t)xw * 4);
+    const uint32_t l4 = (uint32_t)lane << 2, l8 = (uint32_t)lane << 3, l16 = (uint32_t)lane << 4, l32 = (uint32_t)lane << 5;
+    const uint32_t W16 = (uint32_t)W * 16u;
+    const float n2_0 = P.K.n2[0], n2_1 = P.K.n2[1], n2_2 = P.K.n2[2];
+    const float d1_0 = P.K.d1[0], d1_1 = P.K.d1[1], d1_2 = P.K.d1[2];
+    float sa[NC][3], sb[NC][3];
+    { // record gs: mu2's state and the sums of the mask, the same for every candidate of the wave
+        const float *cf = P.ckf + P.S.off_ckf[s] + ((size_t)ch * (H4 + 2) + gs) * 18 * W + xw;
+        const double *ca = P.cka + P.S.off_cka[s] + ((size_t)ch * (H4 + 2) + gs) * 6 * W + xw;
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const float a = ld_at<float>(cf + (size_t)q * W, l4), b = ld_at<float>(cf + (size_t)(3 + q) * W, l4);
+#pragma unroll
+            for (int c = 0; c < NC; c++) { sa[c][q] = a; sb[c][q] = b; }
+        }
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            const double a = ((MASK >> q) & 1) ? ld_at<double>(ca + (size_t)q * W, l8) : 0.0;
+#pragma unroll
+            for (int c = 0; c < NC; c++) acc[c][q] = a;
+        }
+    }
+#define SNES_HLOAD(C, GG, DST)                                                                                                \
+    {                                                                                                                         \
+        const int gg_ = (GG);                                                                                                 \
+        const bool below_ = gg_ >= H4;                                                                                        \
+        const int sl_ = uni((int)slot[C][below_ ? 0 : gg_]);                                                                  \
+        const rsrc_t r_ = below_ ? h_zero : (sl_ >= 0 ? h_own[C] : h_b);                                                      \
+        const uint32_t so_ = below_ ? 0u : (uint32_t)(sl_ >= 0 ? sl_ : gg_) * 9u * W16;                                       \
+        DST = buf_ld4(r_, l16, so_);                                                                                          \
+    }
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float2 *ring_xy = reinterpret_cast<float2 *>(s_raw) + t;                             // + (slot*3 + plane) * 256
+    float2 *ring_zw = reinterpret_cast<float2 *>(s_raw + 2 * 3 * 256 * sizeof(float2)) + t;
+    float4 bufA[NC], bufB[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+        float4 g1 = zero4, g2 = zero4, g3 = zero4;
+        bufA[c] = zero4; bufB[c] = zero4;
+        if (gs < H4) SNES_HLOAD(c, gs, bufA[c])
+        if (gs - 1 >= 0) SNES_HLOAD(c, gs - 1, g1)
+        if (gs - 2 >= 0) SNES_HLOAD(c, gs - 2, g2)
+        if (gs - 3 >= 0) SNES_HLOAD(c, gs - 3, g3)
+        const int p = rp[c];
+        ring_xy[(1 * 3 + p) * 256] = make_float2(g1.x, g1.y); ring_zw[(2 * 3 + p) * 256] = make_float2(g1.z, g1.w); // r = -1
+        ring_xy[(0 * 3 + p) * 256] = make_float2(g2.x, g2.y); ring_zw[(1 * 3 + p) * 256] = make_float2(g2.z, g2.w); // r = -2
+        ring_zw[(0 * 3 + p) * 256] = make_float2(g3.z, g3.w);                                                       // r = -3
+    }
+    int r2 = 0, r3 = 0;
+    // the map inputs of row group g are fetched during iteration g, an iteration ahead of their use (sparse_v2_body, PRE): a1 and
+    // r1 once, the XYB quad per candidate
+    float4 n_a1, n_x[NC];
+    double2 n_ra, n_rb;
+#define SNES_V2MLOAD(GM)                                                                                                      \
+    {                                                                                                                         \
+        const int gm_ = (GM);                                                                                                 \
+        const uint32_t go_ = (uint32_t)gm_ * W16;                                                                             \
+        n_a1 = buf_ld4(a1_b, l16, go_);                                                                                       \
+        n_ra = buf_ld2d(r1_b, l32, 2u * go_); n_rb = buf_ld2d(r1_b, l32 + 16u, 2u * go_);                                     \
+        _Pragma("unroll") for (int c = 0; c < NC; c++) {                                                                      \
+            const int sl_ = uni((int)slot[c][gm_]);                                                                           \
+            n_x[c] = buf_ld4(sl_ >= 0 ? x_own[c] : x_b, l16, (uint32_t)(sl_ >= 0 ? sl_ : gm_) * 3u * W16);                    \
+        }                                                                                                                     \
+    }
+    SNES_V2MLOAD(min(max(gs - 1, 0), H4 - 1))
+#define SNES_V2GROUP(CUR, NXT)                                                                                                \
+    {                                                                                                                         \
+        _Pragma("unroll") for (int c = 0; c < NC; c++) SNES_HLOAD(c, g + 1, NXT[c])                                           \
+        float4 c_a1 = n_a1, c_x[NC];                                                                                          \
+        const double2 c_ra = n_ra, c_rb = n_rb;                                                                               \
+        _Pragma("unroll") for (int c = 0; c < NC; c++) c_x[c] = n_x[c];                                                       \
+        SNES_V2MLOAD(min(g, H4 - 1))                                                                                          \
+        float outp[NC][4];                                                                                                    \
+        _Pragma("unroll") for (int c = 0; c < NC; c++) {                                                                      \
+            float2 *pz = ring_zw + (r3 * 3 + rp[c]) * 256, *px = ring_xy + (r2 * 3 + rp[c]) * 256;                            \
+            const float2 tz = *pz, tx = *px;                                                                                  \
+            *pz = make_float2(CUR[c].z, CUR[c].w);                                                                            \
+            *px = make_float2(CUR[c].x, CUR[c].y);                                                                            \
+            SNES_VSTEP(tz.x + CUR[c].x, sa[c], sb[c], outp[c][0])                                                             \
+            SNES_VSTEP(tz.y + CUR[c].y, sb[c], sa[c], outp[c][1])                                                             \
+            SNES_VSTEP(tx.x + CUR[c].z, sa[c], sb[c], outp[c][2])                                                             \
+            SNES_VSTEP(tx.y + CUR[c].w, sb[c], sa[c], outp[c][3])                                                             \
+        }                                                                                                                     \
+        asm volatile("" : "+v"(c_a1.x), "+v"(c_a1.y), "+v"(c_a1.z), "+v"(c_a1.w));                                            \
+        if (g >= 1) {                                                                                                         \
+            const float a1v[4] = {c_a1.x, c_a1.y, c_a1.z, c_a1.w};                                                            \
+            const double r1v[4] = {c_ra.x, c_ra.y, c_rb.x, c_rb.y};                                                           \
+            _Pragma("unroll") for (int c = 0; c < NC; c++) {                                                                  \
+                const float i2v[4] = {c_x[c].x, c_x[c].y, c_x[c].z, c_x[c].w};                                                \
+                _Pragma("unroll") for (int q = 0; q < 4; q++)                                                                 \
+                    maps_accumulate<MASK>(acc[c], 0.0f, 0.0f, a1v[q], r1v[q], outp[c][q], 0.0f, 0.0f, i2v[q]);                \
+            }                                                                                                                 \
+        }                                                                                                                     \
+        r2 ^= 1; r3 = r3 == 2 ? 0 : r3 + 1;                                                                                   \
+    }
+    for (int g = gs; g <= H4; g++) {
+        SNES_V2GROUP(bufA, bufB)
+        g++;
+        if (g > H4) break;
+        SNES_V2GROUP(bufB, bufA)
+    }
+#undef SNES_V2GROUP
+#undef SNES_V2MLOAD
+#undef SNES_HLOAD
+}
+// One block = the four 64-column waves of (channel ch, partners 2 pi and 2 pi + 1 of the launch's order); W = 256.
+template <int MASK>
+__device__ __forceinline__ void sparse_v2_pair_body(const SparseParams &P, const int s, const int ch, const int pi, V2Shared &sh) {
+    unsigned char *const s_raw = sh.raw;
+    double (*red)[6] = reinterpret_cast<double (*)[6]>(s_raw);
+    static_assert(sizeof(sh.raw) >= 2 * 256 * 6 * sizeof(double), "the reduction scratch of two candidates must fit the tail ring");
+    const Geom &G = P.G;
+    const int W = uni(G.sw[s]), H = uni(G.sh[s]), H4 = H >> 2;
+    const int t = threadIdx.x, lane = t & 63;
+    const int wv = uni(t >> 6), xw = wv << 6;
+    const bool two = 2 * pi + 1 < P.ncand; // a last odd candidate runs unpaired
+    const int ci0 = 2 * pi, ci1 = two ? 2 * pi + 1 : ci0;
+    const int k0 = uni(P.k0 + (P.order ? P.order[ci0] : ci0)), k1 = uni(P.k0 + (P.order ? P.order[ci1] : ci1));
+    // group -> slot per candidate, by the single body's rule; the second table in the plane-2 slot of the xy ring
+    short *const slot0 = sh.slot[wv], *const slot1 = reinterpret_cast<short *>(s_raw + (0 * 3 + 2) * 256 * sizeof(float2)) + wv * 64;
+    int gs0, gs1;
+    {
+        const int g = lane;
+        short sl0 = -1, sl1 = -1;
+        if (g < H4) {
+            const CandMeta *M0 = P.meta + k0, *M1 = P.meta + k1;
+            sl0 = M0->gslot[P.S.goff[s] + g]; if (sl0 >= 0 && ((int)M0->gcb[P.S.goff[s] + g] << 6) > xw) sl0 = -1;
+            if (two) { sl1 = M1->gslot[P.S.goff[s] + g]; if (sl1 >= 0 && ((int)M1->gcb[P.S.goff[s] + g] << 6) > xw) sl1 = -1; }
+        }
+        slot0[lane] = sl0; slot1[lane] = sl1;
+        const unsigned long long own0 = __ballot(sl0 >= 0), own1 = __ballot(sl1 >= 0);
+        gs0 = uni(own0 ? __ffsll((long long)own0) - 1 : H4 + 1);
+        gs1 = uni(own1 ? __ffsll((long long)own1) - 1 : H4 + 1);
+    }
+    __syncthreads();
+    double acc[2][6];
+    if (gs0 <= H4 && gs1 <= H4) {
+        const int kk[2] = {k0, k1}, rp[2] = {0, 1};
+        const short *const sl[2] = {slot0, slot1};
+        sparse_v2_sweep<MASK, 2>(P, s, W, H, ch, xw, min(gs0, gs1), kk, sl, rp, s_raw, acc);
+    } else {
+        { // B's final sums (record H/4 + 1) for whoever has no own group on these columns
+            const double *ca = P.cka + P.S.off_cka[s] + ((size_t)ch * (H4 + 2) + H4 + 1) * 6 * W + xw;
+#pragma unroll
+            for (int q = 0; q < 6; q++) acc[0][q] = acc[1][q] = ((MASK >> q) & 1) ? ld_at<double>(ca + (size_t)q * W, (uint32_t)lane << 3) : 0.0;
+        }
+        if (gs0 <= H4 || gs1 <= H4) {
+            const bool first = gs0 <= H4;
+            const int kk[1] = {first ? k0 : k1}, rp[1] = {0};
+            const short *const sl[1] = {first ? slot0 : slot1};
+            double a1[1][6];
+            sparse_v2_sweep<MASK, 1>(P, s, W, H, ch, xw, first ? gs0 : gs1, kk, sl, rp, s_raw, a1);
+#pragma unroll
+            for (int q = 0; q < 6; q++) { if (first) acc[0][q] = a1[0][q]; else acc[1][q] = a1[0][q]; }
+        }
+    }
+    __syncthreads(); // the tail rings and the second slot table are dead: their space becomes the reduction scratch
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+        for (int q = 0; q < 6; q++) if ((MASK >> q) & 1) red[c * 256 + t][q] = acc[c][q];
+    __syncthreads();
+    for (int stride = W >> 1; stride > 0; stride >>= 1) { // per candidate the single body's tree (W = 256: a column per thread)
+        if (t < stride) {
+#pragma unroll
+            for (int c = 0; c < 2; c++)
+#pragma unroll
+                for (int q = 0; q < 6; q++) if ((MASK >> q) & 1) red[c * 256 + t][q] += red[c * 256 + t + stride][q];
+        }
+        __syncthreads();
+    }
+    if (t == 0 || (t == 64 && two)) {
+        const int c = t >> 6;
+        double *o = P.part + (((size_t)(c ? k1 : k0) * G.nscales + s) * 3 + ch) * 6;
+#pragma unroll
+        for (int q = 0; q < 6; q++) o[q] = ((MASK >> q) & 1) ? red[c * 256][q] : 0.0; // a sum not formed: +0.0, never what the storage held
+    }
+}
 // B's sweep: every sum
 __device__ __forceinline__ void sparse_v2_base(const SparseParams &P, const int s, const int bx) {
     __shared__ V2Shared sh;
@@ -709,8 +923,51 @@ __device__ __forceinline__ void sparse_v2_class(const SparseParams &P, const int
     if (first && cls == I) sparse_v2_body<false, kSumClassesHost.m[I]>(P, s, bx, sh);
     else if constexpr (I + 1 < kSumClasses) sparse_v2_class<I + 1>(P, s, bx, sh, cls);
 }
-__device__ __forceinline__ void sparse_v2_cand(const SparseParams &P, const int s, const int bx) {
+// Two candidates per wave (sparse_v2_pair_body): which channels of scale 0 pair, and the blocks of the launch.  A channel pairs
+// where its class — the instantiation its blocks run, by the rule of sum_class_of — forms no SSIM map and a (candidate, channel)
+// fills the block (W = 256).  The host restates sum_class() over the same constexpr tables and hands the kernel the channels
+// as a mask (SparseParams::v2_pair), so that the grid and the kernel's block -> (channel, partners) map come from one value.
+// Blocks stay channel-major (a channel's shared planes fit an XCD's L2): a pairing channel has (ncand + 1) / 2 blocks, the
+// others ncand.  Without a pairing channel the grid is ncand * 3, the single form's.
+constexpr int sum_class_host(const int need) {
+    int best = kSumClasses - 1, bits = 7;
+    for (int i = 0; i < kSumClasses; i++) {
+        const int m = kSumClassesHost.m[i];
+        int pc = 0;
+        for (int b = 0; b < 6; b++) pc += (m >> b) & 1;
+        if ((m & need) == need && pc < bits) { best = i; bits = pc; }
+    }
+    return best;
+}
+constexpr bool sum_class_pairs(const int i) { return !(kSumClassesHost.m[i] & kSumSsim) && (kSumClassesHost.m[i] & kSumEdge); }
+inline int v2_pair_channels(const Geom &G) { // bit ch: channel ch of scale 0 runs two candidates per wave
+    int m = 0;
+    if ((G.sw[0] >> 6) == 4) for (int ch = 0; ch < 3; ch++) if (sum_class_pairs(sum_class_host(kSumMasksHost.m[G.nscales][ch][0]))) m |= 1 << ch;
+    return m;
+}
+inline unsigned v2_pair_grid(const unsigned nc, const int mask) { unsigned n = 0; for (int ch = 0; ch < 3; ch++) n += ((mask >> ch) & 1) ? (nc + 1) / 2 : nc; return n; }
+template <int I>
+__device__ __forceinline__ void sparse_v2_pair_class(const SparseParams &P, const int s, const int ch, const int pi, V2Shared &sh, const int cls) {
+    if constexpr (sum_class_is_first(I) && sum_class_pairs(I)) { if (cls == I) { sparse_v2_pair_body<kSumClassesHost.m[I]>(P, s, ch, pi, sh); return; } }
+    if constexpr (I + 1 < kSumClasses) sparse_v2_pair_class<I + 1>(P, s, ch, pi, sh, cls);
+}
+// PAIR: the kernel honours SparseParams::v2_pair (k_sparse_v2); the batched shells do not and keep the single form's registers
+template <bool PAIR = false>
+__device__ __forceinline__ void sparse_v2_cand(const SparseParams &P, const int s, int bx) {
     __shared__ V2Shared sh;
+    if (PAIR && s == 0 && P.v2_pair) {
+        int ch = 0;
+        bool pr = false;
+        for (;; ch++) {
+            if (ch == 3) return;
+            pr = (P.v2_pair >> ch) & 1;
+            const int nb = pr ? (P.ncand + 1) >> 1 : P.ncand;
+            if (bx < nb) break;
+            bx -= nb;
+        }
+        if (pr) { sparse_v2_pair_class<0>(P, s, ch, bx, sh, uni(sum_class_of(P.G.nscales, ch, s))); return; }
+        bx += ch * P.ncand; // the single form's block of (ch, candidate bx)
+    }
     const int ppw = 4 / (P.G.sw[s] >> 6), npairs = P.ncand * 3; // pairs per block
     if (bx * ppw >= npairs) return;
     int cls;
@@ -881,7 +1138,7 @@ __global__ __launch_bounds__(64) void k_sparse_h2_base(SparseParams P) { sparse_
 // copy meet at the joins of the dispatch), and the kernels took 1 KB of scratch per lane and spilled.  The first argument of a
 // kernel lies at offset 0 of its argument segment, which is constant, wave-uniform memory: scalar loads, as before.
 __device__ __forceinline__ const SparseParams &kernarg_params() { return *(const SparseParams *)__builtin_amdgcn_kernarg_segment_ptr(); }
-__global__ __launch_bounds__(256, 5) void k_sparse_v2(SparseParams) { const SparseParams &P = kernarg_params(); if ((int)blockIdx.y < P.G.nscales && P.G.sw[blockIdx.y] >= 64) sparse_v2_cand(P, (int)blockIdx.y, (int)blockIdx.x); }
+__global__ __launch_bounds__(256, 5) void k_sparse_v2(SparseParams) { const SparseParams &P = kernarg_params(); if ((int)blockIdx.y < P.G.nscales && P.G.sw[blockIdx.y] >= 64) sparse_v2_cand<true>(P, (int)blockIdx.y, (int)blockIdx.x); }
 // the wide scales from s0 on (the launch that follows the other scales' H pass when scale 0, whose H pass went ahead, runs beside it)
 __global__ __launch_bounds__(256, 5) void k_sparse_v2_from(SparseParams, int s0) { const SparseParams &P = kernarg_params(); const int s = s0 + (int)blockIdx.y; if (s < P.G.nscales && P.G.sw[s] >= 64) sparse_v2_cand(P, s, (int)blockIdx.x); }
 // B: the wide scales in this body (grid.y = scale), the narrow ones in the general one (grid.y = scale - s_first), two launches:
