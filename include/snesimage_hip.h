@@ -339,6 +339,51 @@ int32_t snesimage_tile_sweep(snesimage_ctx *ctx, uint32_t first_tile, uint32_t n
 int32_t snesimage_shared_tile_sweep(snesimage_shared *set, uint32_t first_tile, uint32_t n_tiles, uint32_t window,
                                     snesimage_tile_result *log, snesimage_run_stats *stats);
 
+/* Palette blocks — NOT a reference method.  Only an SNES background in 8 x 8 tile mode chooses a subpalette per tile: the NES
+ * attribute table and an SNES background in 16 x 16 tile mode choose one per 2 x 2 tiles, an OBJ one per 16 x 16, 32 x 32 or
+ * 64 x 64 object.  snesimage_set_palette_blocks(ctx, bw, bh) makes the context choose per BLOCK of bw x bh tiles, bw and bh each
+ * one of 1, 2, 4, 8, bh dividing h/8.  Block b = by * (32/bw) + bx covers tiles tx in [bx*bw, (bx+1)*bw), ty in
+ * [by*bh, (by+1)*bh).  1 x 1, the default, switches blocking off: every launch is then what it is without this section.
+ *   THE INVARIANT.  On a context with bw*bh > 1 ("blocked") tile_palettes is constant over every block of the image, always.
+ *   The setter changes nothing else (map, incumbent and epoch stay); it checks the current table and refuses with SNES_ERR_STATE
+ *   if it is not constant over the new blocks — set such a table first, or call the setter before snesimage_initialize_tiles (a
+ *   fresh context, all zeros, passes).  Other refusals: SNES_ERR_ARG for a null context, other values, a bh that does not divide
+ *   h/8; SNES_ERR_STATE for a pending split-phase step or window and a context lent to a set, batch or group.
+ * On a blocked context:
+ *   - snesimage_set_tile_palettes with a table that is not constant over the image's blocks is SNES_ERR_ARG, the message names
+ *     the lowest offending block, the context is untouched; entries behind the image's tiles are not judged;
+ *   - snesimage_initialize_tiles is lib.rs:79-189 with the block in place of the tile: the outer loops run bx outer, by inner
+ *     (the order of the k-means points, so the starting centres); per block the f32 sums and the count run over its opaque
+ *     pixels, x outer, y inner over bw*8 x bh*8 pixels, one ordered chain; the test sum[0] + sum[1] + sum[2] > 0 is the block's;
+ *     the mean is f64(sum) / f64(count); every tile of a clustered block takes the cluster's index, a block left out keeps
+ *     what it had; centre -> colour, the fill and the closing optimize() are unchanged; cogset's 2 <= k < n counts blocks
+ *     (SNES_ERR_KMEANS); sub_count == 1 is unchanged;
+ *   - snesimage_reassign_tiles moves blocks: cost(b, p) = the binary64 sum, over the block's tiles in raster order (ty outer, tx
+ *     inner), of the tile costs defined above, tiles without an opaque pixel contributing nothing; a block with an opaque pixel
+ *     moves as a whole by the same rule (strictly smallest, ties keep the current subpalette, then the lower index); *moved
+ *     counts tiles, a multiple of bw*bh;
+ *   - snesimage_score_tile_moves, snesimage_tile_step and snesimage_tile_sweep answer SNES_ERR_UNSUPPORTED (a single-tile move
+ *     would break the invariant; the message names the block call to use), snesimage_import_native likewise, and
+ *     snesimage_batch_create, snesimage_group_create, snesimage_shared_create and snesimage_shared_create_backdrop refuse a
+ *     blocked member with SNES_ERR_UNSUPPORTED;
+ *   - everything else reads tile_palettes and never writes it, so it works unchanged and leaves the table as it found it:
+ *     steps, snesimage_run_slots, guided calls and sweeps, snesimage_recalculate_palettes, the backdrop slot, ordered dither
+ *     and level sweeps, the character budget, refit and tilemap JSON, snesimage_export_native and snesimage_render_native
+ *     (characters stay 8 x 8 cells).
+ * BLOCK MOVES decided by the objective are the tile call and the tile sweep above with "tile_palettes[t] := k" read as "every
+ * tile of block b := k": ascending k != cur (cur = the block's subpalette), optimize(), error(), strict < against the
+ * incumbent, the state of the winning candidate taken whole; a pair naming the block's current subpalette returns the incumbent
+ * bit for bit; with --dither a candidate is the whole Floyd-Steinberg run under its own tile table.  They work on every
+ * context: at 1 x 1 a block is a tile and the three calls equal the tile calls bit for bit.  Windows, stats, log and refusals
+ * are those of snesimage_tile_sweep with blocks for tiles (a block beyond the image's (32/bw)*((h/8)/bh): SNES_ERR_ARG). */
+int32_t snesimage_set_palette_blocks(snesimage_ctx *ctx, uint32_t bw, uint32_t bh);
+int32_t snesimage_get_palette_blocks(snesimage_ctx *ctx, uint32_t *bw, uint32_t *bh);
+int32_t snesimage_score_block_moves(snesimage_ctx *ctx, const uint16_t *blocks, const uint8_t *subs, uint32_t n,
+                                    double *errors, uint8_t *maps_out);
+int32_t snesimage_block_step(snesimage_ctx *ctx, uint32_t block, snesimage_tile_result *out);
+int32_t snesimage_block_sweep(snesimage_ctx *ctx, uint32_t first_block, uint32_t n_blocks, uint32_t window,
+                              snesimage_tile_result *log, snesimage_run_stats *stats);
+
 /* The character budget — NOT a reference method.  The JSON gives every tile its own 64 indices; the SNES has 64 KB of VRAM for
  * all layers, and a 256 x 224 picture of 896 distinct 4bpp characters takes 28 KB of it.  These calls count the distinct
  * characters of the result, merge tiles until at most N are left — each merge chosen by error() itself — and write the tilemap

@@ -87,6 +87,11 @@ SIGNATURES = [
     ("snesimage_tile_step", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(TileResult)]),
     ("snesimage_tile_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
     ("snesimage_shared_tile_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
+    ("snesimage_set_palette_blocks", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("snesimage_get_palette_blocks", C.c_int32, [C.c_void_p, _u32p, _u32p]),
+    ("snesimage_score_block_moves", C.c_int32, [C.c_void_p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),
+    ("snesimage_block_step", C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(TileResult)]),
+    ("snesimage_block_sweep", C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TileResult), C.POINTER(RunStats)]),
     ("snesimage_characters", C.c_int32, [C.c_void_p, _u32p, _u16p, _u8p, _u8p]),
     ("snesimage_merge_shortlist", C.c_int32, [C.c_void_p, C.c_uint32, _u16p, _u16p, _u8p, _u64p, _u32p]),
     ("snesimage_score_merges", C.c_int32, [C.c_void_p, _u16p, _u16p, _u8p, C.c_uint32, _f64p, _u8p]),

@@ -229,6 +229,55 @@ class OptimizedImage:
         out = np.array([(r.error, r.sub, r.changed) for r in log[:n_tiles]], dtype=TILE_LOG_DTYPE)
         return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
 
+    # -- palette blocks (not in the reference; include/snesimage_hip.h) ----------------------------------------------
+    @property
+    def palette_blocks(self):
+        """(bw, bh): the tiles that share one subpalette — (1, 1) per tile, (2, 2) an NES attribute area or an SNES 16 x 16 tile,
+        up to (8, 8) a 64 x 64 object.  Setting it needs a tile_palettes that is constant over the new blocks (a fresh context is)."""
+        bw, bh = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.snesimage_get_palette_blocks(self._c, C.byref(bw), C.byref(bh)))
+        return bw.value, bh.value
+
+    @palette_blocks.setter
+    def palette_blocks(self, v):
+        bw, bh = v
+        self._chk(self._L.snesimage_set_palette_blocks(self._c, int(bw), int(bh)))
+
+    def _nblock(self):
+        bw, bh = self.palette_blocks
+        return (32 // bw) * ((self.h // 8) // bh)
+
+    def score_block_moves(self, blocks, subs, want_maps=False):
+        """error() of the image with every tile of block blocks[j] drawn from subpalette subs[j], for every j; the state is
+        left unchanged.  Returns errors (float64), or (errors, maps[n, h, w]) with want_maps."""
+        blocks = np.ascontiguousarray(blocks, np.uint16).reshape(-1)
+        subs = np.ascontiguousarray(subs, np.uint8).reshape(-1)
+        if blocks.size != subs.size:
+            raise ValueError("blocks and subs differ in length")
+        errs = np.zeros(blocks.size, np.float64)
+        maps = np.zeros((blocks.size, self.h, self.w), np.uint8) if want_maps else None
+        self._chk(self._L.snesimage_score_block_moves(self._c, _p(blocks, _ffi._u16p), _p(subs, _ffi._u8p), blocks.size, _p(errs, _ffi._f64p),
+                                                      _p(maps, _ffi._u8p) if want_maps else None))
+        return (errs, maps) if want_maps else errs
+
+    def block_step(self, block):
+        """One block call: the block moves to the subpalette with the strictly lowest error(), if one beats the incumbent.
+        Returns (error, sub, changed)."""
+        r = _ffi.TileResult()
+        self._chk(self._L.snesimage_block_step(self._c, int(block), C.byref(r)))
+        return r.error, r.sub, int(r.changed)
+
+    def block_sweep(self, first_block=0, n_blocks=None, window=0):
+        """Block calls on first_block .. first_block + n_blocks - 1 in order, several per launch set (bit-identical to
+        `block_step` per block for every `window`, as `tile_sweep`).  Returns (log, stats), one record per block."""
+        if n_blocks is None:
+            n_blocks = self._nblock() - int(first_block)
+        log = (_ffi.TileResult * max(1, n_blocks))()
+        stats = _ffi.RunStats()
+        self._chk(self._L.snesimage_block_sweep(self._c, int(first_block), int(n_blocks), int(window), log, C.byref(stats)))
+        out = np.array([(r.error, r.sub, r.changed) for r in log[:n_blocks]], dtype=TILE_LOG_DTYPE)
+        return out, {k: getattr(stats, k) for k in ("calls", "accepted", "windows", "voided", "scored", "useful")}
+
     # -- the character budget (not in the reference; include/snesimage_hip.h) ---------------------------------------
     def characters(self):
         """The distinct characters of the image as it stands, equal under the tilemap's flips counted once.

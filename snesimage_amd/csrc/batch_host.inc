@@ -210,6 +210,7 @@ int32_t batch_create_members(snesimage_ctx **ctxs, uint32_t n, snesimage_batch *
         if (c->owner) return fail(SNES_ERR_STATE, "context already belongs to a batch");
         if (c->backdrop && !backdrop_ok) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
         if (c->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
+        if (blocked(c)) return fail(SNES_ERR_UNSUPPORTED, kBlockedRefused);
         if (c->device != c0->device || c->W != c0->W || c->H != c0->H || c->sub_count != c0->sub_count || c->sub_size != c0->sub_size || c->chunk != c0->chunk)
             return fail(SNES_ERR_ARG, "contexts of a batch must share device, image size, palette geometry and chunk");
         if (c->perceptual != c0->perceptual) return fail(SNES_ERR_ARG, "contexts of a batch must share their flags");

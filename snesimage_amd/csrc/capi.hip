@@ -9,6 +9,7 @@
 #include "kernels_batch.hpp"
 #include "kernels_shared.hpp"
 #include "kernels_tile.hpp"
+#include "kernels_block.hpp"
 #include "kernels_level.hpp"
 #include "kernels_char.hpp"
 #include "kernels_char_set.hpp"
@@ -250,6 +251,7 @@ struct snesimage_ctx {
     struct snesimage_window *win = nullptr;  // slot windows of snesimage_run_slots (window_host.inc), created on first use
     bool win_pend = false;                   // snesimage_slots_begin without its snesimage_slots_commit yet
     bool pack_borrowed = false;              // a slot context of a --dither window: pack and subpalette planes are the parent's
+    uint32_t pb_w = 1, pb_h = 1;               // palette blocks (block_host.inc): one subpalette per pb_w x pb_h tiles; 1 x 1: per tile
     struct snesimage_tilework *tile = nullptr; // workspace of the objective-scored tile moves (tile_host.inc), created on first use
     struct snesimage_charwork *chr = nullptr;  // workspace of the character budget (char_host.inc), created on first use
     struct snesimage_guidework *guide = nullptr; // workspace and generator of the guided calls (guide_host.inc), created on first use
@@ -1045,6 +1047,38 @@ struct SlotScope {
 // the members of a batch, a set or a group are scored by shared launches and summed or compared: one ordered-dither table for all
 bool ordered_tables_equal(const snesimage_ctx *a, const snesimage_ctx *b) { return a->od_n == b->od_n && (a->od_n == 0 || memcmp(a->od_tab, b->od_tab, (size_t)a->od_n * a->od_n) == 0); }
 const char *kLevelsRefused = "the context holds an ordered-dither bank of several tables: batches, groups and shared-palette sets share launches and one table (per-tile levels for them are not built yet)";
+// Palette blocks (snesimage_set_palette_blocks; block_host.inc): while pb_w * pb_h > 1, tile_palettes is constant over every block
+bool blocked(const snesimage_ctx *c) { return c->pb_w * c->pb_h > 1; }
+const char *kBlockedRefused = "the context holds palette blocks (snesimage_set_palette_blocks): blocked members of batches, groups and shared-palette sets are not built yet; set 1 x 1 blocks first";
+// the lowest block of the image over which `tp` is not constant, or -1
+int untied_block(const uint8_t *tp, uint32_t H, uint32_t bw, uint32_t bh) {
+    const uint32_t nbx = 32 / bw, nby = (H / 8) / bh;
+    for (uint32_t b = 0; b < nbx * nby; b++) {
+        const uint32_t tx0 = (b % nbx) * bw, ty0 = (b / nbx) * bh;
+        for (uint32_t ty = ty0; ty < ty0 + bh; ty++)
+            for (uint32_t tx = tx0; tx < tx0 + bw; tx++) if (tp[ty * 32 + tx] != tp[ty0 * 32 + tx0]) return (int)b;
+    }
+    return -1;
+}
+int block_log2(uint32_t v) { return v == 8 ? 3 : v == 4 ? 2 : v == 2 ? 1 : 0; }
+// the context's blocks; at 1 x 1 a block is a tile (nbx = 32, nblock = the image's tiles)
+struct BlockGeom { uint32_t bw, bh, nbx, nblock; int lbw, lbh; };
+BlockGeom block_geom(const snesimage_ctx *c) {
+    BlockGeom g{c->pb_w, c->pb_h, 32 / c->pb_w, (32 / c->pb_w) * ((c->H / 8) / c->pb_h), block_log2(c->pb_w), block_log2(c->pb_h)};
+    return g;
+}
+uint32_t block_first_tile(const BlockGeom &g, uint32_t b) { return (b / g.nbx) * g.bh * 32 + (b % g.nbx) * g.bw; }
+// every tile of block b := v in a host copy of tile_palettes
+void block_fill(const BlockGeom &g, uint8_t *tp, uint32_t b, uint8_t v) {
+    const uint32_t t0 = block_first_tile(g, b);
+    for (uint32_t ty = 0; ty < g.bh; ty++)
+        for (uint32_t tx = 0; tx < g.bw; tx++) tp[t0 + ty * 32 + tx] = v;
+}
+void block_move_launch(snesimage_ctx *c) {
+    const BlockGeom g = block_geom(c);
+    hipLaunchKernelGGL(k_block_move, dim3((g.nblock + 255) / 256), dim3(256), 0, c->stream, (const double *)c->d_tile_cost, (const int *)c->d_tile_any, (int)c->H, (int)c->sub_count, g.lbw, g.lbh,
+                       c->d_tile_pal, c->d_tile_moved);
+}
 const char *kBackdropRefused = "SNES_BACKDROP contexts are not supported here: the backdrop schedule is not carried through batches, groups, shared-palette sets and split-phase slot windows";
 
 int32_t batch_quiesce(struct snesimage_batch *b);
@@ -1514,6 +1548,11 @@ int32_t snesimage_get_tile_palettes(snesimage_ctx *c, uint8_t *out) {
 int32_t snesimage_set_tile_palettes(snesimage_ctx *c, const uint8_t *in) {
     if (!c || !in) return fail(SNES_ERR_ARG, "null pointer");
     for (int i = 0; i < 1024; i++) if (in[i] >= c->sub_count) return fail(SNES_ERR_ARG, "tile palette index out of range");
+    if (blocked(c)) { // the invariant of a blocked context: the table is constant over every block of the image
+        const int b = untied_block(in, c->H, c->pb_w, c->pb_h);
+        if (b >= 0) return fail(SNES_ERR_ARG, "tile_palettes is not constant over block " + std::to_string(b) + " of the context's " + std::to_string(c->pb_w) + " x " + std::to_string(c->pb_h) +
+                                              " palette blocks (snesimage_set_palette_blocks)");
+    }
     CHECK(set_device(c));
     CHECK(ensure_map(c)); // the owed optimize() belongs to the state before this change
     HIPCHK(hipMemcpyAsync(c->d_tile_pal, in, 1024, hipMemcpyHostToDevice, c->stream));
@@ -1706,6 +1745,8 @@ int32_t snesimage_reassign_tiles(snesimage_ctx *c, uint32_t *moved_out) {
     HIPCHK(hipMemsetAsync(c->d_tile_moved, 0, sizeof(unsigned int), c->stream));
     hipLaunchKernelGGL(k_tile_costs, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_target, c->d_pal_rgb8, c->d_pal_lab, c->d_labpx_t, (int)c->W, (int)c->H, (int)c->sub_count,
                        (int)c->sub_size, c->perceptual ? 1 : 0, c->d_tile_cost, c->d_tile_any);
+    if (blocked(c)) block_move_launch(c); // whole blocks, on the sums of their tiles' costs (block_host.inc)
+    else
     hipLaunchKernelGGL(k_tile_move, dim3((ntile + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost, c->d_tile_any, ntile, (int)c->sub_count, c->d_tile_pal, c->d_tile_moved);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&moved, c->d_tile_moved, sizeof(moved), hipMemcpyDeviceToHost, c->stream));
@@ -1772,6 +1813,7 @@ int32_t snesimage_debug_math(int32_t device, int32_t op, const float *x, const f
 #include "shared_window_host.inc"
 #include "group_host.inc"
 #include "tile_host.inc"
+#include "block_host.inc"
 #include "char_host.inc"
 #include "shared_char_host.inc"
 #include "export_host.inc"

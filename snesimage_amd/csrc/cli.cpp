@@ -19,6 +19,9 @@
 // --ordered-dither N [--dither-amplitude A] adds the N x N Bayer pattern of amplitude A to the picture before the nearest-colour
 // choice (include/snesimage_hip.h: snesimage_set_ordered_dither): the alternative to -d that keeps animation frames steady.
 // The JSON does not record it: a --resume run names the option again.
+// --palette-blocks WxH (include/snesimage_hip.h: "Palette blocks") gives one subpalette per block of W x H tiles instead of per
+// tile; it is set before the initialisers, --reassign-tiles then moves whole blocks and --tile-moves runs block sweeps.  The
+// JSON stays per tile and does not record it either.
 // --tile-dither K [--dither-levels L] lets every tile choose its own strength of that pattern (include/snesimage_hip.h:
 // snesimage_level_sweep): a ladder of L amplitudes from none to A, every tile starting on A; every K sweeps of the palette and
 // once behind the last call each tile is tried on every other level and kept where the error itself falls.
@@ -143,6 +146,11 @@ void usage() {
             "      --tile-moves <K>     every K sweeps of the palette, try every tile in every other subpalette and keep the moves that\n"
             "                           lower the error itself (dithering included); cannot be used with --reassign-tiles, which\n"
             "                           moves tiles by colour distance and undoes these moves, nor with --devices\n"
+            "      --palette-blocks <WxH>  one subpalette per block of W x H tiles (W, H = 1, 2, 4 or 8; H divides the image's rows of\n"
+            "                           tiles), such as 2x2 for the NES attribute table or an SNES background of 16 x 16 tiles, 4x4 or 8x8\n"
+            "                           for sprites; set before the initialisers, which then cluster blocks; --reassign-tiles then moves\n"
+            "                           whole blocks and --tile-moves tries whole blocks; not with --share, --devices or the --import-\n"
+            "                           family; the output stays per tile and does not record it: name it again with --resume\n"
             "      --guided <G>         behind every G sweeps of the palette, one guided sweep: on every slot, all 32,768 colours are ranked by what\n"
             "                           the slot's pixels would cost in colour distance, and the --guided-shortlist best are scored by the error\n"
             "                           itself; runs in front of --reassign-tiles, --tile-moves and --tile-dither; with --backdrop-fixed the\n"
@@ -388,6 +396,7 @@ int main(int argc, char **argv) {
     std::vector<int> devices; // --devices: candidate sharding over several GPUs from this one process
     std::vector<std::pair<std::string, std::string>> shares; // --share SOURCE=TARGET: images optimized with the source's palette
     bool decode_only = false;
+    bool blocks_given = false; std::string blocks_arg; uint32_t blocks_w = 1, blocks_h = 1; // --palette-blocks WxH
     uint32_t ordered_n = 0, ordered_amp = 32; bool ordered_given = false, amp_given = false; std::string ordered_arg, amp_arg;
     bool backdrop = false, backdrop_fixed = false; uint8_t backdrop_rgb[3] = {0, 0, 0}; std::string backdrop_arg;
     bool set_backdrop = false, set_backdrop_fixed = false; std::string set_backdrop_arg; // the backdrop colour of a --share set
@@ -437,6 +446,7 @@ int main(int argc, char **argv) {
         else if (a == "--reassign-tiles") reassign_every = (uint32_t)strtoul(need("--reassign-tiles"), nullptr, 10);
         else if (a == "--tile-moves") tile_every = (uint32_t)strtoul(need("--tile-moves"), nullptr, 10);
         else if (a == "--resume") resume_file = need("--resume");
+        else if (a == "--palette-blocks") { blocks_given = true; blocks_arg = need("--palette-blocks"); }
         else if (a == "--guided") { gd.given = true; gd.arg = need("--guided"); }
         else if (a == "--guided-shortlist") { gd.short_given = true; gd.short_arg = need("--guided-shortlist"); }
         else if (a == "--guided-proxy") { gd.proxy_given = true; gd.proxy_arg = need("--guided-proxy"); }
@@ -581,6 +591,15 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+    }
+    if (blocks_given) { // palette blocks: said before any file or device is touched (the height is judged once the image is read)
+        const char *bad = !shares.empty() ? "--share" : !devices.empty() ? "--devices" : import_first >= 0 ? kImportName[import_first] : set_import_first >= 0 ? kSetImportName[set_import_first] : nullptr;
+        if (bad) { fprintf(stderr, "error: the argument '--palette-blocks <WxH>' cannot be used with '%s'\n", bad); return 2; }
+        unsigned bw = 0, bh = 0; char tail = 0;
+        auto ok = [](unsigned v) { return v == 1 || v == 2 || v == 4 || v == 8; };
+        if (sscanf(blocks_arg.c_str(), "%ux%u%c", &bw, &bh, &tail) != 2 || !ok(bw) || !ok(bh)) {
+            fprintf(stderr, "error: invalid value '%s' for '--palette-blocks <WxH>': expected W and H of 1, 2, 4 or 8 tiles, such as 2x2\n", blocks_arg.c_str()); return 2; }
+        blocks_w = bw; blocks_h = bh;
     }
     if (pos.size() != 2) { fprintf(stderr, "error: the following required arguments were not provided: <SOURCE_FILENAME> <TARGET_FILENAME>\n"); usage(); return 2; }
     const std::string source = pos[0], target = pos[1];
@@ -740,6 +759,8 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> rgba;
     uint32_t w = 256, h = 256;
     load_source(source, w, h, rgba);
+    if (blocks_given && (h / 8) % blocks_h) { // known once the image is decoded: said before any device is touched
+        fprintf(stderr, "error: invalid value '%s' for '--palette-blocks <WxH>': H must divide the image's %u rows of tiles\n", blocks_arg.c_str(), h / 8); return 2; }
     if (decode_only) {
         FILE *f = fopen(target.c_str(), "wb");
         if (!f) die("cannot create " + target);
@@ -790,6 +811,10 @@ int main(int argc, char **argv) {
     snesimage_ctx *ctx = nullptr;
     if (create(rgba.data(), w, h, device, &ctx) != 0) die(snesimage_last_error());
     if (gd.proxy != SNES_GUIDE_REDMEAN && snesimage_set_guided_proxy(ctx, gd.proxy) != 0) die(snesimage_last_error()); // (before the context is lent to anything)
+    if (blocks_given) { // before the initialisers, --resume and --tile-palettes: they cluster, and are held to, the blocks
+        if (snesimage_set_palette_blocks(ctx, blocks_w, blocks_h) != 0) die(snesimage_last_error());
+        log_info("Palette blocks: one subpalette per " + std::to_string(blocks_w) + " x " + std::to_string(blocks_h) + " tiles");
+    }
     if (ordered_n) log_info("Ordered dithering: " + std::to_string(ordered_n) + " x " + std::to_string(ordered_n) + " Bayer pattern, amplitude " + std::to_string(ordered_amp));
     if (!level_amps.empty() && !set_level_opts) {
         std::string m = "Per-tile dither levels: " + std::to_string(level_amps.size()) + " levels, amplitudes";
@@ -989,12 +1014,13 @@ int main(int argc, char **argv) {
             log_info("Reassigned " + std::to_string(moved) + " tiles");
         }
         if (tile_every && step != sweep && step % tile_every == 0) { // one tile sweep over the whole image, each call decided by error()
-            const uint32_t ntile = 32 * (h / 8);
+            const uint32_t ntile = 32 * (h / 8), nblock = (32 / blocks_w) * ((h / 8) / blocks_h);
             snesimage_run_stats ts{};
             double e = 0.0;
-            if (set ? (snesimage_shared_tile_sweep(set, 0, ntile, 0, nullptr, &ts) != 0 || snesimage_shared_error(set, &e) != 0)
-                    : (snesimage_tile_sweep(ctx, 0, ntile, 0, nullptr, &ts) != 0 || snesimage_error(ctx, &e) != 0)) die(std::string("Unable to move tiles: ") + snesimage_last_error());
-            log_info("Moved " + std::to_string(ts.accepted) + " tiles in " + std::to_string(ts.windows) + " launch sets");
+            if (set          ? (snesimage_shared_tile_sweep(set, 0, ntile, 0, nullptr, &ts) != 0 || snesimage_shared_error(set, &e) != 0)
+                : blocks_given ? (snesimage_block_sweep(ctx, 0, nblock, 0, nullptr, &ts) != 0 || snesimage_error(ctx, &e) != 0) // a block sweep over all blocks
+                               : (snesimage_tile_sweep(ctx, 0, ntile, 0, nullptr, &ts) != 0 || snesimage_error(ctx, &e) != 0)) die(std::string("Unable to move tiles: ") + snesimage_last_error());
+            log_info("Moved " + std::to_string(ts.accepted) + (blocks_given ? " blocks in " : " tiles in ") + std::to_string(ts.windows) + " launch sets");
             if (std::abs(e - last_error) > 2.220446049250313e-16) { log_info("Current Error: " + fmt_f64(e)); last_error = e; }
         }
         if (level_every && step != sweep && step % level_every == 0) level_sweep(); // behind the tile moves: the levels are chosen for the subpalettes the tiles ended on

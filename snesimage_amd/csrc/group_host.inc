@@ -106,6 +106,7 @@ int32_t snesimage_group_create(snesimage_ctx **ctxs, uint32_t n, snesimage_group
         if (c->group) return fail(SNES_ERR_STATE, "context already belongs to a group");
         if (c->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
         if (c->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
+        if (blocked(c)) return fail(SNES_ERR_UNSUPPORTED, kBlockedRefused);
         if (c->W != ctxs[0]->W || c->H != ctxs[0]->H || c->sub_count != ctxs[0]->sub_count || c->sub_size != ctxs[0]->sub_size || c->dither != ctxs[0]->dither ||
             c->perceptual != ctxs[0]->perceptual)
             return fail(SNES_ERR_ARG, "contexts of a group must hold the same image geometry, palette geometry and flags");

@@ -86,6 +86,7 @@ extern "C" {
 
 int32_t snesimage_import_native(snesimage_ctx *c, const snesimage_native_layout *layout, const uint8_t *cgram, const uint8_t *chr, uint64_t chr_bytes, const uint16_t *map, snesimage_native_info *info) {
     CHECK(char_check(c));
+    if (blocked(c)) return fail(SNES_ERR_UNSUPPORTED, "snesimage_import_native: the context holds palette blocks (snesimage_set_palette_blocks) and native data carries a palette per tile; set 1 x 1 blocks first");
     if (!cgram || !chr || !map) return fail(SNES_ERR_ARG, "null pointer");
     snes::NativeLayout L{};
     CHECK(export_layout(layout, c->user_size, c->sub_count, &L));

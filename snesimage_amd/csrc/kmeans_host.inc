@@ -170,6 +170,8 @@ int32_t kmeans_recalculate_palettes(snesimage_ctx *c) { // lib.rs:407-415
     return SNES_OK;
 }
 
+// On a context with palette blocks (snesimage_set_palette_blocks) the block stands in the tile's place: sums over the block's
+// pixels, points in block order (bx outer, by inner), every tile of a clustered block assigned.  At 1 x 1 a block is a tile.
 int32_t kmeans_initialize_tiles(snesimage_ctx *c) { // lib.rs:79-189
     if (c->sub_count == 1) {
         CHECK(kmeans_recalculate(c, std::vector<uint32_t>{0}));
@@ -178,11 +180,15 @@ int32_t kmeans_initialize_tiles(snesimage_ctx *c) { // lib.rs:79-189
         return SNES_OK;
     }
     if (c->perceptual) CHECK(ensure_source(c));
-    const uint32_t wt = c->W / 8, ht = c->H / 8, ntile = wt * ht;
+    const BlockGeom g = block_geom(c);
+    const uint32_t wt = g.nbx, ht = g.nblock / g.nbx, ntile = g.nblock; // the units that are clustered: tiles, or blocks of them
     CHECK(kmeans_reserve(c, 1, 1, (int)c->sub_count));
     float *d_sums = c->km.d_sums; int *d_counts = c->km.d_counts; // (ntile <= 1,024)
     std::vector<float> sums(3 * (size_t)ntile); std::vector<int> counts(ntile);
     auto body0 = [&]() -> int32_t {
+        if (blocked(c)) hipLaunchKernelGGL(k_block_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, (const uint8_t *)c->d_orig, (const float *)c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0,
+                                           g.lbw, g.lbh, d_sums, d_counts);
+        else
         hipLaunchKernelGGL(k_tile_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, c->d_orig, c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0, d_sums, d_counts);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(sums.data(), d_sums, sizeof(float) * sums.size(), hipMemcpyDeviceToHost, c->stream));
@@ -212,7 +218,7 @@ int32_t kmeans_initialize_tiles(snesimage_ctx *c) { // lib.rs:79-189
     std::vector<uint8_t> tp(1024);
     HIPCHK(hipMemcpyAsync(tp.data(), c->d_tile_pal, 1024, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (size_t t = 0; t < map.size(); t++) tp[map[t]] = (uint8_t)assign[t]; // lib.rs:133-138
+    for (size_t t = 0; t < map.size(); t++) block_fill(g, tp.data(), map[t], (uint8_t)assign[t]); // lib.rs:133-138 (a unit left out keeps what it had)
     std::vector<uint8_t> col(3 * (size_t)c->ncol);
     if (c->backdrop) { HIPCHK(hipMemcpyAsync(col.data(), c->d_colors, col.size(), hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); } // (B stays)
     for (int i = 0; i < k; i++) {

@@ -310,6 +310,7 @@ int32_t snesimage_shared_create(snesimage_ctx **ctxs, uint32_t n, snesimage_shar
         if (ctxs[i]->group) return fail(SNES_ERR_STATE, "context belongs to a group");
         if (ctxs[i]->backdrop) return fail(SNES_ERR_UNSUPPORTED, kBackdropRefused);
         if (ctxs[i]->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
+        if (blocked(ctxs[i])) return fail(SNES_ERR_UNSUPPORTED, kBlockedRefused);
         for (uint32_t j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(SNES_ERR_ARG, "a context appears twice in the set");
     }
     // the batch checks the rest (device, size, geometry, chunk, flags, the group-sparse path) and readies every member
@@ -344,6 +345,7 @@ int32_t snesimage_shared_create_backdrop(snesimage_ctx **ctxs, uint32_t n, const
         if (ctxs[i]->group) return fail(SNES_ERR_STATE, "context belongs to a group");
         if (!ctxs[i]->backdrop) return fail(SNES_ERR_ARG, "member " + std::to_string(i) + " was created without SNES_BACKDROP: a set of plain contexts is made by snesimage_shared_create");
         if (ctxs[i]->od_L > 1) return fail(SNES_ERR_ARG, kLevelsRefused);
+        if (blocked(ctxs[i])) return fail(SNES_ERR_UNSUPPORTED, kBlockedRefused);
         for (uint32_t j = 0; j < i; j++) if (ctxs[j] == ctxs[i]) return fail(SNES_ERR_ARG, "a context appears twice in the set");
     }
     if (backdrop_rgb5 && (backdrop_rgb5[0] > 31 || backdrop_rgb5[1] > 31 || backdrop_rgb5[2] > 31)) return fail(SNES_ERR_ARG, "backdrop channels are 5-bit values");

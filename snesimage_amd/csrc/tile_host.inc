@@ -118,9 +118,13 @@ void tile_score_head(snesimage_ctx *c, uint32_t nc) {
     hipLaunchKernelGGL(k_candidate_tables, dim3((nc + 63) / 64), dim3(64), 0, st, t.zero_rgb5, (int)nc, c->d_eotf, t.cand_tab);
     hipLaunchKernelGGL(k_candidate_slot, dim3((nc + 63) / 64), dim3(64), 0, st, t.cand_tab, (int)nc, 0xffffffffu); // no colour index is "the candidate's"
 }
-int32_t tile_score_tail(snesimage_ctx *c, uint32_t nc, double *d_errors) {
+// g: the pairs are (block, subpalette) of a block move (block_host.inc), t.tiles holds block indices
+int32_t tile_score_tail(snesimage_ctx *c, uint32_t nc, double *d_errors, const BlockGeom *g = nullptr) {
     snesimage_tilework &t = *c->tile;
     hipStream_t st = c->stream;
+    if (g) hipLaunchKernelGGL(k_block_full, dim3((unsigned)((c->npx / 4 + 255) / 256), nc), dim3(256), 0, st, (const uint8_t *)t.lmaps, (const uint8_t *)c->d_tile_pal, (const uint16_t *)t.tiles,
+                              (const uint8_t *)t.subs, (int)c->W, (int)c->H, (int)c->sub_size, g->lbw, g->lbh, t.maps, t.mapsC4);
+    else
     hipLaunchKernelGGL(k_tile_full, dim3((unsigned)((c->npx / 4 + 255) / 256), nc), dim3(256), 0, st, (const uint8_t *)t.lmaps, (const uint8_t *)c->d_tile_pal, (const uint16_t *)t.tiles,
                        (const uint8_t *)t.subs, (int)c->W, (int)c->H, (int)c->sub_size, t.maps, t.mapsC4);
     const bool fast0 = (c->fast_mask & 1) != 0;
@@ -133,34 +137,51 @@ int32_t tile_score_tail(snesimage_ctx *c, uint32_t nc, double *d_errors) {
     return SNES_OK;
 }
 
+// The candidates' Floyd-Steinberg runs, each under its own tile table (t.tabs, written by the caller): maps into t.lmaps
+void tile_dither_launch(snesimage_ctx *c, uint32_t nc) {
+    snesimage_tilework &t = *c->tile;
+    hipStream_t st = c->stream;
+    DitherParams Dp{};
+    Dp.orig = c->d_orig; Dp.tile_pal = c->d_tile_pal; Dp.pal_rgb8 = c->d_pal_rgb8; Dp.pal_lab = c->d_pal_lab; Dp.cand_tab = t.cand_tab; Dp.cand_lab = nullptr;
+    Dp.lab_eotf = c->d_lab_eotf; Dp.maps = t.lmaps; Dp.mapsC4 = nullptr;
+    Dp.W = (int)c->W; Dp.H = (int)c->H; Dp.sub_size = (int)c->sub_size; Dp.ncol = c->ncol; Dp.slot_ci = 0xffffffffu; Dp.perceptual = c->perceptual ? 1 : 0;
+    const bool quad = c->dither4 && nc <= c->dither4_max; // as launch_dither: a quad of lanes per row while the runs are few
+    if (c->perceptual && quad) hipLaunchKernelGGL((k_dither4_tile<0, true>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
+    else if (c->perceptual) hipLaunchKernelGGL((k_dither_tile<true, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
+    else if (quad && c->sub_size == 15) hipLaunchKernelGGL((k_dither4_tile<15, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
+    else if (quad && c->sub_size == 16) hipLaunchKernelGGL((k_dither4_tile<16, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
+    else if (quad) hipLaunchKernelGGL((k_dither4_tile<0, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
+    else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither_tile<false, 15>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
+    else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither_tile<false, 16>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
+    else hipLaunchKernelGGL((k_dither_tile<false, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
+}
+
 // nc candidates, pairs at t.tiles / t.subs [0, nc): maps into t.lmaps, errors into d_errors[0, nc)
-int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors) {
+// g: block moves — the candidates' tables and maps come from k_block_tabs / k_block_remap, everything else is shared
+int32_t tile_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors, const BlockGeom *g = nullptr) {
     snesimage_tilework &t = *c->tile;
     hipStream_t st = c->stream;
     tile_score_head(c, nc);
     if (c->dither) {
+        if (g) hipLaunchKernelGGL(k_block_tabs, dim3(nc), dim3(256), 0, st, (const uint8_t *)c->d_tile_pal, (const uint16_t *)t.tiles, (const uint8_t *)t.subs, g->lbw, g->lbh, t.tabs);
+        else
         hipLaunchKernelGGL(k_tile_tabs, dim3(nc), dim3(256), 0, st, c->d_tile_pal, t.tiles, t.subs, t.tabs);
-        DitherParams Dp{};
-        Dp.orig = c->d_orig; Dp.tile_pal = c->d_tile_pal; Dp.pal_rgb8 = c->d_pal_rgb8; Dp.pal_lab = c->d_pal_lab; Dp.cand_tab = t.cand_tab; Dp.cand_lab = nullptr;
-        Dp.lab_eotf = c->d_lab_eotf; Dp.maps = t.lmaps; Dp.mapsC4 = nullptr;
-        Dp.W = (int)c->W; Dp.H = (int)c->H; Dp.sub_size = (int)c->sub_size; Dp.ncol = c->ncol; Dp.slot_ci = 0xffffffffu; Dp.perceptual = c->perceptual ? 1 : 0;
-        const bool quad = c->dither4 && nc <= c->dither4_max; // as launch_dither: a quad of lanes per row while the runs are few
-        if (c->perceptual && quad) hipLaunchKernelGGL((k_dither4_tile<0, true>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
-        else if (c->perceptual) hipLaunchKernelGGL((k_dither_tile<true, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
-        else if (quad && c->sub_size == 15) hipLaunchKernelGGL((k_dither4_tile<15, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
-        else if (quad && c->sub_size == 16) hipLaunchKernelGGL((k_dither4_tile<16, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
-        else if (quad) hipLaunchKernelGGL((k_dither4_tile<0, false>), dim3(nc), dim3(512), 0, st, Dp, (const uint8_t *)t.tabs);
-        else if (c->sub_size == 15) hipLaunchKernelGGL((k_dither_tile<false, 15>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
-        else if (c->sub_size == 16) hipLaunchKernelGGL((k_dither_tile<false, 16>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
-        else hipLaunchKernelGGL((k_dither_tile<false, 0>), dim3(nc), dim3(128), 0, st, Dp, (const uint8_t *)t.tabs);
+        tile_dither_launch(c, nc);
+    } else if (g) {
+        BlockRemapParams R{};
+        R.orig = c->d_target; R.base_map = base_map; R.pal_rgb8 = c->d_pal_rgb8; R.pal_lab = c->d_pal_lab; R.labpx = c->d_labpx_t;
+        R.blocks = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps; R.W = (int)c->W; R.H = (int)c->H; R.sub_size = (int)c->sub_size; R.perceptual = c->perceptual ? 1 : 0; R.lbw = g->lbw; R.lbh = g->lbh;
+        hipLaunchKernelGGL(k_block_remap, dim3(nc), dim3(256), 0, st, R);
     } else {
         TileRemapParams R{};
         R.orig = c->d_target; R.base_map = base_map; R.tile_pal = c->d_tile_pal; R.pal_rgb8 = c->d_pal_rgb8; R.pal_lab = c->d_pal_lab; R.labpx = c->d_labpx_t;
         R.tiles = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps; R.W = (int)c->W; R.H = (int)c->H; R.sub_size = (int)c->sub_size; R.perceptual = c->perceptual ? 1 : 0;
         hipLaunchKernelGGL(k_tile_remap, dim3(nc), dim3(256), 0, st, R);
     }
-    return tile_score_tail(c, nc, d_errors);
+    return tile_score_tail(c, nc, d_errors, g);
 }
+
+const char *kTileOnBlocks = "the context holds palette blocks (snesimage_set_palette_blocks): a single-tile move would leave a block with two subpalettes; use ";
 
 int32_t tile_check(snesimage_ctx *c) {
     if (!c) return fail(SNES_ERR_ARG, "null context");
@@ -168,10 +189,12 @@ int32_t tile_check(snesimage_ctx *c) {
     return SNES_OK;
 }
 
-int32_t tile_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats) {
+// g: a block sweep (block_host.inc) — "tile" reads "block": the calls walk blocks, a candidate moves every tile of its block
+// and k_block_commit writes the accepted block's table entries; the window policy and the state flags are one and the same
+int32_t tile_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats, const BlockGeom *g = nullptr) {
     CHECK(tile_check(c));
-    const uint32_t ntile = (c->W / 8) * (c->H / 8);
-    if (first_tile > ntile || n_tiles > ntile - first_tile) return fail(SNES_ERR_ARG, "tile range beyond the image");
+    const uint32_t ntile = g ? g->nblock : (c->W / 8) * (c->H / 8);
+    if (first_tile > ntile || n_tiles > ntile - first_tile) return fail(SNES_ERR_ARG, g ? "block range beyond the image" : "tile range beyond the image");
     CHECK(set_device(c));
     snesimage_run_stats S{};
     if (n_tiles == 0) { if (stats) *stats = S; return SNES_OK; }
@@ -202,7 +225,7 @@ int32_t tile_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles,
         const uint32_t k = K < n_tiles - pos ? K : n_tiles - pos;
         h_tiles.clear(); h_subs.clear(); h_calls.clear();
         for (uint32_t i = 0; i < k; i++) {
-            const uint32_t tile = first_tile + pos + i, cur = tp[tile];
+            const uint32_t tile = first_tile + pos + i, cur = tp[g ? block_first_tile(*g, tile) : tile];
             snes::TileCall tc{tile, (uint32_t)h_tiles.size(), m, cur};
             for (uint32_t s = 0; s < c->sub_count; s++) if (s != cur) { h_tiles.push_back((uint16_t)tile); h_subs.push_back((uint8_t)s); }
             h_calls.push_back(tc);
@@ -211,7 +234,10 @@ int32_t tile_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles,
         HIPCHK(hipMemcpyAsync(t.tiles, h_tiles.data(), sizeof(uint16_t) * nc, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(t.subs, h_subs.data(), nc, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(t.calls, h_calls.data(), sizeof(snes::TileCall) * k, hipMemcpyHostToDevice, c->stream));
-        CHECK(tile_score_group(c, nc, base_map, t.errs));
+        CHECK(tile_score_group(c, nc, base_map, t.errs, g));
+        if (g) hipLaunchKernelGGL(k_block_commit, dim3(1), dim3(1024), 0, c->stream, (const double *)t.errs, (const snes::TileCall *)t.calls, (int)k, (const uint8_t *)t.subs, (const uint8_t *)t.lmaps,
+                                  (int)c->npx, g->lbw, g->lbh, c->d_tile_pal, c->d_map, c->d_inc_err, reinterpret_cast<snes::TileLog *>(t.result + 16), reinterpret_cast<snes::TileWinRes *>(t.result));
+        else
         hipLaunchKernelGGL(k_tile_commit, dim3(1), dim3(1024), 0, c->stream, (const double *)t.errs, (const snes::TileCall *)t.calls, (int)k, (const uint8_t *)t.subs, (const uint8_t *)t.lmaps,
                            (int)c->npx, c->d_tile_pal, c->d_map, c->d_inc_err, reinterpret_cast<snes::TileLog *>(t.result + 16), reinterpret_cast<snes::TileWinRes *>(t.result));
         HIPCHK(hipGetLastError());
@@ -220,13 +246,14 @@ int32_t tile_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles,
         HIPCHK(hipStreamSynchronize(c->stream)); // the one synchronisation of the window
         snes::TileWinRes res; memcpy(&res, h_res.data(), sizeof(res));
         const uint32_t used = (uint32_t)res.consumed;
-        if (used < 1 || used > k) return fail(SNES_ERR_HIP, "tile window: bad commit record");
+        if (used < 1 || used > k) return fail(SNES_ERR_HIP, g ? "block window: bad commit record" : "tile window: bad commit record");
         const snes::TileLog *recs = reinterpret_cast<const snes::TileLog *>(h_res.data() + 16);
         if (log) memcpy(log + pos, recs, sizeof(snes::TileLog) * used);
         S.calls += used; S.windows += 1; S.scored += nc; S.useful += (uint64_t)used * m;
         if (res.accepted >= 0) { // as snesimage_set_tile_palettes + snesimage_optimize would leave it, with the incumbent error known
             S.accepted += 1;
-            tp[first_tile + pos + (uint32_t)res.accepted] = (uint8_t)recs[res.accepted].sub;
+            if (g) block_fill(*g, tp.data(), first_tile + pos + (uint32_t)res.accepted, (uint8_t)recs[res.accepted].sub);
+            else tp[first_tile + pos + (uint32_t)res.accepted] = (uint8_t)recs[res.accepted].sub;
             c->pack_valid = false; c->sp.plist_valid = false; c->epoch++; c->epoch_by_commit = false;
             c->map_synced = true; c->map_pending = false; c->inc_valid = true; c->best_valid = false;
             base_map = c->d_map;
@@ -244,6 +271,7 @@ extern "C" {
 
 int32_t snesimage_score_tile_moves(snesimage_ctx *c, const uint16_t *tiles, const uint8_t *subs, uint32_t n, double *errors, uint8_t *maps_out) {
     CHECK(tile_check(c));
+    if (blocked(c)) return fail(SNES_ERR_UNSUPPORTED, kTileOnBlocks + std::string("snesimage_score_block_moves"));
     if (!tiles || !subs || !errors) return fail(SNES_ERR_ARG, "null pointer");
     if (n == 0) return SNES_OK;
     const uint32_t ntile = (c->W / 8) * (c->H / 8);
@@ -270,12 +298,14 @@ int32_t snesimage_score_tile_moves(snesimage_ctx *c, const uint16_t *tiles, cons
 
 int32_t snesimage_tile_step(snesimage_ctx *c, uint32_t tile, snesimage_tile_result *out) {
     snesimage_tile_result r{};
+    if (c && blocked(c)) return fail(SNES_ERR_UNSUPPORTED, kTileOnBlocks + std::string("snesimage_block_step"));
     CHECK(tile_sweep_impl(c, tile, 1, 1, &r, nullptr));
     if (out) *out = r;
     return SNES_OK;
 }
 
 int32_t snesimage_tile_sweep(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats) {
+    if (c && blocked(c)) return fail(SNES_ERR_UNSUPPORTED, kTileOnBlocks + std::string("snesimage_block_sweep"));
     return tile_sweep_impl(c, first_tile, n_tiles, window, log, stats);
 }
 
