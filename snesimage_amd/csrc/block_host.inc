@@ -1,12 +1,11 @@
 // snesimage_amd/csrc/block_host.inc — palette blocks: snesimage_set_palette_blocks / _get_palette_blocks, the blocked k-means
 // initialiser and proxy reassignment, and the block moves decided by the objective: snesimage_score_block_moves,
-// snesimage_block_step, snesimage_block_sweep (definition: include/snesimage_hip.h; kernels: kernels_block.hpp).
+// snesimage_block_step, snesimage_block_sweep (definition: include/snesimage_hip.h; kernels: kernels_tile.hpp).
 //
-// A block move is a tile move with every tile of the block changing hands, so it runs through the tile moves' own host code
-// (tile_host.inc: tile_prepare, tile_score_group, tile_sweep_impl) with the context's BlockGeom handed in: t.tiles then holds
-// block indices and the k_block_* kernels stand in for k_tile_tabs, k_tile_remap, k_tile_full and k_tile_commit.  The blocked
-// initialiser is kmeans_initialize_tiles (kmeans_host.inc) and the blocked reassignment snesimage_reassign_tiles (capi.hip), each
-// with the block kernel in the tile kernel's place.  Included by capi.hip behind tile_host.inc.
+// A tile move is the move of a 1 x 1 block, so both run through one host code (tile_host.inc: move_score_list, tile_sweep_impl)
+// and one kernel family (k_move_*, k_unit_*): the block entry points hand in the context's BlockGeom, the tile entry points
+// tile_geom.  The blocked initialiser is kmeans_initialize_tiles (kmeans_host.inc) and the blocked reassignment
+// snesimage_reassign_tiles (capi.hip), on the context's geometry too.  Included by capi.hip behind tile_host.inc.
 
 extern "C" {
 
@@ -38,43 +37,20 @@ int32_t snesimage_get_palette_blocks(snesimage_ctx *c, uint32_t *bw, uint32_t *b
 
 int32_t snesimage_score_block_moves(snesimage_ctx *c, const uint16_t *blocks, const uint8_t *subs, uint32_t n, double *errors, uint8_t *maps_out) {
     CHECK(tile_check(c));
-    if (!blocks || !subs || !errors) return fail(SNES_ERR_ARG, "null pointer");
-    if (n == 0) return SNES_OK;
-    const BlockGeom g = block_geom(c);
-    for (uint32_t j = 0; j < n; j++) {
-        if (blocks[j] >= g.nblock) return fail(SNES_ERR_ARG, "block beyond the image");
-        if (subs[j] >= c->sub_count) return fail(SNES_ERR_ARG, "subpalette out of range");
-    }
-    CHECK(set_device(c));
-    const uint32_t group = n < tile_group(c) ? n : tile_group(c);
-    const uint8_t *base_map = nullptr;
-    CHECK(tile_prepare(c, group, &base_map));
-    snesimage_tilework &t = *c->tile;
-    for (uint32_t c0 = 0; c0 < n; c0 += group) {
-        const uint32_t nc = n - c0 < group ? n - c0 : group;
-        HIPCHK(hipMemcpyAsync(t.tiles, blocks + c0, sizeof(uint16_t) * nc, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(t.subs, subs + c0, nc, hipMemcpyHostToDevice, c->stream));
-        CHECK(tile_score_group(c, nc, base_map, t.errs, &g));
-        HIPCHK(hipMemcpyAsync(errors + c0, t.errs, sizeof(double) * nc, hipMemcpyDeviceToHost, c->stream));
-        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out + (size_t)c0 * c->npx, t.lmaps, c->npx * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SNES_OK;
+    return move_score_list(c, blocks, subs, n, errors, maps_out, block_geom(c), "block");
 }
 
 int32_t snesimage_block_step(snesimage_ctx *c, uint32_t block, snesimage_tile_result *out) {
     snesimage_tile_result r{};
     if (!c) return fail(SNES_ERR_ARG, "null context");
-    const BlockGeom g = block_geom(c);
-    CHECK(tile_sweep_impl(c, block, 1, 1, &r, nullptr, &g));
+    CHECK(tile_sweep_impl(c, block, 1, 1, &r, nullptr, block_geom(c), "block"));
     if (out) *out = r;
     return SNES_OK;
 }
 
 int32_t snesimage_block_sweep(snesimage_ctx *c, uint32_t first_block, uint32_t n_blocks, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats) {
     if (!c) return fail(SNES_ERR_ARG, "null context");
-    const BlockGeom g = block_geom(c);
-    return tile_sweep_impl(c, first_block, n_blocks, window, log, stats, &g);
+    return tile_sweep_impl(c, first_block, n_blocks, window, log, stats, block_geom(c), "block");
 }
 
 } // extern "C"

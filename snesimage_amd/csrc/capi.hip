@@ -9,7 +9,6 @@
 #include "kernels_batch.hpp"
 #include "kernels_shared.hpp"
 #include "kernels_tile.hpp"
-#include "kernels_block.hpp"
 #include "kernels_level.hpp"
 #include "kernels_char.hpp"
 #include "kernels_char_set.hpp"
@@ -1067,6 +1066,8 @@ BlockGeom block_geom(const snesimage_ctx *c) {
     BlockGeom g{c->pb_w, c->pb_h, 32 / c->pb_w, (32 / c->pb_w) * ((c->H / 8) / c->pb_h), block_log2(c->pb_w), block_log2(c->pb_h)};
     return g;
 }
+// the 1 x 1 geometry, whatever blocks the context holds: what the tile entry points and every (tile, option) pair hand in
+BlockGeom tile_geom(const snesimage_ctx *c) { return BlockGeom{1, 1, 32, 32 * (c->H / 8), 0, 0}; }
 uint32_t block_first_tile(const BlockGeom &g, uint32_t b) { return (b / g.nbx) * g.bh * 32 + (b % g.nbx) * g.bw; }
 // every tile of block b := v in a host copy of tile_palettes
 void block_fill(const BlockGeom &g, uint8_t *tp, uint32_t b, uint8_t v) {
@@ -1074,9 +1075,10 @@ void block_fill(const BlockGeom &g, uint8_t *tp, uint32_t b, uint8_t v) {
     for (uint32_t ty = 0; ty < g.bh; ty++)
         for (uint32_t tx = 0; tx < g.bw; tx++) tp[t0 + ty * 32 + tx] = v;
 }
+// the proxy reassignment of snesimage_reassign_tiles: whole blocks on the sums of their tiles' costs; at 1 x 1, tiles
 void block_move_launch(snesimage_ctx *c) {
     const BlockGeom g = block_geom(c);
-    hipLaunchKernelGGL(k_block_move, dim3((g.nblock + 255) / 256), dim3(256), 0, c->stream, (const double *)c->d_tile_cost, (const int *)c->d_tile_any, (int)c->H, (int)c->sub_count, g.lbw, g.lbh,
+    hipLaunchKernelGGL(k_unit_move, dim3((g.nblock + 255) / 256), dim3(256), 0, c->stream, (const double *)c->d_tile_cost, (const int *)c->d_tile_any, (int)c->H, (int)c->sub_count, g.lbw, g.lbh,
                        c->d_tile_pal, c->d_tile_moved);
 }
 const char *kBackdropRefused = "SNES_BACKDROP contexts are not supported here: the backdrop schedule is not carried through batches, groups, shared-palette sets and split-phase slot windows";
@@ -1745,9 +1747,7 @@ int32_t snesimage_reassign_tiles(snesimage_ctx *c, uint32_t *moved_out) {
     HIPCHK(hipMemsetAsync(c->d_tile_moved, 0, sizeof(unsigned int), c->stream));
     hipLaunchKernelGGL(k_tile_costs, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_target, c->d_pal_rgb8, c->d_pal_lab, c->d_labpx_t, (int)c->W, (int)c->H, (int)c->sub_count,
                        (int)c->sub_size, c->perceptual ? 1 : 0, c->d_tile_cost, c->d_tile_any);
-    if (blocked(c)) block_move_launch(c); // whole blocks, on the sums of their tiles' costs (block_host.inc)
-    else
-    hipLaunchKernelGGL(k_tile_move, dim3((ntile + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost, c->d_tile_any, ntile, (int)c->sub_count, c->d_tile_pal, c->d_tile_moved);
+    block_move_launch(c);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&moved, c->d_tile_moved, sizeof(moved), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

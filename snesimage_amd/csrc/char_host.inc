@@ -112,7 +112,7 @@ int32_t char_score_group(snesimage_ctx *c, uint32_t nc, double *d_errors) {
     tile_score_head(c, nc);
     hipLaunchKernelGGL(k_merge_maps, dim3(nc), dim3(256), 0, c->stream, (const unsigned long long *)c->chr->keys, (const uint8_t *)c->d_map, (const uint8_t *)c->d_tile_pal, (int)c->W, (int)c->npx,
                        t.lmaps, t.tiles, t.subs);
-    return tile_score_tail(c, nc, d_errors);
+    return tile_score_tail(c, nc, d_errors, tile_geom(c));
 }
 
 int32_t char_shortlist_len(uint32_t *k) {
@@ -150,7 +150,7 @@ int32_t refit_score_group(snesimage_ctx *c, uint32_t nc, double *d_errors) {
     tile_score_head(c, nc);
     hipLaunchKernelGGL(k_refit_maps, dim3(nc), dim3(256), 0, c->stream, (const uint16_t *)w.rcalls, (const uint8_t *)c->d_map, (const uint16_t *)w.rep, (const uint8_t *)w.flip, (const uint8_t *)w.fits,
                        (const uint8_t *)c->d_tile_pal, (int)c->W, (int)c->npx, t.lmaps, t.tiles, t.subs);
-    return tile_score_tail(c, nc, d_errors);
+    return tile_score_tail(c, nc, d_errors, tile_geom(c));
 }
 
 } // namespace

@@ -32,6 +32,20 @@ SNES_HD long long idx_c4(int x, int y, int H) { return ((long long)(x >> 2) * H 
 SNES_HD long long idx_r4(int x, int y, int W) { return ((long long)(y >> 2) * W + x) * 4 + (y & 3); }   // [y/4][x][y%4]
 SNES_HD long long idx_xt4(int x, int y, int H) { return ((((long long)(x >> 6) * (H >> 2)) + (y >> 2)) << 8) + ((x & 63) << 2) + (y & 3); } // [x/64][y/4][x%64][y%4]
 
+// A palette_map (npx bytes, a multiple of 16) copied by the NT threads of a block; copy_map_sync then holds the block at a
+// barrier, so that the copy is in place before a caller replaces some of its bytes ("copy the base map, then patch").
+template <int NT>
+__device__ __forceinline__ void copy_map(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, int npx) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    for (int i = threadIdx.x; i < npx / 16; i += NT) d[i] = s[i];
+}
+template <int NT>
+__device__ __forceinline__ void copy_map_sync(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, int npx) {
+    copy_map<NT>(dst, src, npx);
+    __syncthreads();
+}
+
 struct BlurK { // recursive-Gaussian constants (host-computed in binary64, rounded to f32)
     float n2[3];   // MUL_IN_k = VERT_MUL_IN_k
     float d1[3];   // VERT_MUL_PREV_k; MUL_PREV_k = -d1

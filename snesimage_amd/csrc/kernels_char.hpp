@@ -177,7 +177,7 @@ __global__ __launch_bounds__(1024) void k_merge_topk(const unsigned long long *_
 }
 
 // A candidate's palette_map: the stored map with tile t's 64 pixels taken from tile b under flip f; and the candidate's
-// (tile, subpalette) pair for k_tile_full — the tile keeps its subpalette.  grid = candidates, block 256.
+// (tile, subpalette) pair for k_move_full — the tile keeps its subpalette.  grid = candidates, block 256.
 __global__ __launch_bounds__(256) void k_merge_maps(const unsigned long long *__restrict__ keys, const uint8_t *__restrict__ base_map, const uint8_t *__restrict__ tile_pal, int W, int npx,
                                                    uint8_t *__restrict__ lmaps, uint16_t *__restrict__ tiles, uint8_t *__restrict__ subs) {
     const int cand = blockIdx.x, tid = threadIdx.x;
@@ -190,10 +190,7 @@ __global__ __launch_bounds__(256) void k_merge_maps(const unsigned long long *__
         px = ((t >> 5) * 8 + y) * W + (t & 31) * 8 + x;
         mine = base_map[((b >> 5) * 8 + sy) * W + (b & 31) * 8 + sx];
     }
-    const uint4 *src = reinterpret_cast<const uint4 *>(base_map);
-    uint4 *dst = reinterpret_cast<uint4 *>(lmaps + (size_t)cand * npx);
-    for (int i = tid; i < npx / 16; i += 256) dst[i] = src[i];
-    __syncthreads(); // the copy of the tile's rows is in place before its 64 bytes are replaced
+    copy_map_sync<256>(lmaps + (size_t)cand * npx, base_map, npx); // the copy of the tile's rows is in place before its 64 bytes are replaced
     if (tid < 64 && inside) lmaps[(size_t)cand * npx + px] = mine;
     if (tid == 0) { tiles[cand] = (uint16_t)t; subs[cand] = tile_pal[t]; }
 }
@@ -309,7 +306,7 @@ __global__ __launch_bounds__(256) void k_refit_fit(const uint8_t *__restrict__ o
 }
 
 // A refit candidate's palette_map: the stored map with every member m of class reps[cand] rewritten to
-// fitted[p ^ mask(flip[m])]; and the pair (rep, its own subpalette) for k_tile_full, which so substitutes nothing.
+// fitted[p ^ mask(flip[m])]; and the pair (rep, its own subpalette) for k_move_full, which so substitutes nothing.
 // grid = candidates, block 256: a wave per member tile, a lane per pixel.
 __global__ __launch_bounds__(256) void k_refit_maps(const uint16_t *__restrict__ reps, const uint8_t *__restrict__ base_map, const uint16_t *__restrict__ rep, const uint8_t *__restrict__ flip,
                                                    const uint8_t *__restrict__ fits, const uint8_t *__restrict__ tile_pal, int W, int npx, uint8_t *__restrict__ lmaps,
@@ -317,10 +314,7 @@ __global__ __launch_bounds__(256) void k_refit_maps(const uint16_t *__restrict__
     const int cand = blockIdx.x, tid = threadIdx.x, ntile = npx >> 6;
     int r = reps[cand];
     r = r < ntile ? r : 0; // (the host hands over representatives of the image only)
-    const uint4 *src = reinterpret_cast<const uint4 *>(base_map);
-    uint4 *dst = reinterpret_cast<uint4 *>(lmaps + (size_t)cand * npx);
-    for (int i = tid; i < npx / 16; i += 256) dst[i] = src[i];
-    __syncthreads(); // the copy is in place before the members' bytes are replaced
+    copy_map_sync<256>(lmaps + (size_t)cand * npx, base_map, npx); // the copy is in place before the members' bytes are replaced
     const int p = tid & 63;
     for (int u = tid >> 6; u < ntile; u += 4) {
         if ((int)rep[u] != r) continue; // (the same for the whole wave)

@@ -199,10 +199,7 @@ __global__ __launch_bounds__(256) void ks_merge_maps(const unsigned long long *_
         px = tile_px(t, tid, W);
         mine = tab[mb].map[((b >> 5) * 8 + sy) * W + (b & 31) * 8 + sx];
     }
-    const uint4 *src = reinterpret_cast<const uint4 *>(base_map);
-    uint4 *dst = reinterpret_cast<uint4 *>(lmaps + (size_t)cand * npx);
-    for (int i = tid; i < npx / 16; i += 256) dst[i] = src[i];
-    __syncthreads(); // the copy of the tile's rows is in place before its 64 bytes are replaced
+    copy_map_sync<256>(lmaps + (size_t)cand * npx, base_map, npx); // the copy of the tile's rows is in place before its 64 bytes are replaced
     if (tid < 64 && inside) lmaps[(size_t)cand * npx + px] = mine;
     if (tid == 0) { tiles[cand] = (uint16_t)(inside ? t : 0); subs[cand] = tab[member].tile_pal[inside ? t : 0]; }
 }
@@ -343,17 +340,14 @@ __global__ __launch_bounds__(256) void ks_refit_fit(const SetMember *__restrict_
 
 // One member's refit candidates, into that member's tile workspace: the member's stored map with every tile of class
 // reps[cand] THAT LIES IN THIS MEMBER rewritten to fitted[p ^ mask(flip)]; and the pair (tile 0, its own subpalette) for
-// k_tile_full, which so substitutes nothing.  grid = the member's candidates, block 256: a wave per tile, a lane per pixel.
+// k_move_full, which so substitutes nothing.  grid = the member's candidates, block 256: a wave per tile, a lane per pixel.
 __global__ __launch_bounds__(256) void ks_refit_maps(const uint16_t *__restrict__ reps, const SetMember *__restrict__ tab, int member, int ntile, int G, int W, int npx,
                                                     const uint16_t *__restrict__ rep, const uint8_t *__restrict__ flip, const uint8_t *__restrict__ fits, uint8_t *__restrict__ lmaps,
                                                     uint16_t *__restrict__ tiles, uint8_t *__restrict__ subs) {
     const int cand = blockIdx.x, tid = threadIdx.x;
     int r = reps[cand];
     r = r < G ? r : 0; // (the host hands over representatives of the set only)
-    const uint4 *src = reinterpret_cast<const uint4 *>(tab[member].map);
-    uint4 *dst = reinterpret_cast<uint4 *>(lmaps + (size_t)cand * npx);
-    for (int i = tid; i < npx / 16; i += 256) dst[i] = src[i];
-    __syncthreads(); // the copy is in place before the class's bytes are replaced
+    copy_map_sync<256>(lmaps + (size_t)cand * npx, tab[member].map, npx); // the copy is in place before the class's bytes are replaced
     const int p = tid & 63, g0 = member * ntile;
     for (int u = tid >> 6; u < ntile; u += 4) {
         if ((int)rep[g0 + u] != r) continue; // (the same for the whole wave)

@@ -1051,25 +1051,7 @@ __global__ __launch_bounds__(1024) void k_kmeans(KmParams P) {
     if (t == 0) P.rounds[prob] = round;
 }
 
-// per-tile f32 sums in the reference's order (tile pixels x outer, y inner; lib.rs:91-116)
-__global__ void k_tile_sums(const uint8_t *__restrict__ orig, const float *__restrict__ labpx, int W, int H, int perceptual, float *__restrict__ sums /*[tiles][3]*/, int *__restrict__ counts) {
-    int tile = blockIdx.x * blockDim.x + threadIdx.x;
-    int wt = W / 8, ht = H / 8;
-    if (tile >= wt * ht) return;
-    int tx = tile % wt, ty = tile / wt;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f; int cnt = 0;
-    for (int x = 0; x < 8; x++)
-        for (int y = 0; y < 8; y++) {
-            size_t px = (size_t)(ty * 8 + y) * W + tx * 8 + x;
-            uint32_t o = reinterpret_cast<const uint32_t *>(orig)[px];
-            if ((o >> 24) != 0) {
-                if (perceptual) { s0 += labpx[3 * px]; s1 += labpx[3 * px + 1]; s2 += labpx[3 * px + 2]; }
-                else { s0 += (float)(o & 0xff); s1 += (float)((o >> 8) & 0xff); s2 += (float)((o >> 16) & 0xff); }
-                cnt++;
-            }
-        }
-    sums[3 * tile] = s0; sums[3 * tile + 1] = s1; sums[3 * tile + 2] = s2; counts[tile] = cnt;
-}
+// (the per-tile f32 sums of initialize_tiles: k_unit_sums of kernels_tile.hpp)
 // gather k-means points from a pixel index list (RGB as f64, or Lab f32 widened to f64; lib.rs:344-358)
 __global__ void k_gather_points(const uint8_t *__restrict__ orig, const float *__restrict__ labpx, const uint32_t *__restrict__ index, long long n, int perceptual, double *__restrict__ pts) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1116,15 +1098,7 @@ __global__ void k_tile_costs(const uint8_t *__restrict__ orig, const uint32_t *_
     cost[i] = c;
     if (p == 0) any[tile] = a;
 }
-// the move: strictly smallest cost, scanning upwards from the current subpalette's (ties keep the current one, then the lower index)
-__global__ void k_tile_move(const double *__restrict__ cost, const int *__restrict__ any, int ntile, int sub_count, uint8_t *__restrict__ tile_pal, unsigned int *__restrict__ moved) {
-    const int tile = blockIdx.x * blockDim.x + threadIdx.x;
-    if (tile >= ntile || !any[tile]) return;
-    const int cur = tile_pal[tile];
-    int best = cur;
-    for (int p = 0; p < sub_count; p++) if (cost[tile * sub_count + p] < cost[tile * sub_count + best]) best = p;
-    if (best != cur) { tile_pal[tile] = (uint8_t)best; atomicAdd(moved, 1u); }
-}
+// (the move over these costs, by tile or by block: k_unit_move of kernels_tile.hpp)
 
 // ---- kernel entry points of the bodies above ----
 template <bool PERC, int SUB, int MODE = 0, int NT = 128>

@@ -186,10 +186,8 @@ int32_t kmeans_initialize_tiles(snesimage_ctx *c) { // lib.rs:79-189
     float *d_sums = c->km.d_sums; int *d_counts = c->km.d_counts; // (ntile <= 1,024)
     std::vector<float> sums(3 * (size_t)ntile); std::vector<int> counts(ntile);
     auto body0 = [&]() -> int32_t {
-        if (blocked(c)) hipLaunchKernelGGL(k_block_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, (const uint8_t *)c->d_orig, (const float *)c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0,
-                                           g.lbw, g.lbh, d_sums, d_counts);
-        else
-        hipLaunchKernelGGL(k_tile_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, c->d_orig, c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0, d_sums, d_counts);
+        hipLaunchKernelGGL(k_unit_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, (const uint8_t *)c->d_orig, (const float *)c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0, g.lbw, g.lbh,
+                           d_sums, d_counts);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(sums.data(), d_sums, sizeof(float) * sums.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(counts.data(), d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, c->stream));

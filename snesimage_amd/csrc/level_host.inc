@@ -84,7 +84,7 @@ int32_t level_score_pairs(snesimage_ctx *c, const uint16_t *ltiles, const uint8_
     R.ltiles = ltiles; R.llevels = llevels; R.tiles = t.tiles; R.subs = t.subs; R.lmaps = t.lmaps;
     R.W = (int)c->W; R.H = (int)c->H; R.sub_size = (int)c->sub_size; R.perceptual = c->perceptual ? 1 : 0; R.n = (int)c->od_n;
     hipLaunchKernelGGL(k_level_remap, dim3(nc), dim3(256), 0, c->stream, R, level_bank(c));
-    return tile_score_tail(c, nc, d_errors);
+    return tile_score_tail(c, nc, d_errors, tile_geom(c)); // (the pair k_level_remap wrote is the tile with its own subpalette)
 }
 // ... the pairs in the context's own arrays
 int32_t level_score_group(snesimage_ctx *c, uint32_t nc, const uint8_t *base_map, double *d_errors) { return level_score_pairs(c, c->lvl->ltiles, c->lvl->llevels, nc, base_map, d_errors); }
@@ -95,40 +95,22 @@ int32_t level_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles
     CHECK(set_device(c));
     if (n_tiles == 0) return SNES_OK;
     const uint32_t m = c->od_L - 1; // candidates per call
-    uint32_t kmax = m ? tile_group(c) / m : n_tiles;
-    if (kmax < 1) kmax = 1;
-    if (kmax > n_tiles) kmax = n_tiles;
-    if (window == 1) kmax = 1; else if (window > 1 && window < kmax) kmax = window;
+    const uint32_t kmax = window_limit(tile_group(c), m, n_tiles, window);
     const uint8_t *base_map = nullptr;
     CHECK(tile_prepare(c, (kmax * m > 0 ? kmax * m : 1), &base_map));
-    if (m == 0) { // one table: no candidates, nothing accepted
-        double inc = 0.0;
-        HIPCHK(hipMemcpyAsync(&inc, c->d_inc_err, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (log) for (uint32_t i = 0; i < n_tiles; i++) { log[i].error = inc; log[i].sub = 0; log[i].changed = 0; }
-        S.calls = n_tiles;
-        return SNES_OK;
-    }
+    if (m == 0) return window_idle_ctx(c, n_tiles, log, S); // one table
     CHECK(level_alloc(c, kmax * m));
     snesimage_tilework &t = *c->tile;
     snesimage_levelwork &w = *c->lvl;
-    uint32_t K = window == 0 ? (w.adapt < kmax ? w.adapt : kmax) : kmax;
-    if (K < 1) K = 1;
-    std::vector<uint16_t> h_tiles; std::vector<uint8_t> h_levels; std::vector<snes::TileCall> h_calls; std::vector<unsigned char> h_res;
+    uint32_t K = window_first(window, w.adapt, kmax);
+    WindowCalls wc;
     uint32_t pos = 0;
     while (pos < n_tiles) {
         const uint32_t k = K < n_tiles - pos ? K : n_tiles - pos;
-        h_tiles.clear(); h_levels.clear(); h_calls.clear();
-        for (uint32_t i = 0; i < k; i++) {
-            const uint32_t tile = first_tile + pos + i, cur = c->od_level[tile];
-            snes::TileCall tc{tile, (uint32_t)h_tiles.size(), m, cur};
-            for (uint32_t l = 0; l < c->od_L; l++) if (l != cur) { h_tiles.push_back((uint16_t)tile); h_levels.push_back((uint8_t)l); }
-            h_calls.push_back(tc);
-        }
-        const uint32_t nc = (uint32_t)h_tiles.size();
-        HIPCHK(hipMemcpyAsync(w.ltiles, h_tiles.data(), sizeof(uint16_t) * nc, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(w.llevels, h_levels.data(), nc, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(t.calls, h_calls.data(), sizeof(snes::TileCall) * k, hipMemcpyHostToDevice, c->stream));
+        const uint32_t nc = window_build(wc, first_tile + pos, k, c->od_L, [&](uint32_t tile) { return (uint32_t)c->od_level[tile]; });
+        HIPCHK(hipMemcpyAsync(w.ltiles, wc.units.data(), sizeof(uint16_t) * nc, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(w.llevels, wc.opts.data(), nc, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(t.calls, wc.calls.data(), sizeof(snes::TileCall) * k, hipMemcpyHostToDevice, c->stream));
         CHECK(level_score_group(c, nc, base_map, t.errs));
         snes::LevelCommitParams P{};
         P.errs = t.errs; P.calls = t.calls; P.ncalls = (int)k; P.llevels = w.llevels; P.lmaps = t.lmaps; P.npx = (int)c->npx;
@@ -136,19 +118,10 @@ int32_t level_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles
         P.orig = c->d_orig; P.lab_eotf = c->d_lab_eotf; P.n = (int)c->od_n; P.W = (int)c->W; P.H = (int)c->H;
         P.target = c->d_target_own; P.labpx = c->perceptual ? c->d_labpx_t_own : nullptr; P.labpxT = c->perceptual ? c->d_labpxT_t_own : nullptr;
         hipLaunchKernelGGL(k_level_commit, dim3(1), dim3(1024), 0, c->stream, P, level_bank(c));
-        HIPCHK(hipGetLastError());
-        h_res.resize(16 + sizeof(snes::TileLog) * (size_t)k);
-        HIPCHK(hipMemcpyAsync(h_res.data(), t.result, h_res.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream)); // the one synchronisation of the window
-        snes::TileWinRes res; memcpy(&res, h_res.data(), sizeof(res));
-        const uint32_t used = (uint32_t)res.consumed;
-        if (used < 1 || used > k) return fail(SNES_ERR_HIP, "level window: bad commit record");
-        const snes::TileLog *recs = reinterpret_cast<const snes::TileLog *>(h_res.data() + 16);
-        if (log) memcpy(log + pos, recs, sizeof(snes::TileLog) * used);
-        S.calls += used; S.windows += 1; S.scored += nc; S.useful += (uint64_t)used * m;
-        if (res.accepted >= 0) { // as snesimage_set_tile_levels + snesimage_optimize would leave it, with the incumbent error known
-            S.accepted += 1;
-            c->od_level[first_tile + pos + (uint32_t)res.accepted] = (uint8_t)recs[res.accepted].sub;
+        WindowOutcome o{};
+        CHECK(window_read_record(c->stream, t.result, wc.res, k, nc, m, 1, "level window", log ? log + pos : nullptr, S, o));
+        if (o.accepted >= 0) { // as snesimage_set_tile_levels + snesimage_optimize would leave it, with the incumbent error known
+            c->od_level[first_tile + pos + (uint32_t)o.accepted] = o.opt;
             c->pack_valid = false; c->sp.plist_valid = false; c->sp.counters_cleared = false; c->epoch++; c->epoch_by_commit = false;
             c->map_synced = true; c->map_pending = false; c->inc_valid = true; c->best_valid = false;
             // (the workspace's planes stay: with maps handed in the scorer takes the transparency marker from them and nothing else, and T.a == orig.a)
@@ -157,8 +130,8 @@ int32_t level_sweep_impl(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles
                     for (snesimage_ctx *kc : set) { kc->pack_valid = false; kc->sp.plist_valid = false; kc->sp.counters_cleared = false; }
             base_map = c->d_map;
         }
-        pos += used;
-        if (window == 0) { K = w.policy.next(used, res.accepted >= 0 ? 1u : 0u, kmax < 2 ? kmax : 2u, kmax, 1, k, 0.2 * (double)m); if (K > kmax) K = kmax; if (K < 1) K = 1; w.adapt = K; }
+        pos += o.used;
+        K = window_next(window, K, w.policy, w.adapt, o, kmax, k, 0.2 * (double)m);
     }
     return SNES_OK;
 }
@@ -224,17 +197,7 @@ int32_t snesimage_score_tile_levels(snesimage_ctx *c, const uint16_t *tiles, con
     const uint8_t *base_map = nullptr;
     CHECK(tile_prepare(c, group, &base_map));
     CHECK(level_alloc(c, group));
-    snesimage_tilework &t = *c->tile;
-    for (uint32_t c0 = 0; c0 < n; c0 += group) {
-        const uint32_t nc = n - c0 < group ? n - c0 : group;
-        HIPCHK(hipMemcpyAsync(c->lvl->ltiles, tiles + c0, sizeof(uint16_t) * nc, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->lvl->llevels, levels + c0, nc, hipMemcpyHostToDevice, c->stream));
-        CHECK(level_score_group(c, nc, base_map, t.errs));
-        HIPCHK(hipMemcpyAsync(errors + c0, t.errs, sizeof(double) * nc, hipMemcpyDeviceToHost, c->stream));
-        if (maps_out) HIPCHK(hipMemcpyAsync(maps_out + (size_t)c0 * c->npx, t.lmaps, c->npx * (size_t)nc, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return SNES_OK;
+    return score_pair_groups(c, tiles, levels, n, group, c->lvl->ltiles, c->lvl->llevels, errors, maps_out, [&](uint32_t nc) { return level_score_group(c, nc, base_map, c->tile->errs); });
 }
 
 int32_t snesimage_level_sweep(snesimage_ctx *c, uint32_t first_tile, uint32_t n_tiles, uint32_t window, snesimage_tile_result *log, snesimage_run_stats *stats) {

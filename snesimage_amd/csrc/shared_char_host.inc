@@ -154,7 +154,7 @@ int32_t sc_score_member(snesimage_shared *s, uint32_t m, uint32_t nc) {
     tile_score_head(c, nc);
     hipLaunchKernelGGL(ks_merge_maps, dim3(nc), dim3(256), 0, c->stream, (const unsigned long long *)(w.mkeys + (size_t)m * kCharShort), (const snes::SetMember *)w.tab, (int)m, (int)sc_ntile(s),
                        (int)w.F, (int)c->W, (int)c->npx, t.lmaps, t.tiles, t.subs);
-    return tile_score_tail(c, nc, t.errs);
+    return tile_score_tail(c, nc, t.errs, tile_geom(c));
 }
 
 } // namespace

@@ -178,7 +178,8 @@ int32_t shared_kmeans_initialize_tiles(snesimage_shared *s) {
         snesimage_ctx *c = M[i];
         if (c->perceptual) CHECK(ensure_source(c));
         CHECK(kmeans_reserve(c, 1, 1, (int)c->sub_count));
-        hipLaunchKernelGGL(k_tile_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, c->d_orig, c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0, c->km.d_sums, c->km.d_counts);
+        hipLaunchKernelGGL(k_unit_sums, dim3((ntile + 63) / 64), dim3(64), 0, c->stream, (const uint8_t *)c->d_orig, (const float *)c->d_labpx, (int)c->W, (int)c->H, c->perceptual ? 1 : 0, 0, 0,
+                           c->km.d_sums, c->km.d_counts); // (the members of a set hold 1 x 1 blocks: tiles)
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(sums[i].data(), c->km.d_sums, sizeof(float) * sums[i].size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(counts[i].data(), c->km.d_counts, sizeof(int) * counts[i].size(), hipMemcpyDeviceToHost, c->stream));

@@ -107,26 +107,21 @@ int32_t sl_tied_sweep(snesimage_shared *s, uint32_t first_tile, uint32_t n_tiles
     auto &M = members(s);
     snesimage_ctx *c0 = M[0];
     const uint32_t F = (uint32_t)M.size(), m = c0->od_L - 1; // candidates per call
-    uint32_t kmax = m ? sl_group(s) / m : n_tiles;
-    if (kmax < 1) kmax = 1;
-    if (kmax > n_tiles) kmax = n_tiles;
-    if (window == 1) kmax = 1; else if (window > 1 && window < kmax) kmax = window;
+    const uint32_t kmax = window_limit(sl_group(s), m, n_tiles, window);
     if (m) CHECK(sl_alloc(s, kmax * m)); // (every allocation comes before the first commit)
     CHECK(sl_prepare(s, kmax * m > 0 ? kmax * m : 1, m != 0));
     hipStream_t st = s->b->stream;
     if (m == 0) { // one table: no candidates, nothing accepted
         std::vector<double> inc; double E = 0.0;
         CHECK(sr_incumbents(s, inc, &E));
-        if (log) for (uint32_t i = 0; i < n_tiles; i++) { log[i].error = E; log[i].sub = 0; log[i].changed = 0; }
-        S.calls = n_tiles;
+        window_idle(n_tiles, E, log, S);
         return SNES_OK;
     }
     snesimage_sharedlevel &w = *s->lvl;
-    uint32_t K = window == 0 ? (w.adapt < kmax ? w.adapt : kmax) : kmax;
-    if (K < 1) K = 1;
+    uint32_t K = window_first(window, w.adapt, kmax);
     struct Flags { bool pack_valid, plist_valid, map_synced, map_pending, inc_valid, best_valid, epoch_by_commit; };
     std::vector<Flags> saved(F);
-    std::vector<uint16_t> h_tiles; std::vector<uint8_t> h_levels; std::vector<snes::TileCall> h_calls; std::vector<unsigned char> h_res;
+    WindowCalls wc;
     ScStreams on_set(s);
     // One window.  From the launch of the commit on, every member's stored map may be a candidate's: the flags say "a stored map
     // of unknown error" before anything can fail.  Once the records are read, an accepted call leaves every member as
@@ -134,16 +129,10 @@ int32_t sl_tied_sweep(snesimage_shared *s, uint32_t first_tile, uint32_t n_tiles
     uint32_t pos = 0;
     while (pos < n_tiles) {
         const uint32_t k = K < n_tiles - pos ? K : n_tiles - pos;
-        h_tiles.clear(); h_levels.clear(); h_calls.clear();
-        for (uint32_t i = 0; i < k; i++) {
-            const uint32_t tile = first_tile + pos + i, cur = c0->od_level[tile]; // (every member is on it: checked before any work, kept by every commit)
-            snes::TileCall tc{tile, (uint32_t)h_tiles.size(), m, cur};
-            for (uint32_t l = 0; l < c0->od_L; l++) if (l != cur) { h_tiles.push_back((uint16_t)tile); h_levels.push_back((uint8_t)l); }
-            h_calls.push_back(tc);
-        }
-        const uint32_t nc = (uint32_t)h_tiles.size();
-        HIPCHK(hipMemcpyAsync(w.calls, h_calls.data(), sizeof(snes::TileCall) * k, hipMemcpyHostToDevice, st));
-        CHECK(sl_enqueue(s, h_tiles.data(), h_levels.data(), nc));
+        // (every member is on c0's level: checked before any work, kept by every commit)
+        const uint32_t nc = window_build(wc, first_tile + pos, k, c0->od_L, [&](uint32_t tile) { return (uint32_t)c0->od_level[tile]; });
+        HIPCHK(hipMemcpyAsync(w.calls, wc.calls.data(), sizeof(snes::TileCall) * k, hipMemcpyHostToDevice, st));
+        CHECK(sl_enqueue(s, wc.units.data(), wc.opts.data(), nc));
         for (uint32_t i = 0; i < F; i++) {
             snesimage_ctx *c = M[i];
             saved[i] = Flags{c->pack_valid, c->sp.plist_valid, c->map_synced, c->map_pending, c->inc_valid, c->best_valid, c->epoch_by_commit};
@@ -156,20 +145,12 @@ int32_t sl_tied_sweep(snesimage_shared *s, uint32_t first_tile, uint32_t n_tiles
         P.tab = w.tab; P.F = (int)F; P.calls = w.calls; P.ncalls = (int)k; P.ncand = (int)nc; P.llevels = w.llevels; P.npx = (int)c0->npx; P.n = (int)c0->od_n; P.W = (int)c0->W; P.H = (int)c0->H;
         P.log = reinterpret_cast<snes::TileLog *>(w.result + 16); P.res = reinterpret_cast<snes::TileWinRes *>(w.result);
         hipLaunchKernelGGL(ks_level_commit, dim3(1), dim3(1024), 0, st, P, level_bank(c0));
-        HIPCHK(hipGetLastError());
-        h_res.resize(16 + sizeof(snes::TileLog) * (size_t)k);
-        HIPCHK(hipMemcpyAsync(h_res.data(), w.result, h_res.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st)); // the one synchronisation of the window
-        snes::TileWinRes res; memcpy(&res, h_res.data(), sizeof(res));
-        const uint32_t used = (uint32_t)res.consumed;
-        if (used < 1 || used > k || res.accepted >= (int32_t)used) return fail(SNES_ERR_HIP, "level window of the set: bad commit record");
-        const snes::TileLog *recs = reinterpret_cast<const snes::TileLog *>(h_res.data() + 16);
-        if (log) memcpy(log + pos, recs, sizeof(snes::TileLog) * used);
-        S.calls += used; S.windows += 1; S.scored += (uint64_t)nc * F; S.useful += (uint64_t)used * m * F;
+        WindowOutcome o{};
+        CHECK(window_read_record(st, w.result, wc.res, k, nc, m, F, "level window of the set", log ? log + pos : nullptr, S, o));
         for (uint32_t i = 0; i < F; i++) {
             snesimage_ctx *c = M[i];
-            if (res.accepted >= 0) { // as snesimage_shared_set_tile_levels + optimize() would leave the member, with the incumbent error known
-                c->od_level[first_tile + pos + (uint32_t)res.accepted] = (uint8_t)recs[res.accepted].sub;
+            if (o.accepted >= 0) { // as snesimage_shared_set_tile_levels + optimize() would leave the member, with the incumbent error known
+                c->od_level[first_tile + pos + (uint32_t)o.accepted] = o.opt;
                 c->sp.counters_cleared = false; c->map_synced = true; c->inc_valid = true;
                 if (c->win)
                     for (auto &set : c->win->child)
@@ -181,9 +162,9 @@ int32_t sl_tied_sweep(snesimage_shared *s, uint32_t first_tile, uint32_t n_tiles
             c->epoch_by_commit = f.epoch_by_commit; c->epoch--; s->epoch[i] = c->epoch;
         }
         s->reduced = false; // every stored map is the optimize() of the palette against its member's T again
-        if (res.accepted >= 0) { S.accepted += 1; sl_reach_slots(s); }
-        pos += used;
-        if (window == 0) { K = w.policy.next(used, res.accepted >= 0 ? 1u : 0u, kmax < 2 ? kmax : 2u, kmax, 1, k, 0.2 * (double)m * (double)F); if (K > kmax) K = kmax; if (K < 1) K = 1; w.adapt = K; }
+        if (o.accepted >= 0) sl_reach_slots(s);
+        pos += o.used;
+        K = window_next(window, K, w.policy, w.adapt, o, kmax, k, 0.2 * (double)m * (double)F);
     }
     return SNES_OK;
 }

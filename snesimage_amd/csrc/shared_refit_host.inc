@@ -106,7 +106,7 @@ int32_t sr_enqueue(snesimage_shared *s, const SrWindow &win) {
         tile_score_head(c, nc);
         hipLaunchKernelGGL(ks_refit_maps, dim3(nc), dim3(256), 0, c->stream, (const uint16_t *)(w.rmreps + (size_t)m * kCharShort), (const snes::SetMember *)w.tab, (int)m, (int)sc_ntile(s), (int)w.G,
                            (int)c->W, (int)c->npx, (const uint16_t *)w.rep, (const uint8_t *)w.flip, (const uint8_t *)w.rfits, t.lmaps, t.tiles, t.subs);
-        CHECK(tile_score_tail(c, nc, t.errs));
+        CHECK(tile_score_tail(c, nc, t.errs, tile_geom(c)));
     }
     return SNES_OK;
 }

@@ -8,6 +8,7 @@ import block_model as BM
 #        id                  h   count size bw bh  flags                               image
 CASES = [
     ("16_2x2",              16,  4,    3,   2, 2, {},                                  "synth"),   # one block row
+    ("16_2x1",              16,  4,    3,   2, 1, {},                                  "synth"),   # 128 pixels: half of the remap's 256 threads, rows of 16
     ("32_2x2_alpha",        32,  4,    7,   2, 2, {},                                  "alpha"),
     ("32_4x2_perceptual",   32,  2,    3,   4, 2, {"perceptual": True},                "synth"),   # with the next: bw / bh exchanged
     ("32_2x4",              32,  4,    3,   2, 4, {},                                  "synth"),
