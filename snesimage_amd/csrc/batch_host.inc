@@ -162,6 +162,7 @@ int32_t enqueue_batched_scoring(hipStream_t st, const snes::BatchArgs *A, uint32
     // are K images x 12 lists of them: a grid sized for the worst case is mostly blocks that find nothing to do
     { size_t gx = ((size_t)n * 8 * 3 + 15) / 16; if (gx > c0->sp.hgrid) gx = c0->sp.hgrid; if (gx < 8) gx = 8;
       if (quad) hipLaunchKernelGGL(kb_sparse_h2q, dim3((unsigned)(gx * 4), (unsigned)(s_first * kColBuckets), K), dim3(64), h2_lds(c0), st, A, dead);
+      else if (two && (c0->sp.h_forms & 1)) { if (s_first > 1) hipLaunchKernelGGL(kb_sparse_h2_from, dim3((unsigned)gx, (unsigned)((s_first - 1) * kColBuckets), K), dim3(64), h2_lds(c0), st, A, dead, (int)kColBuckets); }
       else if (two) { if (s_first > 1) hipLaunchKernelGGL(kb_sparse_h2_lists, dim3((unsigned)gx, (unsigned)((s_first - 1) * kColBuckets), K), dim3(64), h2_lds(c0), st, A, dead, (int)kColBuckets); }
       else hipLaunchKernelGGL(kb_sparse_h2, dim3((unsigned)gx, (unsigned)(s_first * kColBuckets), K), dim3(64), h2_lds(c0), st, A, dead);
       if (s_first < G.nscales) hipLaunchKernelGGL(kb_sparse_h, dim3((unsigned)((gx + 7) / 8), (unsigned)((G.nscales - s_first) * kColBuckets), K), dim3(64), 0, st, A, 0, dead); }

@@ -208,6 +208,12 @@ struct snesimage_ctx {
         // and r1 are fetched once for both (kernels_sparse2.hpp, sparse_v2_pair_body).  SNES_V2_PAIR=0: one candidate
         // per wave, the launch and the grid as they were.
         bool v2_pair = true;
+        // The candidates' long H pass in a kernel per form, each at its own register count (kernels_sparse2.hpp, "One kernel per
+        // form").  SNES_H_FORMS, a bit mask: 1 = scales 1.. behind the downscale in a kernel that holds their body alone
+        // (k_sparse_h2_from, kb_sparse_h2_from); 2 = scale 0's map input (--dither) decided by the launch, not in the kernel;
+        // 4 = scale 0's one-plane waves in a kernel of their own in front of the full form's.  0: the kernels of every form.
+        // The default is the bits that measured as gains; bit 2 costs what a second tail costs and stays off.
+        uint32_t h_forms = 3;
         // SNES_DEBUG_POISON=1 (a debug aid, off by default): every call fills its candidates' storage with 0xFF bytes (binary32
         // NaNs) before anything of the call writes it, so that a read of a plane the H pass left out shows as a NaN error instead of
         // hiding behind a stale finite value with a zero weight.
@@ -655,6 +661,29 @@ SparseParams sparse_params(snesimage_ctx *c, uint32_t lane) {
 
 static size_t h2_lds(const snesimage_ctx *c) { return sizeof(float) * 3 * (size_t)(c->ncol + 2); } // k_sparse_h2's palette table in LDS
 
+// The candidates' long H pass over the lists of grid.y = ny (from list 0), gx blocks per list at most, by SNES_H_FORMS:
+// bit 1 picks the kernel by the context's dither flag (which is what sets P.use_maps); bit 2, where the launch is scale 0's
+// alone (h0_only) and some but not all channels take the one-plane form, launches that form's waves and the full form's as two
+// kernels, each with its share of the blocks (the full form's has the wave that straddles the two: one block more).
+static void launch_sparse_h2(const snesimage_ctx *c, const SparseParams &P, size_t gx, unsigned ny, bool h0_only, hipStream_t st) {
+    const uint32_t forms = c->sp.h_forms;
+    const size_t lds = h2_lds(c);
+    const int nfree = h2_free_channels(c->G);
+    if ((forms & 4) && h0_only && P.h_planes && !P.full_sums && nfree > 0 && nfree < 3) {
+        size_t g1 = gx * (size_t)nfree / 3; if (g1 < 1) g1 = 1;
+        const size_t g2 = gx - gx * (size_t)nfree / 3 + 1;
+        const dim3 d1((unsigned)g1, ny), d2((unsigned)g2, ny);
+        if (!(forms & 2)) { hipLaunchKernelGGL(k_sparse_h2_one<-1>, d1, dim3(64), lds, st, P); hipLaunchKernelGGL(k_sparse_h2_full<-1>, d2, dim3(64), lds, st, P); }
+        else if (c->dither) { hipLaunchKernelGGL(k_sparse_h2_one<1>, d1, dim3(64), lds, st, P); hipLaunchKernelGGL(k_sparse_h2_full<1>, d2, dim3(64), lds, st, P); }
+        else { hipLaunchKernelGGL(k_sparse_h2_one<0>, d1, dim3(64), lds, st, P); hipLaunchKernelGGL(k_sparse_h2_full<0>, d2, dim3(64), lds, st, P); }
+        return;
+    }
+    const dim3 d((unsigned)gx, ny);
+    if (!(forms & 2)) hipLaunchKernelGGL(k_sparse_h2, d, dim3(64), lds, st, P);
+    else if (c->dither) hipLaunchKernelGGL(k_sparse_h2_um<true>, d, dim3(64), lds, st, P);
+    else hipLaunchKernelGGL(k_sparse_h2_um<false>, d, dim3(64), lds, st, P);
+}
+
 // B of the current slot: compact list of contested pixels, then the pipeline once with checkpoints (main stream)
 int32_t sparse_base_pass(snesimage_ctx *c, int sp_idx, int si, uint32_t n_cand) { // n_cand: candidates of the call (decides where B's downscale runs)
     auto &sp = c->sp;
@@ -828,7 +857,7 @@ int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, 
         HIPCHK(hipStreamWaitEvent(hs, sp.ev_scan[lane], 0));  // the work items
         HIPCHK(hipStreamWaitEvent(hs, sp.ev_base_h, 0));      // B's H-pass checkpoints
         size_t gx = ((size_t)nc * (G.sh[0] / 4) * 3 + 15) / 16; if (gx > sp.h0_grid) gx = sp.h0_grid;
-        hipLaunchKernelGGL(k_sparse_h2, dim3((unsigned)gx, (unsigned)kColBuckets), dim3(64), h2_lds(c), hs, P); // grid.y = scale 0's lists only
+        launch_sparse_h2(c, P, gx, (unsigned)kColBuckets, true, hs); // grid.y = scale 0's lists only
         if (c->sp.lpt) hipLaunchKernelGGL(k_sparse_order, dim3(1), dim3(1024), 0, hs, P, sp.order + P.k0); // (the V pass's order needs the scan only: off the main stream)
         HIPCHK(hipEventRecord(sp.ev_h0[lane], hs));
         if (v0_aside) { // scale 0's V pass needs scale 0's H pass, B's sweeps and the order: nothing of the main stream's
@@ -856,9 +885,11 @@ int32_t sparse_score_chunk(snesimage_ctx *c, uint32_t lane, hipStream_t stream, 
           size_t gq = ((size_t)nc * (G.sh[0] / 4) * 3 + 3) / 4; if (gq > sp.hgrid) gq = sp.hgrid;
           hipLaunchKernelGGL(k_sparse_h2q, dim3((unsigned)gq, (unsigned)(P.s_first * kColBuckets)), dim3(64), h2_lds(c), stream, P);
       } else
-      if (h0_ahead) { if (P.s_first > 1) hipLaunchKernelGGL(k_sparse_h2_from, dim3((unsigned)gx, (unsigned)((P.s_first - 1) * kColBuckets)), dim3(64), h2_lds(c), stream, P, (int)kColBuckets); } // (scale 0's lists went ahead)
-      else
-      hipLaunchKernelGGL(k_sparse_h2, dim3((unsigned)gx, (unsigned)(P.s_first * kColBuckets)), dim3(64), h2_lds(c), stream, P);
+      if (h0_ahead) { // (scale 0's lists went ahead)
+          if (P.s_first > 1 && (sp.h_forms & 1)) hipLaunchKernelGGL(k_sparse_h2_from, dim3((unsigned)gx, (unsigned)((P.s_first - 1) * kColBuckets)), dim3(64), h2_lds(c), stream, P, (int)kColBuckets);
+          else if (P.s_first > 1) hipLaunchKernelGGL(k_sparse_h2_from_all, dim3((unsigned)gx, (unsigned)((P.s_first - 1) * kColBuckets)), dim3(64), h2_lds(c), stream, P, (int)kColBuckets);
+      } else
+      launch_sparse_h2(c, P, gx, (unsigned)(P.s_first * kColBuckets), false, stream);
       if (P.s_first < G.nscales) hipLaunchKernelGGL(k_sparse_h, dim3((unsigned)((gx + 7) / 8), (unsigned)((G.nscales - P.s_first) * kColBuckets)), dim3(64), 0, stream, P);
       if (vn_aside) HIPCHK(hipEventRecord(sp.ev_hn[lane], stream)); // the narrow scales' H output is in place
       if (h0_ahead) HIPCHK(hipStreamWaitEvent(stream, sp.ev_h0[lane], 0)); }
@@ -1234,6 +1265,7 @@ int32_t snesimage_create(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t s
     if (const char *e = getenv("SNES_WEIGHT_MASK")) c->sp.weight_mask = atoi(e) != 0;
     if (const char *e = getenv("SNES_H_PLANES")) c->sp.h_planes = atoi(e) != 0;
     if (const char *e = getenv("SNES_V2_PAIR")) c->sp.v2_pair = atoi(e) != 0;
+    if (const char *e = getenv("SNES_H_FORMS")) { int v = atoi(e); if (v >= 0 && v <= 7) c->sp.h_forms = (uint32_t)v; }
     if (const char *e = getenv("SNES_DEBUG_POISON")) c->sp.debug_poison = atoi(e) != 0;
     if (const char *e = getenv("SNES_DEDUP_MIN")) { int v = atoi(e); if (v >= 1) c->sp.dedup_min = (uint32_t)v; }
     Geom &G = c->G;

@@ -77,8 +77,8 @@ __device__ __forceinline__ void lds_order() { asm volatile("s_waitcnt lgkmcnt(0)
 // colour indices of the four pixels of a column quad of row y at scale 0 (pa / pb: the quad's pack words — or, with --dither,
 // its map and subpalette-base words; bw: the word of the candidate's won-pixel bitmap that holds the quad's four bits)
 template <bool BASE>
-__device__ __forceinline__ void h2_resolve(const SparseParams &P, const uint4 pa, const uint4 pb, const uint32_t bw, const int g, const uint32_t crgb, uint32_t (&ci)[4]) {
-    if (P.use_maps) resolve4_maps(pa.x, pa.y, BASE ? 0xffffffffu : P.slot_ci, (uint32_t)P.ncol, ci);
+__device__ __forceinline__ void h2_resolve(const SparseParams &P, const uint4 pa, const uint4 pb, const uint32_t bw, const int g, const uint32_t crgb, const bool um, uint32_t (&ci)[4]) {
+    if (um) resolve4_maps(pa.x, pa.y, BASE ? 0xffffffffu : P.slot_ci, (uint32_t)P.ncol, ci);
     else if (P.perceptual && !BASE) { // four consecutive pixels of a row: four consecutive bits (W = 256: a row is eight words)
         const uint32_t b4 = (bw >> ((g & 7) << 2)) & 0xfu;
         ci[0] = (b4 & 1u) ? (uint32_t)P.ncol : (pa.x >> 24); ci[1] = (b4 & 2u) ? (uint32_t)P.ncol : (pa.z >> 24);
@@ -110,8 +110,14 @@ __device__ __forceinline__ void sparse_h2_load_lut(const SparseParams &P, float 
     lds_order();
 }
 // lut_ready: the caller has loaded the colour table for this wave (the dispatch, which runs two forms over one list)
-template <bool S0, bool BASE, bool ONE = false>
-__device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int list, const int bx, const int gx, H2Shared &sh, const int nfree = 0, const int ord = 0, const bool lut_ready = false) {
+// UM (scale 0): where the colour indices come from.  -1: SparseParams::use_maps, tested as the kernel runs — the body then holds
+// the pack input and the --dither map input both; 0 / 1: the launch knows (the host sets use_maps from the context's dither flag
+// and picks the kernel by it), and the body holds the one input.
+// i_begin / i_end: the virtual item indices the launch's blocks stride over (multiples of 16: whole waves; the list by default).
+// The kernels of one form (k_sparse_h2_one / k_sparse_h2_full) hand each form its own waves: no block meets the other form's.
+template <bool S0, bool BASE, bool ONE = false, int UM = -1>
+__device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int list, const int bx, const int gx, H2Shared &sh, const int nfree = 0, const int ord = 0, const bool lut_ready = false,
+                                               const int i_begin = 0, const int i_end = 0x7fffffff) {
     static_assert(!ONE || (S0 && !BASE), "the one-plane form is the candidates' at scale 0");
     // staged planes: the three H outputs + the XYB input, which the V pass reads in the R4 layout (at scale 0 it is looked up
     // here; at the other scales it is the downscale's output in the C4 layout, and rewriting it from here — whole lines,
@@ -130,7 +136,8 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
     const int W = G.sw[s], H = G.sh[s];
     const int lane = threadIdx.x;
     const int count = P.item_count[list];
-    if (bx * 16 >= count) return;
+    const int cend = min(count, i_end);
+    if (i_begin + bx * 16 >= cend) return;
     if (S0 && !lut_ready) sparse_h2_load_lut(P, s_lut);
     const float n2_0 = P.K.n2[0], n2_1 = P.K.n2[1], n2_2 = P.K.n2[2];
     const float mp_0 = -P.K.d1[0], mp_1 = -P.K.d1[1], mp_2 = -P.K.d1[2];
@@ -141,7 +148,7 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
     const int ntri = count / 3;                                            // triples of the list (the scan writes whole triples)
     float *const trash = P.trash + (lane << 2);
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i0 = bx * 16; i0 < count; i0 += gx * 16) { // grid-stride over item quads
+    for (int i0 = i_begin + bx * 16; i0 < cend; i0 += gx * 16) { // grid-stride over item quads
         if (nf > 0 && (((min(i0 + 16, count) - 1) / ntri < nf) != ONE)) continue; // the other form's wave
         const int qi = i0 + (lane >> 2);
         const bool valid = qi < count;
@@ -155,7 +162,7 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
         const uint32_t crgb = (S0 && !BASE) ? __float_as_uint(P.cand_tab[8 * (size_t)k + 6]) : 0u;
         const float4 *in1 = reinterpret_cast<const float4 *>(P.img1C4 + G.src_off[s] + (size_t)ch * ns) + y;   // C4: + g*H
         const uint4 *pk = S0 ? reinterpret_cast<const uint4 *>(P.packC4) + 2 * (size_t)y : nullptr;            // + g*2H
-        const bool um = S0 && P.use_maps;
+        const bool um = S0 && (UM < 0 ? P.use_maps != 0 : UM > 0);
         const uint32_t *mw = um ? reinterpret_cast<const uint32_t *>(BASE ? P.bmapC4 : P.mapsC4 + (size_t)(k - P.k0) * ns) + y : nullptr; // C4 bytes: word (g*H + y)
         const uint32_t *sw = um ? reinterpret_cast<const uint32_t *>(P.subC4) + y : nullptr;
         // the row's words of the candidate's won-pixel bitmap (--perceptual-palettes); any readable words otherwise: the load is part of every prefetch
@@ -194,7 +201,7 @@ __device__ __forceinline__ void sparse_h2_body(const SparseParams &P, const int 
         };
         auto convert = [&](const int g, const uint4 wa, const uint4 wb, const uint32_t wbm, float4 &d2) { // scale 0: XYB of quad g
             uint32_t ci[4];
-            h2_resolve<BASE>(P, wa, wb, wbm, g, crgb, ci);
+            h2_resolve<BASE>(P, wa, wb, wbm, g, crgb, um, ci);
             const float *lut = s_lut + ch * lstr;
             d2.x = ci[0] == (uint32_t)P.ncol ? cand_v : lut[ci[0]]; d2.y = ci[1] == (uint32_t)P.ncol ? cand_v : lut[ci[1]];
             d2.z = ci[2] == (uint32_t)P.ncol ? cand_v : lut[ci[2]]; d2.w = ci[3] == (uint32_t)P.ncol ? cand_v : lut[ci[3]];
@@ -366,7 +373,7 @@ __device__ __forceinline__ void sparse_h2q_body(const SparseParams &P, const int
         };
         auto convert = [&](const int g, const uint4 wa, const uint4 wb, const uint32_t wbm, float4 &d2) {
             uint32_t ci[4];
-            h2_resolve<BASE>(P, wa, wb, wbm, g, crgb, ci);
+            h2_resolve<BASE>(P, wa, wb, wbm, g, crgb, um, ci);
             const float *lut = s_lut + ch * lstr;
             d2.x = ci[0] == (uint32_t)P.ncol ? cand_v : lut[ci[0]]; d2.y = ci[1] == (uint32_t)P.ncol ? cand_v : lut[ci[1]];
             d2.z = ci[2] == (uint32_t)P.ncol ? cand_v : lut[ci[2]]; d2.w = ci[3] == (uint32_t)P.ncol ? cand_v : lut[ci[3]];
@@ -1094,7 +1101,21 @@ __device__ __forceinline__ void sparse_v2_base_split_body(const SparseParams &P,
 #undef SNES_VSTEP
 
 // entry points: the H pass takes the lists of the wide scales (grid.y = list), the V pass the wide scales (grid.y = scale)
-template <bool BASE>
+// Whether a scale-0 list of the candidates is read channel-major with the one-plane form for its SSIM-free channels, and if so
+// how many those are and the channel order (sparse_h2_body, nfree / ord).
+// count % 3: the channel-major read takes the list for whole triples (v, v + 1, v + 2 = channels 0, 1, 2 of one (candidate,
+// group)).  scan_publish is the only writer of the candidates' lists and writes nothing else; a second writer has to
+// keep that: this test is a consistency guard, not a proof, and a list of another make with a count that happens to
+// be a multiple of three would go through the remap unnoticed.
+__device__ __forceinline__ bool sparse_h2_forms(const SparseParams &P, const int count, int &nfree, int &ord) {
+    nfree = 0; ord = 0;
+    if (!(P.h_planes && !P.full_sums && (P.G.sw[0] >> 6) == 4 && count % 3 == 0)) return false;
+    int pos = 0;
+    for (int c = 0; c < 3; c++) if (!sum_class_has_ssim(P.G.nscales, c, 0)) { ord |= c << (2 * pos++); nfree++; }
+    for (int c = 0; c < 3; c++) if (sum_class_has_ssim(P.G.nscales, c, 0)) ord |= c << (2 * pos++);
+    return nfree > 0;
+}
+template <bool BASE, int UM = -1>
 __device__ __forceinline__ void sparse_h2_dispatch(const SparseParams &P, const int list, const int bx, const int gx) {
     const int s = list / kColBuckets;
     if (s >= P.G.nscales || P.G.sw[s] < 64 || (list % kColBuckets) >= (P.G.sw[s] >> 6)) return;
@@ -1107,29 +1128,59 @@ __device__ __forceinline__ void sparse_h2_dispatch(const SparseParams &P, const 
     // SSIM-free channel's items (B at scales 1 and 2 of a 256x128 image), so those scales write every plane.
     if constexpr (!BASE) {
         const int count = P.item_count[list];
-        // count % 3: the channel-major read takes the list for whole triples (v, v + 1, v + 2 = channels 0, 1, 2 of one (candidate,
-        // group)).  scan_publish is the only writer of the candidates' lists and writes nothing else; a second writer has to
-        // keep that: this test is a consistency guard, not a proof, and a list of another make with a count that happens to
-        // be a multiple of three would go through the remap unnoticed.
-        if (P.h_planes && !P.full_sums && (P.G.sw[0] >> 6) == 4 && count % 3 == 0) {
-            int nfree = 0, ord = 0, pos = 0;
-            for (int c = 0; c < 3; c++) if (!sum_class_has_ssim(P.G.nscales, c, 0)) { ord |= c << (2 * pos++); nfree++; }
-            for (int c = 0; c < 3; c++) if (sum_class_has_ssim(P.G.nscales, c, 0)) ord |= c << (2 * pos++);
-            if (nfree > 0) {
-                if (bx * 16 >= count) return;
-                extern __shared__ float s_lut[];
-                sparse_h2_load_lut(P, s_lut); // once, for both forms
-                sparse_h2_body<true, false, true>(P, list, bx, gx, sh, nfree, ord, true);
-                sparse_h2_body<true, false, false>(P, list, bx, gx, sh, nfree, ord, true);
-                return;
-            }
+        int nfree, ord;
+        if (sparse_h2_forms(P, count, nfree, ord)) {
+            if (bx * 16 >= count) return;
+            extern __shared__ float s_lut[];
+            sparse_h2_load_lut(P, s_lut); // once, for both forms
+            sparse_h2_body<true, false, true, UM>(P, list, bx, gx, sh, nfree, ord, true);
+            sparse_h2_body<true, false, false, UM>(P, list, bx, gx, sh, nfree, ord, true);
+            return;
         }
     }
-    sparse_h2_body<true, BASE>(P, list, bx, gx, sh);
+    sparse_h2_body<true, BASE, false, UM>(P, list, bx, gx, sh);
+}
+// One kernel per form (SNES_H_FORMS).  A kernel's register count — and with it the waves a SIMD holds, which is
+// what this chain of dependent iterations lives on — is that of the largest body it holds, run or not: the kernels above
+// hold every form and take the full scale-0 form's (two waves per SIMD) for all of them.
+// The candidates' wide scales from 1 on: the one body those lists ever run.  list: kColBuckets and up (scale 0 is not this kernel's).
+__device__ __forceinline__ void sparse_h2_rest(const SparseParams &P, const int list, const int bx, const int gx) {
+    const int s = list / kColBuckets;
+    if (s == 0 || s >= P.G.nscales || P.G.sw[s] < 64 || (list % kColBuckets) >= (P.G.sw[s] >> 6)) return;
+    __shared__ H2Shared sh;
+    sparse_h2_body<false, false>(P, list, bx, gx, sh);
+}
+// Scale 0 of the candidates, one form per kernel: ONE takes the waves whose 16 items are all of an SSIM-free channel (virtual
+// indices below nfree * count / 3, whole waves), the full form the rest, from the first wave that holds another item — the cut
+// of sparse_h2_body's class rule, which is monotone in the wave index.  Each kernel's blocks stride over its own waves only.
+// A list that is not read channel-major (sparse_h2_forms) is the full kernel's whole.
+template <bool ONE, int UM>
+__device__ __forceinline__ void sparse_h2_form(const SparseParams &P, const int list, const int bx, const int gx) {
+    if (list >= kColBuckets || P.G.sw[0] < 64 || list >= (P.G.sw[0] >> 6)) return;
+    __shared__ H2Shared sh;
+    const int count = P.item_count[list];
+    int nfree, ord;
+    if (!sparse_h2_forms(P, count, nfree, ord)) { if constexpr (!ONE) sparse_h2_body<true, false, false, UM>(P, list, bx, gx, sh); return; }
+    const int cut = nfree >= 3 ? ((count + 15) & ~15) : ((nfree * (count / 3)) & ~15); // first item of the first wave that is not ONE's
+    if constexpr (ONE) sparse_h2_body<true, false, true, UM>(P, list, bx, gx, sh, nfree, ord, false, 0, cut);
+    else sparse_h2_body<true, false, false, UM>(P, list, bx, gx, sh, nfree, ord, false, cut);
+}
+// how many of the three channels take the one-plane form at scale 0: the host's restatement (sum_class_host), for the two grids
+inline int h2_free_channels(const Geom &G) {
+    int n = 0;
+    if ((G.sw[0] >> 6) == 4) for (int ch = 0; ch < 3; ch++) if (!(kSumClassesHost.m[sum_class_host(kSumMasksHost.m[G.nscales][ch][0])] & kSumSsim)) n++;
+    return n;
 }
 __global__ __launch_bounds__(64) void k_sparse_h2(SparseParams P) { sparse_h2_dispatch<false>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
-// the lists from list0 on (the launch that follows the downscale when scale 0's lists, which do not read it, went ahead beside it)
-__global__ __launch_bounds__(64) void k_sparse_h2_from(SparseParams P, int list0) { sparse_h2_dispatch<false>(P, list0 + (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
+// the same with the map input of scale 0 decided by the launch (UM = the context's dither flag)
+template <bool UM> __global__ __launch_bounds__(64) void k_sparse_h2_um(SparseParams P) { sparse_h2_dispatch<false, UM ? 1 : 0>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
+// scale 0's lists (grid.y = column bucket), a kernel per form: k_sparse_h2_one directly in front of k_sparse_h2_full on one stream
+template <int UM> __global__ __launch_bounds__(64) void k_sparse_h2_one(SparseParams P) { sparse_h2_form<true, UM>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
+template <int UM> __global__ __launch_bounds__(64) void k_sparse_h2_full(SparseParams P) { sparse_h2_form<false, UM>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
+// the lists from list0 on (the launch that follows the downscale when scale 0's lists, which do not read it, went ahead beside it):
+// list0 = kColBuckets, always — the body of scales 1.. alone; k_sparse_h2_from_all: inside the kernel of every form (SNES_H_FORMS bit 0 off)
+__global__ __launch_bounds__(64) void k_sparse_h2_from(SparseParams P, int list0) { sparse_h2_rest(P, list0 + (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(64) void k_sparse_h2_from_all(SparseParams P, int list0) { sparse_h2_dispatch<false>(P, list0 + (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }
 __global__ __launch_bounds__(64) void k_sparse_h2q(SparseParams P) { sparse_h2q_dispatch<false>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); } // short lists
 __global__ __launch_bounds__(64) void k_sparse_h2q_base(SparseParams P) { sparse_h2q_dispatch<true>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); } // B: a single image is a short list
 __global__ __launch_bounds__(64) void k_sparse_h2_base(SparseParams P) { sparse_h2_dispatch<true>(P, (int)blockIdx.y, (int)blockIdx.x, (int)gridDim.x); }

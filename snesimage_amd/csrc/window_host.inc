@@ -122,7 +122,7 @@ int32_t window_make_child(snesimage_ctx *c, snesimage_ctx **out) {
     k->dither = c->dither; k->perceptual = c->perceptual; k->nes = c->nes; k->G = c->G; k->K = c->K; k->npx = c->npx; k->src_floats = c->src_floats; k->fast_mask = c->fast_mask;
     k->chunk = kMemberCand; k->nlanes = 1;
     k->sp.enabled = true; k->sp.side = false; k->sp.lpt = c->sp.lpt; k->sp.down1 = c->sp.down1; k->sp.h2q_max = c->sp.h2q_max; k->sp.scan4_max = c->sp.scan4_max; k->sp.vsplit = c->sp.vsplit; k->sp.down_tiles = c->sp.down_tiles; k->sp.tiles_grid = c->sp.tiles_grid; k->sp.h0_min = c->sp.h0_min; k->sp.hgrid = c->sp.hgrid; k->sp.min_n = 1;
-    k->sp.weight_mask = c->sp.weight_mask; k->sp.h_planes = c->sp.h_planes; k->sp.v2_pair = c->sp.v2_pair; k->sp.debug_poison = c->sp.debug_poison; // (a slot context reads no environment: the parent's switches, or SNES_H_PLANES=0 would not reach a window)
+    k->sp.weight_mask = c->sp.weight_mask; k->sp.h_planes = c->sp.h_planes; k->sp.v2_pair = c->sp.v2_pair; k->sp.h_forms = c->sp.h_forms; k->sp.debug_poison = c->sp.debug_poison; // (a slot context reads no environment: the parent's switches, or SNES_H_PLANES=0 would not reach a window)
     k->d_orig = c->d_orig; k->d_tile_pal = c->d_tile_pal; k->d_colors = c->d_colors; k->d_map = c->d_map; k->d_eotf = c->d_eotf; k->d_lab_eotf = c->d_lab_eotf;
     k->d_pal_rgb8 = c->d_pal_rgb8; k->d_pal_lin = c->d_pal_lin; k->d_pal_xyb = c->d_pal_xyb; k->d_pal_lab = c->d_pal_lab;
     k->d_img1C4 = c->d_img1C4; k->d_mu1R4 = c->d_mu1R4; k->d_sd1R4 = c->d_sd1R4; k->d_a1R4 = c->d_a1R4; k->d_r1R4 = c->d_r1R4; k->d_labpx = c->d_labpx; k->d_labpxT = c->d_labpxT; k->d_target = c->d_target; k->d_labpx_t = c->d_labpx_t; k->d_labpxT_t = c->d_labpxT_t; k->od_n = c->od_n; memcpy(k->od_tab, c->od_tab, sizeof k->od_tab);
